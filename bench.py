@@ -12,7 +12,9 @@
 --config c5: sampled sub-network (ks=7, e=6, d=2, pixel_d=2) 4x inference over the 14 Set14 image sizes, eval mode,
     images of equal size batched together (eval_ofa_net_sr.py); a "step" is one pass over the 14 images.
 
-Prints ONE JSON line on rank 0.  Besides the contract fields it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...); the fields below are measured only with --full (null
+otherwise), since each of them costs runs of its own:
   roofline      the kernel of the HIP library with the largest total time (ALL library kernels compete, on whichever stream
                 they ran; ranked by the committed SERIALIZED trace of this command -- the concurrent ranking flips between
                 runs -- with the next two as `runners_up`), timed live with HIP events attached to each kernel's own dispatch
@@ -30,6 +32,14 @@ Prints ONE JSON line on rank 0.  Besides the contract fields it carries
                 complete leg of its own: value, ms_per_step, roofline, pointwise, kernels (`--dtype f32` makes it the
                 headline of the line instead);
   cpu_baseline  the CPU oracle port of the same training step timed on the host cores in this run.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32), before any --full leg runs:
+  training (c3, c2)  sr_output (the network's output), loss, parameters and gradients (every parameter of the net in
+                     named_parameters() order, flattened and concatenated; zeros for a gradient left None by the sampled
+                     sub-network) after the step's Adam update;
+  inference (c5)     sr_output_<b>, the output of size bucket b.
+Inputs, weights and sub-network seeds depend only on the arguments, so two builds can be compared file for file.  Above
+64 MB in all, every array is cut to the same fraction of its elements, chosen by a fixed seed (flattened, in index order).
 """
 import argparse
 import importlib
@@ -61,6 +71,11 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=16, help="images per GPU (reference train_batch_size 16)")
     ap.add_argument("--lr-size", type=int, default=None, help="LR crop side (c3: 64, c2: 48)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
+    ap.add_argument("--full", action="store_true", help="also measure roofline / kernels / pointwise (profiled steps), the "
+                                                        "fp32 leg and the CPU baseline (c3); the --no-* switches below "
+                                                        "drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, 64 MB at most)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32-activation leg of the c3 line")
@@ -76,7 +91,10 @@ def parse(argv=None):
                          "replayed graph loses part of the two-stream overlap -- so it is not the default")
     ap.add_argument("--cpu-images", type=int, default=2)
     ap.add_argument("--cpu-steps", type=int, default=2)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def subnet_seed(step, sub=0):
@@ -123,6 +141,7 @@ class TrainWorkload(object):
         # step (forward, loss, backward, side-stream join, Adam) is captured once into a hipGraph and replayed (opt-in:
         # measured slower than the eager step here); c3 samples a new sub-network per step (3^16 kernel-size assignments)
         self.graph = None
+        self.keep_output, self.output = False, None   # --dump-outputs: hold the network output of the latest step
         self.want_graph = bool(graph_step) and self.fixed is not None and world == 1 and not h2d
         self.opt = torch.optim.Adam([{"params": decay, "weight_decay": 3e-5}, {"params": no_decay, "weight_decay": 0}],
                                     lr=1e-3, fused=True if os.environ.get("OFASR_FUSED_ADAM", "1") != "0" else None,
@@ -185,6 +204,8 @@ class TrainWorkload(object):
             with torch.autocast("cuda", dtype=self.act_dtype):
                 out = self.net(self.lr)
             loss = F.mse_loss(out.float(), self.hr)
+        if self.keep_output:
+            self.output = out.detach()
         if self.reducer is not None:
             self.reducer.arm()           # (a no-op without OFASR_DP_OVERLAP=1: two-bucket overlapped exchange)
         loss.backward()
@@ -249,6 +270,39 @@ def timed(fn, warmup, steps, fence):
         last = fn(warmup + i)
     fence()
     return time.perf_counter() - t0, last
+
+
+DUMP_BYTES = 60 * 10 ** 6   # array data of --dump-outputs: with the .npy headers under 64 MB
+
+
+def step_outputs(wl, last):
+    """what the last timed step handed its caller, as host float32 arrays (--dump-outputs; names in the module doc)"""
+    import torch
+
+    def host(t):
+        return t.detach().float().cpu().numpy()
+
+    if isinstance(wl, EvalWorkload):
+        return {"sr_output_%d" % b: host(o) for b, o in enumerate(last)}
+    params = list(wl.net.parameters())
+    return {"sr_output": host(wl.output), "loss": host(last),
+            "parameters": host(torch.cat([p.reshape(-1) for p in params])),
+            "gradients": host(torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).reshape(-1)
+                                         for p in params]))}
+
+
+def write_outputs(arrays, out_dir, budget=DUMP_BYTES):
+    """out_dir/<name>.npy.  Above `budget` bytes in all, every array keeps the same fraction of its elements: a choice
+    fixed by the seed (flattened, in index order), so two runs with the same arguments stay comparable element for
+    element."""
+    import numpy as np
+    keep = min(1.0, budget / float(sum(a.nbytes for a in arrays.values())))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        k = max(1, int(a.size * keep))
+        if k < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def profile_steps(M, fn, first, nprof):
@@ -465,14 +519,16 @@ def main():
 
     S = args.lr_size or (48 if args.config == "c2" else 64)
 
-    def leg(dtype, warmup, steps, h2d):
-        """one timed leg (warm-up, EXACTLY `steps` timed steps between two fences, max over ranks) + its profiled steps"""
+    def leg(dtype, warmup, steps, h2d, dump=False):
+        """one timed leg (warm-up, EXACTLY `steps` timed steps between two fences, max over ranks) + with --full its
+        profiled steps; with `dump` also the last timed step's outputs (host arrays, taken before any profiled step)"""
         if args.config == "c5":
             wl = EvalWorkload(M, dev, dtype, graphs=not args.no_graphs)
             per_step = wl.n_images
         else:
             wl = TrainWorkload(M, args.config, dev, args.batch, S, dtype, world, rank, h2d,
                                graph_step=args.config == "c2" and args.graph_step)
+            wl.keep_output = dump   # before a capture, so that a replayed step refreshes the held output too
             per_step = args.batch
             if wl.want_graph:
                 wl.capture()
@@ -481,10 +537,12 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        outputs = step_outputs(wl, last) if dump else None
         out = {"value": round(world * per_step * steps / dt, 2), "unit": "images/s",
                "ms_per_step": round(1e3 * dt / steps, 3), "steps": steps, "warmup": warmup, "dtype": dtype,
                "final_loss": float(last.detach()) if args.config != "c5" else None}
-        if not args.no_roofline:   # every rank runs the profiled steps (they contain the gradient all-reduce); rank 0 reports
+        # every rank runs the profiled steps (they contain the gradient all-reduce); rank 0 reports
+        if args.full and not args.no_roofline:
             nprof = min(steps, 6)
             # (a replayed graph runs no host code, so the per-dispatch events need the eager launches of the same kernels)
             prof_step = (lambda i: wl.step(i, eager=True)) if args.config == "c5" else \
@@ -498,20 +556,23 @@ def main():
                  "graphed": args.config == "c5" and wl.graphed is not None, "per_step": per_step}
         del wl
         torch.cuda.empty_cache()
-        return out, extra
+        return out, extra, outputs
 
-    main_leg, info = leg(args.dtype, args.warmup, args.steps, args.h2d)
+    main_leg, info, outputs = leg(args.dtype, args.warmup, args.steps, args.h2d,
+                                  dump=args.dump_outputs is not None and rank == 0)
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     value, ms_per_step, final_loss = main_leg["value"], main_leg["ms_per_step"], main_leg["final_loss"]
     roofline, kernel_table, pointwise = main_leg["roofline"], main_leg["kernels"], main_leg["pointwise"]
     per_step = info["per_step"]
 
     fp32 = None
-    if args.config == "c3" and args.dtype != "f32" and not args.no_fp32:
+    if args.full and args.config == "c3" and args.dtype != "f32" and not args.no_fp32:
         # the reference computes in fp32: the same step with fp32 activations, a complete leg of its own
-        fp32, _ = leg("f32", 3, args.fp32_steps, False)
+        fp32, _, _ = leg("f32", 3, args.fp32_steps, False)
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c3":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c3":
         cpu_baseline = run_cpu_baseline(args, S)
 
     if rank == 0:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Aggregate a rocprofv3 kernel-trace CSV over the last N training steps (steps are delimited by the
-optimizer's multi_tensor_apply launches), optionally skipping the last `skip` steps (bench.py ends with 7 instrumented
-per-op steps for the roofline figure).  usage: trace_steps.py <kernel_trace.csv> [nsteps] [top] [skip] [summary.json key]
+optimizer's multi_tensor_apply launches), optionally skipping the last `skip` steps (bench.py --full ends with 7
+instrumented per-op steps for the roofline figure).  usage: trace_steps.py <kernel_trace.csv> [nsteps] [top] [skip] [summary.json key]
 With the last two arguments the per-kernel averages are also merged into summary.json under `key` (e.g. "bf16", "f32"),
 keyed by the kernel symbol as bench.py's kernel table spells it (no "void ofasr::", no parameter list): this is the
 file bench.py's roofline.trace_avg_us is read from."""

@@ -62,10 +62,11 @@ def test_step_is_bit_reproducible_and_stream_schedule_invariant():
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the driver's contract keys plus `roofline` and `cpu_baseline` (a short run)."""
+    """bench.py --full prints ONE JSON line with the driver's contract keys plus `roofline` and `cpu_baseline` (a short
+    run)."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--cpu-steps", "1", "--cpu-images", "1"], capture_output=True, text=True, timeout=900)
+                          "--full", "--cpu-steps", "1", "--cpu-images", "1"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -85,3 +86,30 @@ def test_bench_contract_line():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("port", "reference") and c["value"] > 0 and j["value"] > 100 * c["value"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain bench.py run measures the headline only (no profiled steps, fp32 leg or CPU baseline); --dump-outputs
+    writes what its last timed step computed: the network output, the loss, the parameters and gradients after Adam."""
+    import json
+    import numpy as np
+    d = str(tmp_path / "out")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["metric"] == "sr_training_images_per_sec_4x_64to256" and j["unit"] == "images/s" and j["dtype"] == "bf16"
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["higher_is_better"] is True
+    assert j["ms_per_step"] > 0 and abs(j["value"] - 16 * 1e3 / j["ms_per_step"]) <= 1e-2 * j["value"]
+    for k in ("roofline", "kernels", "pointwise", "fp32", "cpu_baseline"):
+        assert j[k] is None, k
+    files = sorted(os.listdir(d))
+    assert files == ["gradients.npy", "loss.npy", "parameters.npy", "sr_output.npy"], files
+    a = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 * 10 ** 6
+    assert all(v.dtype == np.float32 and np.all(np.isfinite(v)) for v in a.values())
+    assert a["sr_output"].shape == (16, 3, 256, 256)
+    assert a["loss"].shape == () and float(a["loss"]) == j["config"]["final_loss"]
+    assert a["parameters"].size == a["gradients"].size > 2 * 10 ** 6 and np.any(a["gradients"] != 0)
