@@ -14,6 +14,37 @@ sys.path.insert(0, ROOT)
 PKG = "ofa-for-super-resolution_amd"
 
 
+STATIC_WEIGHTS = "static_state_dict.pth"
+
+
+def input_key(upscale):
+    """the data provider's LR image for an upscale factor (ask the net, not pixel_d)"""
+    return "%dx_down_image" % upscale
+
+
+def export_static(supernet, out_dir):
+    """the supernet's active sub-network as a static network: out_dir/net_config.json + its state dict"""
+    import json
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sub = supernet.get_active_subnet(preserve_weight=True)
+    with open(os.path.join(out_dir, "net_config.json"), "w") as f:
+        json.dump(sub.config, f, indent=1)
+    torch.save({"state_dict": sub.state_dict()}, os.path.join(out_dir, STATIC_WEIGHTS))
+    return sub
+
+
+def load_static(in_dir):
+    """the static network export_static() wrote (on the CPU; the run manager moves it)"""
+    import json
+    import torch
+    st = importlib.import_module(PKG + ".imagenet_codebase.networks.sr_static")
+    with open(os.path.join(in_dir, "net_config.json")) as f:
+        net = st.build_static_net(json.load(f))
+    net.load_state_dict(torch.load(os.path.join(in_dir, STATIC_WEIGHTS), map_location="cpu", weights_only=True)["state_dict"])
+    return net
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", default=None)
@@ -26,25 +57,37 @@ def main():
     ap.add_argument("--synthetic", action="store_true", help="evaluate on synthetic Set14-sized images when the "
                                                              "dataset directory is absent")
     ap.add_argument("--batch1", action="store_true", help="the reference's batch-1 pass instead of size buckets")
+    ap.add_argument("--export", default=None, metavar="DIR",
+                    help="also write the selected sub-network as a static network: DIR/net_config.json + DIR/%s" % STATIC_WEIGHTS)
+    ap.add_argument("--static", default=None, metavar="DIR", help="evaluate the static network exported to DIR "
+                                                                  "(instead of a supernet sub-network)")
     a = ap.parse_args()
     import torch
     rm = importlib.import_module(PKG + ".imagenet_codebase.run_manager")
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
     dop = importlib.import_module(PKG + ".elastic_nn.modules.dynamic_op")
     dop.DynamicSeparableConv2d.KERNEL_TRANSFORM_MODE = 1
-    net = nets.OFAMobileNetS4(ks_list=[3, 5, 7], expand_ratio_list=[3, 4, 6], depth_list=[2, 3, 4],
-                              pixelshuffle_depth_list=[1, 2])
+    if a.static:
+        net = load_static(a.static)
+    else:
+        net = nets.OFAMobileNetS4(ks_list=[3, 5, 7], expand_ratio_list=[3, 4, 6], depth_list=[2, 3, 4],
+                                  pixelshuffle_depth_list=[1, 2])
     # Set14-like sizes (HR sides multiples of 4)
     cfg = rm.Div2K_SetXXRunConfig(n_epochs=1, init_lr=1e-3, opt_type="adam", no_decay_keys="bn#bias",
                                   label_smoothing=0.0, train_batch_size=1, test_batch_size=1, image_size=256,
                                   test_sizes=[(480, 500), (576, 720), (512, 512), (288, 352), (360, 248), (276, 276), (360, 500), (288, 352),
                                               (512, 512), (512, 512), (512, 768), (512, 512), (656, 528), (388, 584)],
                                   n_train_batches=1, allow_synthetic=True if a.synthetic else None)
-    mgr = rm.SRRunManager(a.path, net, cfg, init=a.checkpoint is None, mix_prec=a.mix_prec, num_gpus=1)
-    if a.checkpoint:
-        net.load_weights_from_net(torch.load(a.checkpoint, map_location="cpu", weights_only=True)["state_dict"])
-    net.set_active_subnet(ks=a.ks, e=a.expand, d=a.depth, pixel_d=a.pixelshuffle_depth)
-    key = "4x_down_image" if a.pixelshuffle_depth == 2 or net.COMPAT_REFERENCE_INDEXING else "2x_down_image"
+    mgr = rm.SRRunManager(a.path, net, cfg, init=a.checkpoint is None and not a.static, mix_prec=a.mix_prec, num_gpus=1)
+    if a.static:
+        key = input_key(net.upscale)
+    else:
+        if a.checkpoint:
+            net.load_weights_from_net(torch.load(a.checkpoint, map_location="cpu", weights_only=True)["state_dict"])
+        net.set_active_subnet(ks=a.ks, e=a.expand, d=a.depth, pixel_d=a.pixelshuffle_depth)
+        key = "4x_down_image" if a.pixelshuffle_depth == 2 or net.COMPAT_REFERENCE_INDEXING else "2x_down_image"
+        if a.export:
+            export_static(net, a.export)
     import time
     n_img = sum(b["image"].shape[0] for b in cfg.test_loader)
 

@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 300 /* round 3 */
+#define OFASR_VERSION 301 /* + ofasr_mbconv_infer_f32_* */
 
 typedef enum {
     OFASR_OK = 0,
@@ -279,6 +279,20 @@ int ofasr_mbconv_infer_run(const ofasr_mbconv_desc* d, const void* x, void* out,
                            size_t operand_bytes, void* scratch, size_t scratch_bytes, void* stream);
 int ofasr_mbconv_infer(const ofasr_mbconv_desc* d, const void* x, void* out, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same block at fp32 (csrc/mbfused_f32.hip): d->dtype == OFASR_F32, exact fp32 products on the fp32 matrix
+ * instruction, fp32 depthwise, BN folded in fp32.  Supported: Cin = Cout = 64, mid % 32 == 0, K in {3,5,7}, eval-mode BN,
+ * any N, H, W with 64 * H * W * 4 < 2^31 (ofasr_mbconv_infer_f32_supported; otherwise OFASR_ERR_UNSUPPORTED and the
+ * caller uses ofasr_mbconv_fwd).  Same two steps as above; the scratch size is 0 (kept for the shape of the contract).
+ * x and out must not overlap.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_mbconv_infer_f32_supported(const ofasr_mbconv_desc* d);
+size_t ofasr_mbconv_infer_f32_operand_bytes(const ofasr_mbconv_desc* d);
+size_t ofasr_mbconv_infer_f32_scratch_bytes(const ofasr_mbconv_desc* d);
+int ofasr_mbconv_infer_f32_prepare(const ofasr_mbconv_desc* d, void* operands, size_t operand_bytes, void* stream);
+int ofasr_mbconv_infer_f32_run(const ofasr_mbconv_desc* d, const void* x, void* out, const void* operands,
+                               size_t operand_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense KxK convolution (K in {3,5}, stride 1, zero padding K/2, no bias) of the static ConvLayers as an

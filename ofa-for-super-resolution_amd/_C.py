@@ -108,6 +108,11 @@ SIGNATURES = {
     "ofasr_mbconv_infer_scratch_bytes": (_c_sz, [_c_vp]),
     "ofasr_mbconv_infer_prepare": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
     "ofasr_mbconv_infer_run": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
+    "ofasr_mbconv_infer_f32_supported": (_c_int, [_c_vp]),
+    "ofasr_mbconv_infer_f32_operand_bytes": (_c_sz, [_c_vp]),
+    "ofasr_mbconv_infer_f32_scratch_bytes": (_c_sz, [_c_vp]),
+    "ofasr_mbconv_infer_f32_prepare": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
+    "ofasr_mbconv_infer_f32_run": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
     "ofasr_debug_mbfused_tile": (_c_int, [_c_int]),
     "ofasr_debug_mbfused_split": (_c_int, [_c_int]),
     "ofasr_debug_mbconv_bn_bwd_stat": (_c_int, [_c_int]),

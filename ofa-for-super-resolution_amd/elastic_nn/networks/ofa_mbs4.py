@@ -19,6 +19,7 @@ Stage-indexing compatibility.  As committed, the referenc
 reference checkpoints / logs; set it to False for the evidently intended behaviour (pixel_d
 drives the shuffle stage, d the four MB stages).
 """
+import copy
 import random
 
 import torch
@@ -26,8 +27,9 @@ import torch
 from ... import ops
 from ...imagenet_codebase.networks.mobilenet_s4 import MobileNetS4
 from ...imagenet_codebase.networks.proxyless_nets import MobileInvertedResidualBlock
+from ...imagenet_codebase.networks.sr_static import SRNetS4, mb_block_config
 from ...layers import ConvLayer, IdentityLayer
-from ...utils import int2list, make_divisible
+from ...utils import get_net_device, int2list, make_divisible
 from ..modules.dynamic_layers import DynamicMBConvLayer
 
 _N_MB_STAGES = 4
@@ -209,6 +211,48 @@ class OFAMobileNetS4(MobileNetS4):
             assert new_key in own, "%s" % new_key
             own[new_key] = value
         self.load_state_dict(own)
+
+    # ------------------------------------------------------------------ specialized sub-network
+    def get_active_net_config(self):
+        """config of the static SRNetS4 that computes what this supernet computes on its active path
+        (active_block_sequence(): whatever COMPAT_REFERENCE_INDEXING selects); JSON-serializable"""
+        seq = self.active_block_sequence()
+        ch = self.dec_first_conv_block.out_channels
+        mbs = []
+        for kind, m in seq:
+            if kind == "mb":
+                mid = m.active_middle_channel(ch)
+                mbs.append(mb_block_config(ch, m.active_out_channel, m.active_kernel_size, m.active_expand_ratio, mid,
+                                           m.act_func))
+                ch = m.active_out_channel
+        return {
+            "name": SRNetS4.__name__, "bn": self.get_bn_param(), "upscale": self.active_upscale(),
+            "dec_first_conv_block": self.dec_first_conv_block.config,
+            "blocks": mbs + [m.config for kind, m in seq if kind == "shuffle"],
+            "n_mb": len(mbs),
+            "dec_final_conv_blocks": [m.config for kind, m in seq if kind == "res"],
+            "dec_final_output_conv_block": self.dec_final_output_conv_block.config,
+        }
+
+    def get_active_subnet(self, preserve_weight=True):
+        """the active sub-network as a static SRNetS4.  preserve_weight: the MB blocks' weights are the active slices
+        (DynamicMBConvLayer.get_active_subnet: the kernel transform runs on the GPU), the static convs are copies."""
+        if not preserve_weight:
+            net = SRNetS4.build_from_config(self.get_active_net_config())
+            return net.to(get_net_device(self))
+        seq = self.active_block_sequence()
+        ch = self.dec_first_conv_block.out_channels
+        mbs = []
+        for kind, m in seq:
+            if kind == "mb":
+                mbs.append(MobileInvertedResidualBlock(m.get_active_subnet(ch, preserve_weight=True), IdentityLayer(ch, ch)))
+                ch = m.active_out_channel
+        net = SRNetS4(copy.deepcopy(self.dec_first_conv_block), mbs,
+                      [copy.deepcopy(m) for kind, m in seq if kind == "res"],
+                      [copy.deepcopy(m) for kind, m in seq if kind == "shuffle"],
+                      copy.deepcopy(self.dec_final_output_conv_block), self.active_upscale())
+        net.set_bn_param(**self.get_bn_param())
+        return net.to(get_net_device(self)).train(self.training)
 
     # ------------------------------------------------------------- active sub-network control
     def set_active_subnet(self, wid=None, ks=None, e=None, d=None, pixel_d=None):

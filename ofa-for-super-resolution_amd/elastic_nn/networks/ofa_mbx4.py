@@ -15,12 +15,14 @@ COMPAT_REFERENCE_INDEXING (default True) reproduces the reference's stage indexi
 read runtime_depth[0] and both encoder stage j and decoder stage j read runtime_depth[j] (:185-254).
 False gives the intended mapping (pd for both un/shuffle stages, d[0:4] encoder, d[4:8] decoder).
 """
+import copy
 import random
 
 from ...imagenet_codebase.networks.mobilenet_x4 import MobileNetX4
 from ...imagenet_codebase.networks.proxyless_nets import MobileInvertedResidualBlock
+from ...imagenet_codebase.networks.sr_static import SRNetX4, mb_block_config
 from ...layers import ConvLayer, IdentityLayer
-from ...utils import int2list
+from ...utils import get_net_device, int2list
 from ..modules.dynamic_layers import DynamicMBConvLayer
 from .ofa_mbs4 import OFAMobileNetS4
 
@@ -132,6 +134,61 @@ class OFAMobileNetX4(MobileNetX4):
         return "\n".join(lines) + "\n"
 
     load_weights_from_net = OFAMobileNetS4.load_weights_from_net
+
+    # ------------------------------------------------------------------ specialized sub-network
+    def _active_groups(self):
+        """the active blocks of every block group (_depth_of: whatever COMPAT_REFERENCE_INDEXING selects)"""
+        return [[self.blocks[i] for i in self.block_group_info[g][:self._depth_of(g)]] for g in range(10)]
+
+    def _active_mb_configs(self, groups, ch):
+        cfgs = []
+        for blk in (b for g in groups for b in g):
+            m = blk.mobile_inverted_conv
+            cfgs.append(mb_block_config(ch, m.active_out_channel, m.active_kernel_size, m.active_expand_ratio,
+                                        m.active_middle_channel(ch), m.act_func))
+            ch = m.active_out_channel
+        return cfgs
+
+    def _active_upscale(self, groups):
+        return 2 ** len(groups[9]) // 2 ** len(groups[0])   # both stages read the same depth: 1
+
+    def get_active_net_config(self):
+        """config of the static SRNetX4 that computes what this supernet computes on its active path; JSON-serializable"""
+        groups = self._active_groups()
+        enc = self._active_mb_configs(groups[1:5], self.blocks[1].out_channels * 4)
+        dec = self._active_mb_configs(groups[5:9], self.dec_first_conv_block.out_channels)
+        return {
+            "name": SRNetX4.__name__, "bn": self.get_bn_param(), "upscale": self._active_upscale(groups),
+            "blocks": [b.config for b in groups[0]] + enc + dec + [b.config for b in groups[9]],
+            "n_unshuffle": len(groups[0]), "n_enc": len(enc), "n_dec": len(dec),
+            "enc_final_conv_blocks": [c.config for c in self.enc_final_conv_blocks],
+            "dec_first_conv_block": self.dec_first_conv_block.config,
+            "dec_final_conv_blocks": [c.config for c in self.dec_final_conv_blocks],
+            "dec_final_output_conv_block": self.dec_final_output_conv_block.config,
+        }
+
+    def get_active_subnet(self, preserve_weight=True):
+        """the active sub-network as a static SRNetX4 (see OFAMobileNetS4.get_active_subnet)"""
+        if not preserve_weight:
+            return SRNetX4.build_from_config(self.get_active_net_config()).to(get_net_device(self))
+        groups = self._active_groups()
+
+        def extract(gs, ch):
+            out = []
+            for blk in (b for g in gs for b in g):
+                m = blk.mobile_inverted_conv
+                out.append(MobileInvertedResidualBlock(m.get_active_subnet(ch, preserve_weight=True), IdentityLayer(ch, ch)))
+                ch = m.active_out_channel
+            return out
+
+        dc = copy.deepcopy
+        net = SRNetX4([dc(b) for b in groups[0]], extract(groups[1:5], self.blocks[1].out_channels * 4),
+                      [dc(c) for c in self.enc_final_conv_blocks], dc(self.dec_first_conv_block),
+                      extract(groups[5:9], self.dec_first_conv_block.out_channels),
+                      [dc(c) for c in self.dec_final_conv_blocks], [dc(b) for b in groups[9]],
+                      dc(self.dec_final_output_conv_block), self._active_upscale(groups))
+        net.set_bn_param(**self.get_bn_param())
+        return net.to(get_net_device(self)).train(self.training)
 
     # ------------------------------------------------------------- active sub-network control
     def _mb_blocks(self):

@@ -269,6 +269,23 @@ class MBInvertedConvLayer(MyModule):
             x = self.inverted_bottleneck(x)
         return self.point_linear(self.depth_conv(x))
 
+    def composite_eligible(self):
+        """the composite HIP calls (ops.FusedMBConvFn / ops.mbstack / ops.mbconv_infer) can serve this block"""
+        return (self.inverted_bottleneck is not None and self.stride == 1 and self.act_func == "relu6"
+                and all(bn.momentum is not None for bn in (self.inverted_bottleneck.bn, self.depth_conv.bn,
+                                                           self.point_linear.bn)))
+
+    def composite_args(self, in_channels, add_x):
+        """(cfg, params) of the composite call, in the shape of DynamicMBConvLayer.composite_args: the static filter is
+        the whole K x K kernel (chain [K], no transform matrices), params = (w1, g1, b1, wdw, g2, b2, w2, g3, b3)"""
+        bn1, bn2, bn3 = self.inverted_bottleneck.bn, self.depth_conv.bn, self.point_linear.bn
+        K = self.kernel_size
+        cfg = {"mid": self.depth_conv.conv.weight.shape[0], "out": self.out_channels, "K": K, "chain": (K,),
+               "residual": add_x, "bns": (bn1, bn2, bn3), "owner": self, "nparams": 9}
+        params = (self.inverted_bottleneck.conv.weight, bn1.weight, bn1.bias, self.depth_conv.conv.weight, bn2.weight,
+                  bn2.bias, self.point_linear.conv.weight, bn3.weight, bn3.bias)
+        return cfg, params
+
     @property
     def module_str(self):
         ratio = self.expand_ratio if self.mid_channels is None else self.mid_channels // self.in_channels

@@ -745,6 +745,8 @@ def mbconv_infer(x, cfg, w1, g1, b1, wdw, g2, b2, w2, g3, b3, *mats):
     (ofasr_mbconv_infer_prepare / _run, csrc/mbfused.hip).  Returns None when the shape / dtype / BN mode is outside
     what the kernel implements (the caller then takes the composite path)."""
     _gpu(x, w1, wdw, w2)
+    if x.dtype == torch.float32 and F32_INFER_SUPERNET:
+        return mbconv_infer_f32(x, cfg, w1, g1, b1, wdw, g2, b2, w2, g3, b3, *mats)
     if x.dtype not in (torch.float16, torch.bfloat16):
         return None
     x = x.contiguous()
@@ -768,6 +770,43 @@ def mbconv_infer(x, cfg, w1, g1, b1, wdw, g2, b2, w2, g3, b3, *mats):
         sst, ssp, ssn = _ws(L.ofasr_mbconv_infer_scratch_bytes(dp), x.device)
         _C.check(L.ofasr_mbconv_infer_run(dp, _p(x), _p(out), _p(opnd), ctypes.c_size_t(opnd.numel()), ssp, ssn, _stream()),
                  "mbconv_infer_run")
+    return out
+
+
+# The fp32 one-kernel eval-mode block (ofasr_mbconv_infer_f32_*, csrc/mbfused_f32.hip): exact fp32 on the fp32 matrix
+# instruction, the reference's precision.  The specialized static networks (imagenet_codebase/networks/sr_static.py) take
+# it when F32_INFER is on; the supernet's fp32 eval keeps the composite path unless OFASR_MBCONV_F32_INFER_SUPERNET=1.
+F32_INFER = os.environ.get("OFASR_MBCONV_F32_INFER", "1") != "0"
+F32_INFER_SUPERNET = os.environ.get("OFASR_MBCONV_F32_INFER_SUPERNET", "0") != "0"
+
+
+def mbconv_infer_f32(x, cfg, w1, g1, b1, wdw, g2, b2, w2, g3, b3, *mats):
+    """mbconv_infer for fp32 activations; None when ofasr_mbconv_infer_f32_supported says no (the caller then takes the
+    composite path)"""
+    _gpu(x, w1, wdw, w2)
+    if x.dtype != torch.float32:
+        return None
+    x = x.contiguous()
+    L = _C.lib()
+    d = _mbconv_desc(x, cfg, w1, g1, b1, wdw, g2, b2, w2, g3, b3, mats)
+    dp = ctypes.byref(d)
+    if not L.ofasr_mbconv_infer_f32_supported(dp):
+        return None
+    out = torch.empty((x.shape[0], cfg["out"], x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device)
+    bns = cfg["bns"]
+    kind = ("mb_f32", cfg["mid"], cfg["out"], cfg["K"], tuple(cfg["chain"]), int(d.transform),
+            tuple(float(bn.eps) for bn in bns))
+    tensors = (w1, g1, b1, wdw, g2, b2, w2, g3, b3) + tuple(mats) + tuple(t for bn in bns
+                                                                         for t in (bn.running_mean, bn.running_var))
+
+    def prepare(ptr, nbytes):
+        _C.check(L.ofasr_mbconv_infer_f32_prepare(dp, ptr, nbytes, _stream()), "mbconv_infer_f32_prepare")
+
+    with _timed("mbconv_infer_f32"):
+        opnd = _infer_operands(kind, tensors, L.ofasr_mbconv_infer_f32_operand_bytes(dp), x.device, prepare)
+        sst, ssp, ssn = _ws(L.ofasr_mbconv_infer_f32_scratch_bytes(dp), x.device)
+        _C.check(L.ofasr_mbconv_infer_f32_run(dp, _p(x), _p(out), _p(opnd), ctypes.c_size_t(opnd.numel()), ssp, ssn,
+                                              _stream()), "mbconv_infer_f32_run")
     return out
 
 
