@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 301 /* + ofasr_mbconv_infer_f32_* */
+#define OFASR_VERSION 302 /* + ofasr_mbconv_recal_f32_*, ofasr_bn_recal_accumulate */
 
 typedef enum {
     OFASR_OK = 0,
@@ -293,6 +293,30 @@ size_t ofasr_mbconv_infer_f32_scratch_bytes(const ofasr_mbconv_desc* d);
 int ofasr_mbconv_infer_f32_prepare(const ofasr_mbconv_desc* d, void* operands, size_t operand_bytes, void* stream);
 int ofasr_mbconv_infer_f32_run(const ofasr_mbconv_desc* d, const void* x, void* out, const void* operands,
                                size_t operand_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BatchNorm re-calibration (csrc/mbrecal_f32.hip): train-mode BN forward with no backward, every BN normalising with the
+ * mean and biased variance of the current batch.  Running statistics and num_batches_tracked are neither read nor
+ * written; instead each BN adds weight * batch mean into acc[0 .. C) and weight * biased batch variance into
+ * acc[C .. 2C) (caller-owned fp64 accumulators; no host round trip, no float atomics, a fixed summation order).
+ *
+ * ofasr_mbconv_recal_f32   the MB block of ofasr_mbconv_infer_f32 (same descriptor and scope: fp32, Cin = Cout = 64,
+ *                          mid % 32 == 0, K in {3,5,7}, any N / H / W; d->bn_training, running_* and momentum are
+ *                          ignored), weight = d->N.  acc1 / acc2: [2][mid], acc3: [2][64].  out = the block's output
+ *                          with batch statistics (+ x when d->residual).  Recompute passes: y1 and y2 never reach HBM;
+ *                          y3 lives in the workspace (ofasr_mbconv_recal_f32_workspace(d) bytes).  x and out must not
+ *                          overlap.
+ * ofasr_bn_recal_accumulate  for a static conv: the ofasr_bn_stats partials of its output (n_partials slabs, `count`
+ *                          elements per channel) -> the accumulators (times `weight`) and stats [4][C] = mean | invstd |
+ *                          scale | shift for ofasr_bn_act_fwd.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_mbconv_recal_f32_supported(const ofasr_mbconv_desc* d);
+size_t ofasr_mbconv_recal_f32_workspace(const ofasr_mbconv_desc* d);
+int ofasr_mbconv_recal_f32(const ofasr_mbconv_desc* d, const void* x, void* out, double* acc1, double* acc2,
+                           double* acc3, void* workspace, size_t workspace_bytes, void* stream);
+int ofasr_bn_recal_accumulate(const void* partial, int64_t n_partials, int64_t C, double count, double weight,
+                              const float* gamma, const float* beta, double eps, double* acc, float* stats,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense KxK convolution (K in {3,5}, stride 1, zero padding K/2, no bias) of the static ConvLayers as an

@@ -113,6 +113,11 @@ SIGNATURES = {
     "ofasr_mbconv_infer_f32_scratch_bytes": (_c_sz, [_c_vp]),
     "ofasr_mbconv_infer_f32_prepare": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
     "ofasr_mbconv_infer_f32_run": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
+    "ofasr_mbconv_recal_f32_supported": (_c_int, [_c_vp]),
+    "ofasr_mbconv_recal_f32_workspace": (_c_sz, [_c_vp]),
+    "ofasr_mbconv_recal_f32": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ofasr_bn_recal_accumulate": (_c_int, [_c_vp, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp,
+                                           ctypes.c_double, _c_vp, _c_vp, _c_vp]),
     "ofasr_debug_mbfused_tile": (_c_int, [_c_int]),
     "ofasr_debug_mbfused_split": (_c_int, [_c_int]),
     "ofasr_debug_mbconv_bn_bwd_stat": (_c_int, [_c_int]),

@@ -70,6 +70,9 @@ class DynamicMBConvLayer(MyModule):
             self.inverted_bottleneck.conv.active_out_channel = self.active_middle_channel(x.size(1))
         self.depth_conv.conv.active_kernel_size = self.active_kernel_size
         self.point_linear.conv.active_out_channel = self.active_out_channel
+        if ops.RECAL is not None and x.is_cuda and self.inverted_bottleneck is not None and self.stride == 1:
+            # BatchNorm re-calibration (elastic_nn.utils.recalibrate_bn): batch statistics into its accumulators
+            return ops.RECAL.mb_block(x, *self.composite_args(x.size(1), residual is x), residual)
         fused = ops.FUSED_BN and self.act_func == "relu6" and not DynamicBatchNorm2d.SET_RUNNING_STATISTICS
         if self.composite_eligible(x):
             return self._forward_composite(x, residual)

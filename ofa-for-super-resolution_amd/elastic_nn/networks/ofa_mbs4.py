@@ -118,7 +118,7 @@ class OFAMobileNetS4(MobileNetS4):
         active = [self.blocks[idx] for stage in range(_N_MB_STAGES)
                   for idx in self.block_group_info[stage][:self.runtime_depth[stage]]]
         infer = ops.FUSED_INFER and not torch.is_grad_enabled() and not self.training
-        if (ops.FUSED_STACK and active and x.is_cuda and not infer and all(b.stackable(x) for b in active)):
+        if (ops.FUSED_STACK and active and x.is_cuda and not infer and ops.RECAL is None and all(b.stackable(x) for b in active)):
             if torch.is_autocast_enabled() and x.dtype == torch.float32:
                 x = x.to(torch.get_autocast_dtype("cuda"))
             cfgs, params, ch = [], [], x.size(1)

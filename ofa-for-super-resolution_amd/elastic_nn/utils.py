@@ -96,3 +96,58 @@ def set_running_statistics(model, data_loader, input_key="image", device=None, d
     # the .data writes above are invisible to the version counters the inference operand cache (BN-folded weight
     # images) and GraphedEval key on: drop both, or the next eval forward replays the OLD running statistics
     ops.clear_infer_cache()
+
+
+def recalibrate_bn(model, data_loader, input_key="image", device=None, max_batches=None):
+    """set_running_statistics on the HIP kernels.  Same contract: every BatchNorm on the active path gets the
+    batch-size-weighted mean of its per-batch means and biased variances over `data_loader` (the same loader forms,
+    lr_on_device batches included) in its first `c` (active) channels.  Differences: the forwards run at fp32 on the
+    re-calibration kernels (ops.Recal: ofasr_mbconv_recal_f32 for the MB blocks, the fp32 conv kernels +
+    ofasr_bn_recal_accumulate for the static convs) even under autocast; the model is not copied; parameters, inactive
+    channels, num_batches_tracked, momentum and model.training are left as they are.  The statistics accumulate in
+    float64 on the device, so the loop never waits for the host.  `max_batches` stops after that many batches.
+
+    Returns the counters of the run: {'batches', 'images', 'mb_kernel', 'mb_fallback', 'conv'} (mb_fallback: MB blocks
+    outside the one-kernel passes' scope, run per op on the HIP kernels instead)."""
+    from .. import ops
+    from ..utils import device_batch
+
+    device = device or next(model.parameters()).device
+    rc = ops.Recal()
+
+    def refuse(mod, args):   # every BatchNorm must be served by ops.Recal: none may run its own (ATen) forward
+        raise ops._C.OfasrError("recalibrate_bn: %s ran outside the HIP re-calibration path" % type(mod).__name__)
+
+    hooks = [m.register_forward_pre_hook(refuse) for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
+    prev, ops.RECAL = ops.RECAL, rc
+    batches = images = 0
+    try:
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            for batch in data_loader:
+                if max_batches is not None and batches >= max_batches:
+                    break
+                if isinstance(batch, dict):
+                    if input_key not in batch:      # lr_on_device providers hand over {'image_u8'} only
+                        batch = device_batch(batch, device)
+                    x = batch[input_key]
+                else:
+                    x = batch[0]
+                x = x.to(device).float()
+                model(x)
+                batches += 1
+                images += x.size(0)
+    finally:
+        ops.RECAL = prev
+        for h in hooks:
+            h.remove()
+
+    with torch.no_grad():
+        for bn, acc, n in rc.entries.values():
+            if n == 0:
+                continue
+            c = acc.shape[1]
+            bn.running_mean[:c].copy_(acc[0] / n)
+            bn.running_var[:c].copy_(acc[1] / n)
+    # folded inference operands and captured graphs were built from the old statistics
+    ops.clear_infer_cache()
+    return dict(rc.counts, batches=batches, images=images)

@@ -60,6 +60,10 @@ def run_mb_blocks(x, blocks):
             raise NotImplementedError("static MB block with a non-identity shortcut")
         items.append(mb.composite_args(ch, add_x))
         ch = mb.out_channels
+    if ops.RECAL is not None:   # BatchNorm re-calibration (elastic_nn.utils.recalibrate_bn)
+        for cfg, ps in items:
+            x = ops.RECAL.mb_block(x, cfg, ps, x if cfg["residual"] else None)
+        return x
     infer = not torch.is_grad_enabled() and not any(bn.training for cfg, _ in items for bn in cfg["bns"])
     if infer:
         for cfg, ps in items:

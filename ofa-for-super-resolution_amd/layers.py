@@ -102,6 +102,8 @@ class ConvLayer(My2DLayer):
                                           groups=self.groups, bias=self.bias))
 
     def forward(self, x):
+        if ops.RECAL is not None and x.is_cuda:   # BatchNorm re-calibration (elastic_nn.utils.recalibrate_bn)
+            return ops.RECAL.conv_layer(self, x)
         # inference (no grad, eval-mode BN, 16-bit activations): conv + BN (+ ReLU6 | PixelShuffle(2)) as ONE kernel with
         # operands prepared once per set of weights (ops.conv_bn_act_infer)
         if (ops.FUSED_INFER and x.is_cuda and not torch.is_grad_enabled() and self.ops_order == "weight_bn_act"

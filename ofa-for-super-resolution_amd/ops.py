@@ -1468,3 +1468,141 @@ def conv2d(x, conv):
             y = Conv2dFn.apply(xa, w, bwd_hip or CONV_FORCE_HIP)
             return y[..., :W] if padw else y
     return conv(x)
+
+
+# ------------------------------------------------------------------------------ BatchNorm re-calibration
+# elastic_nn.utils.recalibrate_bn sets RECAL to a Recal for the duration of its calibration forwards.  While it is set,
+# every MB block (elastic or static) and every static ConvLayer routes its forward through Recal: each BatchNorm
+# normalises with the statistics of the current batch, which go into fp64 accumulators on the device; running statistics,
+# num_batches_tracked and parameters are left alone.  Everything runs at fp32 on the HIP kernels (no ATen batch_norm, no
+# vendor convolution).
+RECAL = None
+RECAL_MB_KERNEL = True   # tests: False routes every MB block through the per-op fallback
+
+
+def mbconv_recal_f32(x, cfg, w1, g1, b1, wdw, g2, b2, w2, g3, b3, *mats, acc):
+    """the MB block (+ shortcut when cfg["residual"]) with train-mode BatchNorm and no backward, in recompute passes
+    (ofasr_mbconv_recal_f32, csrc/mbrecal_f32.hip).  acc = three float64 [2, C] accumulators (C = mid, mid, out): the
+    kernel adds N * batch mean into row 0 and N * biased batch variance into row 1.  Returns the block output, or None
+    when ofasr_mbconv_recal_f32_supported says no."""
+    _gpu(x, w1, wdw, w2)
+    if x.dtype != torch.float32:
+        return None
+    x = x.contiguous()
+    L = _C.lib()
+    d = _mbconv_desc(x, cfg, w1, g1, b1, wdw, g2, b2, w2, g3, b3, mats)
+    dp = ctypes.byref(d)
+    if not L.ofasr_mbconv_recal_f32_supported(dp):
+        return None
+    for a, c in zip(acc, (cfg["mid"], cfg["mid"], cfg["out"])):
+        if a.dtype != torch.float64 or tuple(a.shape) != (2, c) or not a.is_contiguous() or a.device != x.device:
+            raise _C.OfasrError("mbconv_recal_f32: accumulators must be contiguous float64 [2, C] on %s" % x.device)
+    out = torch.empty((x.shape[0], cfg["out"], x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device)
+    wst, wsp, wsn = _ws(L.ofasr_mbconv_recal_f32_workspace(dp), x.device)
+    with _timed("mbconv_recal_f32"):
+        _C.check(L.ofasr_mbconv_recal_f32(dp, _p(x), _p(out), _p(acc[0]), _p(acc[1]), _p(acc[2]), wsp, wsn, _stream()),
+                 "mbconv_recal_f32")
+    return out
+
+
+def bn_recal_act(x, bn, act, acc, residual=None):
+    """act(BatchNorm_[:C](x) with the batch's statistics (+ residual)): ofasr_bn_stats -> ofasr_bn_recal_accumulate (adds
+    N * mean and N * biased variance into the float64 [2, C] accumulator) -> ofasr_bn_act_fwd.  act: ACT_NONE / RELU6."""
+    _gpu(x, bn.weight, residual)
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    HW = H * W
+    L = _C.lib()
+    if tuple(acc.shape) != (2, C) or acc.dtype != torch.float64:
+        raise _C.OfasrError("bn_recal_act: accumulator must be float64 [2, %d]" % C)
+    wst, wsp, wsn = _ws(L.ofasr_bn_workspace(N, C), x.device)
+    stats = torch.empty((4, C), dtype=torch.float32, device=x.device)   # mean, invstd, scale, shift
+    with _timed("bn_recal", x.numel() * x.element_size()):
+        _C.check(L.ofasr_bn_stats(_p(x), N, C, HW, _dt(x), wsp, wsn, _stream()), "bn_stats")
+        _C.check(L.ofasr_bn_recal_accumulate(wsp, L.ofasr_bn_partials(N, C), C, float(N * HW), float(N),
+                                             _p(_f32_param(bn.weight)), _p(_f32_param(bn.bias)), float(bn.eps), _p(acc),
+                                             _p(stats), _stream()), "bn_recal_accumulate")
+    if residual is not None:
+        residual = residual.contiguous()
+        if residual.shape != x.shape or residual.dtype != x.dtype:
+            raise _C.OfasrError("bn_recal_act: residual does not match x")
+    y = torch.empty_like(x)
+    with _timed("bn_recal_apply", (3 + (residual is not None)) * x.numel() * x.element_size()):
+        _C.check(L.ofasr_bn_act_fwd(_p(x), _p(residual) if residual is not None else None, _p(y), _p(stats[2]),
+                                    _p(stats[3]), _p(stats[0]), N, C, HW, int(act), _dt(x), _stream()), "bn_act_fwd")
+    return y
+
+
+def conv_bn_recal(x, conv, bn, act, acc):
+    """the static ConvLayer's conv -> BatchNorm (batch statistics, accumulated) -> ReLU6 | none, at fp32: the conv on
+    the fp32 HIP kernels (csrc/conv2d_f32.hip; the thin-channel layers on csrc/conv_thin.hip), then bn_recal_act"""
+    _gpu(x)
+    w = conv.weight
+    if (x.dtype != torch.float32 or conv.bias is not None
+            or not _conv_hip_ok(x, w, conv.stride, conv.padding, conv.dilation, conv.groups)):
+        raise _C.OfasrError("conv_bn_recal: conv %s outside the fp32 HIP kernels" % (tuple(w.shape),))
+    return bn_recal_act(Conv2dF32Fn.apply(x, w), bn, act, acc)
+
+
+class Recal(object):
+    """one re-calibration run: per-BatchNorm float64 accumulators [2, C] (row 0: sum of N * mean, row 1: sum of
+    N * biased variance), the images each BatchNorm saw, and how the blocks ran (`counts`: mb_kernel, mb_fallback,
+    conv)"""
+
+    def __init__(self):
+        self.entries = collections.OrderedDict()   # id(bn) -> [bn, acc, images]
+        self.counts = {"mb_kernel": 0, "mb_fallback": 0, "conv": 0}
+
+    def acc(self, bn, C, n, device):
+        ent = self.entries.get(id(bn))
+        if ent is None:
+            ent = self.entries[id(bn)] = [bn, torch.zeros((2, C), dtype=torch.float64, device=device), 0]
+        elif ent[1].shape[1] != C:
+            raise _C.OfasrError("recalibration: a BatchNorm ran with %d and %d channels" % (ent[1].shape[1], C))
+        ent[2] += n
+        return ent[1]
+
+    def conv_layer(self, layer, x):
+        """ConvLayer.forward (ops_order weight_bn_act, no dropout) with batch statistics"""
+        if layer.ops_order != "weight_bn_act" or layer.dropout_rate:
+            raise _C.OfasrError("recalibration: ConvLayer ops_order %s / dropout outside the HIP path" % layer.ops_order)
+        if x.dtype != torch.float32:
+            x = x.float()
+        act = layer._modules.get("act", None)
+        relu6 = layer.act_func == "relu6"
+        if layer.use_bn:
+            acc = self.acc(layer.bn, layer.conv.weight.shape[0], x.shape[0], x.device)
+            y = conv_bn_recal(x, layer.conv, layer.bn, ACT_RELU6 if relu6 else ACT_NONE, acc)
+        else:
+            if not _conv_hip_ok(x, layer.conv.weight, layer.conv.stride, layer.conv.padding, layer.conv.dilation,
+                                layer.conv.groups) or layer.conv.bias is not None:
+                raise _C.OfasrError("recalibration: conv outside the fp32 HIP kernels")
+            y = Conv2dF32Fn.apply(x, layer.conv.weight)
+            relu6 = False
+        self.counts["conv"] += 1
+        return y if (act is None or relu6) else act(y)
+
+    def mb_block(self, x, cfg, params, residual):
+        """one MB block (composite_args of DynamicMBConvLayer or MBInvertedConvLayer) with batch statistics; the
+        one-kernel recompute passes when they cover the block, else the per-op HIP chain (counted in mb_fallback)"""
+        if x.dtype != torch.float32:
+            x = x.float()
+        if residual is not None and residual.dtype != torch.float32:
+            residual = residual.float()
+        add_x = residual is not None and residual is x
+        bns = cfg["bns"]
+        mid, out_c = cfg["mid"], cfg["out"]
+        N = x.shape[0]
+        accs = tuple(self.acc(bn, c, N, x.device) for bn, c in zip(bns, (mid, mid, out_c)))
+        if RECAL_MB_KERNEL and (residual is None or add_x):
+            y = mbconv_recal_f32(x, dict(cfg, residual=add_x), *params, acc=accs)
+            if y is not None:
+                self.counts["mb_kernel"] += 1
+                return y
+        self.counts["mb_fallback"] += 1
+        w1, g1, b1, wdw, g2, b2, w2, g3, b3 = params[:9]
+        mats = params[9:]
+        h = bn_recal_act(pwconv(x, w1, mid), bns[0], ACT_RELU6, accs[0])
+        f = KTransformFn.apply(wdw, mid, tuple(cfg["chain"]), bool(mats), *mats)
+        h = bn_recal_act(dwconv(h, f), bns[1], ACT_RELU6, accs[1])
+        return bn_recal_act(pwconv(h, w2, out_c), bns[2], ACT_NONE, accs[2], residual)
