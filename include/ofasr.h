@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 302 /* + ofasr_mbconv_recal_f32_*, ofasr_bn_recal_accumulate */
+#define OFASR_VERSION 303 /* + ofasr_tile_gather_u8, ofasr_tile_scatter_u8 */
 
 typedef enum {
     OFASR_OK = 0,
@@ -398,6 +398,25 @@ int ofasr_conv2d_f32_wgrad(const void* dy, const void* x, float* dw, int64_t N, 
 size_t ofasr_bicubic_resize_u8_workspace(int64_t planes, int64_t in_h, int64_t in_w, int64_t out_h, int64_t out_w);
 int ofasr_bicubic_resize_u8(const void* src, void* dst, int64_t planes, int64_t in_h, int64_t in_w, int64_t out_h,
                             int64_t out_w, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Tiled inference: 8-bit image <-> tile batch  -- the host-side ToTensor (div2k_setxx.to_tensor) and
+ * utils.tensor2img_np quantisation on the device, for the windows of upscale.py's TiledUpscaler.  One launch per batch;
+ * 64-bit addressing; every access stays inside its tensor whatever the device tables hold (entries are clamped).
+ *   gather:  img is a HWC uint8 RGB image [H, W, 3]; origins a device int64 table [n][2] = (y0, x0) of window n (clamped
+ *            to 0 <= y0 <= H - h, 0 <= x0 <= W - w); out is the NCHW batch [n, 3, h, w] of `dtype`:
+ *            out[n,c,r,x] = (dtype)(img[y0+r, x0+x, c] / 255.0f)   (fp32 division, then one RNE cast)
+ *   scatter: src is the network output [n, 3, sh, sw] of `dtype`; table a device int64 table [n][6] =
+ *            (sy, sx, dy, dx, eh, ew); img the HWC uint8 output [OH, OW, 3]:
+ *            img[dy+r, dx+x, c] = round_half_even(clamp(src[n,c,sy+r,sx+x], 0, 1) * 255)   for r < eh, x < ew
+ *            (extents clamped to max_eh x max_ew, to the source window and to the image).  Pixels outside every
+ *            extent are not written; extents of different windows must not overlap.
+ * n <= 65535.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_tile_gather_u8(const void* img, int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h, int64_t w,
+                         void* out, int dtype, void* stream);
+int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table, void* img,
+                          int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (tests and bench.py; nothing on the product path calls these).

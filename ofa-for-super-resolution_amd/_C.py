@@ -118,6 +118,9 @@ SIGNATURES = {
     "ofasr_mbconv_recal_f32": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "ofasr_bn_recal_accumulate": (_c_int, [_c_vp, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp,
                                            ctypes.c_double, _c_vp, _c_vp, _c_vp]),
+    "ofasr_tile_gather_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_int, _c_vp]),
+    "ofasr_tile_scatter_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64,
+                                       _c_vp]),
     "ofasr_debug_mbfused_tile": (_c_int, [_c_int]),
     "ofasr_debug_mbfused_split": (_c_int, [_c_int]),
     "ofasr_debug_mbconv_bn_bwd_stat": (_c_int, [_c_int]),

@@ -1,0 +1,336 @@
+"""Tiled any-size image upscaling with an exported static SR network (SRNetS4 / SRNetX4, sr_static.py).
+
+A whole large image is not run through the network in one call: at 4x for a 1920x1080 input the 64 -> 256 conv before
+the last PixelShuffle alone would be 2.1e9 elements, past the 32-bit extents some kernels guard (mg_supported refuses an
+MB block above 2^31 bytes and the block drops to the slower composite path).  Instead the input is cut into core tiles,
+each core is given a halo of `receptive_radius(config)` input pixels, and the equally shaped windows run as one batch:
+
+  * a window is the core plus `halo` on every side, CLAMPED INTO THE IMAGE BY SHIFTING, never by padding:
+    start = clamp(x0 - halo, 0, W - win).  An outer window edge is then either a true image edge, where every conv
+    zero-pads exactly as in the whole-image forward, or at least halo >= radius away from every core pixel.  Zero-filling
+    outside the image would be wrong: from the second layer on the whole-image forward sees zero padding there, while a
+    zero-filled window would see conv(0) + BN shift != 0.
+  * the core pixels of a window's output therefore equal the whole-image forward's (up to summation order).
+
+The 8-bit image <-> tile batch moves are the HIP kernels ofasr_tile_gather_u8 / ofasr_tile_scatter_u8 (csrc/tile_io.hip:
+ToTensor's / 255 and tensor2img_np's clamp * 255 round, one launch per batch); the network runs on its own HIP kernels,
+replayed from one captured graph per window shape (graphed.GraphedEval).
+"""
+import math
+from fractions import Fraction
+
+import torch
+
+from . import _C, ops
+from .graphed import GraphedEval
+
+LIMIT = 2 ** 31          # no activation of one window reaches 2^31 bytes (fp32); no batched tensor 2^31 elements
+MAX_WINDOWS = 65535      # per launch of the tile kernels (grid.y)
+
+_DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+_CODES = {torch.float32: _C.F32, torch.bfloat16: _C.BF16, torch.float16: _C.F16}
+
+
+# ---------------------------------------------------------------------------------------------- network geometry
+def _layers(config):
+    """the static network as ("conv", kernel extent, out channels) / ("mb", kernel, mid, out) / ("shuffle",) /
+    ("unshuffle",) steps, in the order of SRNetS4.forward / SRNetX4.forward (long skips and residual adds do not widen
+    the support and are left out)"""
+    def conv(c):
+        k = c["kernel_size"]
+        d = c.get("dilation", 1)
+        steps = [("conv", d * (k - 1) + 1, c["out_channels"])]
+        if c.get("act_func") == "pixelshuffle":
+            steps.append(("shuffle",))
+        elif c.get("act_func") == "pixelunshuffle":
+            steps.append(("unshuffle",))
+        return steps
+
+    def block(c):
+        if c["name"] == "MobileInvertedResidualBlock":
+            m = c["mobile_inverted_conv"]
+            return [("mb", m["kernel_size"], m["mid_channels"], m["out_channels"])]
+        return conv(c)
+
+    out = []
+    blocks = config["blocks"]
+    if config["name"] == "SRNetS4":
+        out += conv(config["dec_first_conv_block"])
+        for c in blocks[:config["n_mb"]]:
+            out += block(c)
+        for c in config["dec_final_conv_blocks"]:
+            out += conv(c)
+        for c in blocks[config["n_mb"]:]:
+            out += block(c)
+    elif config["name"] == "SRNetX4":
+        u, e, d = config["n_unshuffle"], config["n_enc"], config["n_dec"]
+        for c in blocks[:u + e]:
+            out += block(c)
+        for c in config["enc_final_conv_blocks"]:
+            out += conv(c)
+        out += conv(config["dec_first_conv_block"])
+        for c in blocks[u + e:u + e + d]:
+            out += block(c)
+        for c in config["dec_final_conv_blocks"]:
+            out += conv(c)
+        for c in blocks[u + e + d:]:
+            out += block(c)
+    else:
+        raise ValueError("not a static SR network config: %r" % config.get("name"))
+    out += conv(config["dec_final_output_conv_block"])
+    return out
+
+
+def receptive_radius(config):
+    """the largest distance, in input pixels, at which an input pixel can affect an output pixel.  At resolution f
+    (layer pixels per input pixel) a k x k conv adds (k - 1) / 2 / f; PixelShuffle(2) doubles f; PixelUnshuffle(2)
+    halves it after its 2 x 2 grouping has added up to one pixel of the finer resolution, 1 / f."""
+    r, f = Fraction(0), Fraction(1)
+    for step in _layers(config):
+        if step[0] in ("conv", "mb"):
+            r += Fraction(step[1] - 1, 2) / f
+        elif step[0] == "shuffle":
+            f *= 2
+        else:
+            r += 1 / f
+            f /= 2
+    return int(math.ceil(r))
+
+
+def activation_elems_per_pixel(config):
+    """elements of the largest activation per input pixel of a window (the MB blocks' mid tensor counted, as the composite
+    path materialises it); for the max S4 sub-network it is the 64 -> 256 conv output before the last PixelShuffle"""
+    f, best = Fraction(1), Fraction(3)
+    for step in _layers(config):
+        if step[0] == "conv":
+            best = max(best, step[2] * f * f)
+        elif step[0] == "mb":
+            best = max(best, max(step[2], step[3]) * f * f)
+        elif step[0] == "shuffle":
+            f *= 2
+        else:
+            f /= 2
+    return int(math.ceil(best))
+
+
+def alignment(config):
+    """the side multiple an input needs: 2 ** (PixelUnshuffle blocks) for X4, 1 for S4"""
+    return 2 ** config.get("n_unshuffle", 0) if config["name"] == "SRNetX4" else 1
+
+
+# ---------------------------------------------------------------------------------------------- tile plan
+def _up(v, m):
+    return -(-v // m) * m
+
+
+class TilePlan(object):
+    """windows of one image: all win_h x win_w; windows[i] = (wy, wx, cy, cx, ch, cw): window origin and core rectangle,
+    in input pixels.  `batch` is the most windows one batch may hold (no batched tensor reaches 2^31 elements)."""
+
+    def __init__(self, H, W, win_h, win_w, windows, scale, batch):
+        self.H, self.W, self.win_h, self.win_w = H, W, win_h, win_w
+        self.windows = windows
+        self.scale = scale
+        self.batch = batch
+
+    def __len__(self):
+        return len(self.windows)
+
+    def overhead(self):
+        """window pixels / core pixels"""
+        return len(self.windows) * self.win_h * self.win_w / float(self.H * self.W)
+
+
+def _axis(L, core, halo, align, mult):
+    """(window side, [(window start, core start, core length)]) along one axis"""
+    n = -(-L // core)
+    c = _up(-(-L // n), align)         # cores of at most `core`, split evenly
+    win = _up(c + 2 * halo, mult)
+    if win >= L:                       # the image is no wider than one window: the window is the whole axis
+        return L, [(0, 0, L)]
+    out = []
+    x0 = 0
+    while x0 < L:
+        out.append((min(max(x0 - halo, 0), L - win), x0, min(c, L - x0)))
+        x0 += c
+    return win, out
+
+
+def plan_windows(H, W, core, halo, align=1, scale=4, px_elems=None):
+    """the tile plan of an H x W input: cores of at most core x core input pixels that tile the image exactly once, each in
+    a window of the core plus `halo` on every side, shifted into the image (never padded).  Window sides are multiples
+    of `align` (input sides must be, too) and, where the image is wide enough, widths are multiples of 8.  `px_elems` is
+    activation_elems_per_pixel(config): it bounds the batch."""
+    H, W, core, halo, align = int(H), int(W), int(core), int(halo), int(align)
+    if H <= 0 or W <= 0:
+        raise ValueError("empty image %dx%d" % (H, W))
+    if H % align or W % align:
+        raise ValueError("this network needs input sides that are multiples of %d (2 ** PixelUnshuffle blocks); got %dx%d"
+                         % (align, H, W))
+    if core < align:
+        raise ValueError("core %d is smaller than the alignment %d" % (core, align))
+    core = core // align * align
+    halo = _up(max(halo, 0), align)
+    win_h, rows = _axis(H, core, halo, align, align)
+    win_w, cols = _axis(W, core, halo, align, align * 8 // math.gcd(align, 8))
+    windows = [(wy, wx, cy, cx, ch, cw) for (wy, cy, ch) in rows for (wx, cx, cw) in cols]
+    px = px_elems if px_elems is not None else max(384, 64 * scale * scale, 3 * scale * scale)
+    batch = max(1, min(MAX_WINDOWS, (LIMIT - 1) // (px * win_h * win_w)))
+    return TilePlan(H, W, win_h, win_w, windows, scale, batch)
+
+
+def default_core(halo, align, px_elems):
+    """the largest core (a multiple of 8 and of align) whose window keeps every fp32 activation below 2^31 bytes"""
+    m = align * 8 // math.gcd(align, 8)
+    side = int(math.isqrt((LIMIT - 1) // (4 * px_elems)))
+    core = (side - 2 * _up(halo, align)) // m * m
+    while core > m and 4 * px_elems * _up(core + 2 * halo, m) ** 2 >= LIMIT:
+        core -= m
+    if core < m:
+        raise ValueError("the network's receptive radius (%d) leaves no room for a core under the 2^31-byte limit" % halo)
+    return core
+
+
+# ---------------------------------------------------------------------------------------------- kernels
+def tile_gather(img, origins, h, w, dtype, out=None):
+    """img: HWC uint8 [H, W, 3] on the GPU; origins: int64 [n, 2] (y0, x0) on the GPU -> [n, 3, h, w] of dtype,
+    u8 / 255 (fp32) then cast (ofasr_tile_gather_u8)"""
+    ops._gpu(img)
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.size(2) != 3 or not img.is_contiguous():
+        raise ValueError("tile_gather needs a contiguous HWC uint8 RGB image")
+    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous():
+        raise ValueError("tile_gather needs a contiguous int64 origin table on the GPU")
+    n = origins.size(0)
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=dtype, device=img.device)
+    _C.check(_C.lib().ofasr_tile_gather_u8(img.data_ptr(), img.size(0), img.size(1), origins.data_ptr(), n, h, w,
+                                           out.data_ptr(), _CODES[out.dtype], ops._stream()), "ofasr_tile_gather_u8")
+    return out
+
+
+def tile_scatter(src, table, img, max_eh, max_ew):
+    """src: network output [n, 3, sh, sw] (contiguous, fp32 / bf16 / f16); table: int64 [n, 6] (sy, sx, dy, dx, eh, ew)
+    on the GPU; writes round_half_even(clamp(v, 0, 1) * 255) into the HWC uint8 image img (ofasr_tile_scatter_u8)"""
+    ops._gpu(src)
+    if not src.is_contiguous() or src.dim() != 4 or src.size(1) != 3:
+        raise ValueError("tile_scatter needs a contiguous [n, 3, h, w] source")
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.size(2) != 3 or not img.is_contiguous():
+        raise ValueError("tile_scatter needs a contiguous HWC uint8 RGB destination")
+    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.size(0) > src.size(0):
+        raise ValueError("tile_scatter needs a contiguous int64 table on the GPU, one row per source window at most")
+    _C.check(_C.lib().ofasr_tile_scatter_u8(src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype],
+                                            table.data_ptr(), img.data_ptr(), img.size(0), img.size(1), max_eh, max_ew,
+                                            ops._stream()), "ofasr_tile_scatter_u8")
+    return img
+
+
+# ---------------------------------------------------------------------------------------------- upscaler
+class TiledUpscaler(object):
+    """Tiled inference of a static SR network (SRNetS4 / SRNetX4 on the GPU; put into eval mode here).
+
+    upscale(img) takes an HWC uint8 RGB image (CPU or GPU tensor, or numpy array) and returns the HWC uint8 output on the
+    GPU.  Per batch of windows: gather (HIP), the network (replayed from one captured graph per window shape when
+    `graphed`; the last batch is padded by repeating a window), scatter of the cores (HIP).  `core` = None: the largest
+    core that keeps every fp32 activation of a window below 2^31 bytes; `batch` = None: as many windows per batch as
+    keep every batched tensor below 2^31 elements, spread evenly over the batches."""
+
+    def __init__(self, net, core=None, batch=None, mix_prec="f32", graphed=True):
+        if mix_prec not in _DTYPES:
+            raise ValueError("mix_prec must be one of %s" % sorted(_DTYPES))
+        self.net = net.eval()
+        self.config = net.config
+        self.scale = int(self.config["upscale"])
+        if self.scale != self.config["upscale"] or self.scale < 1:
+            raise ValueError("tiled upscaling needs an integer upscale factor, got %r" % self.config["upscale"])
+        self.align = alignment(self.config)
+        self.radius = receptive_radius(self.config)
+        self.halo = _up(self.radius, self.align)
+        self.px_elems = activation_elems_per_pixel(self.config)
+        self.core = int(core) if core else default_core(self.halo, self.align, self.px_elems)
+        self.batch = batch
+        self.dtype = _DTYPES[mix_prec]
+        self.autocast_dtype = None if mix_prec == "f32" else self.dtype
+        self.graphed = GraphedEval(net, autocast_dtype=self.autocast_dtype, copy_output=False) if graphed else None
+
+    def plan(self, H, W):
+        return plan_windows(H, W, self.core, self.halo, self.align, self.scale, self.px_elems)
+
+    def _whole_plan(self, H, W):
+        if H % self.align or W % self.align:
+            raise ValueError("this network needs input sides that are multiples of %d; got %dx%d" % (self.align, H, W))
+        if 4 * self.px_elems * H * W >= LIMIT:
+            raise ValueError("a %dx%d image is too large for one forward (an fp32 activation would reach 2^31 bytes): "
+                             "use the tiled path" % (H, W))
+        return TilePlan(H, W, H, W, [(0, 0, 0, 0, H, W)], self.scale, 1)
+
+    def _forward(self, x):
+        if self.graphed is not None:
+            return self.graphed(x)
+        with torch.autocast("cuda", dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
+            return self.net(x)
+
+    def _image(self, img):
+        if not torch.is_tensor(img):
+            img = torch.from_numpy(img)
+        if img.dtype != torch.uint8 or img.dim() != 3 or img.size(2) != 3:
+            raise ValueError("upscale takes an HWC uint8 RGB image, got %s %s" % (tuple(img.shape), img.dtype))
+        dev = next(self.net.parameters()).device
+        if dev.type != "cuda":
+            raise _C.OfasrError("TiledUpscaler needs the network on the GPU")
+        return img.to(dev).contiguous()
+
+    def _run(self, img, whole, sink):
+        """run every batch of the plan; sink(y, real, tables, plan) consumes the network output of a batch"""
+        img = self._image(img)
+        H, W = img.size(0), img.size(1)
+        plan = self._whole_plan(H, W) if whole else self.plan(H, W)
+        s = self.scale
+        n = len(plan)
+        cap = min(plan.batch, int(self.batch)) if self.batch else plan.batch
+        nb = -(-n // cap)
+        B = -(-n // nb)
+        wins = plan.windows + [plan.windows[-1]] * (nb * B - n)   # pad the last batch by repeating a window
+        origins = torch.tensor([[wy, wx] for (wy, wx, _, _, _, _) in wins], dtype=torch.int64).to(img.device)
+        table = torch.tensor([[(cy - wy) * s, (cx - wx) * s, cy * s, cx * s, ch * s, cw * s]
+                              for (wy, wx, cy, cx, ch, cw) in plan.windows], dtype=torch.int64).to(img.device)
+        with torch.no_grad():
+            for b in range(nb):
+                x = tile_gather(img, origins[b * B:(b + 1) * B], plan.win_h, plan.win_w, self.dtype)
+                y = self._forward(x)
+                real = min(B, n - b * B)
+                sink(y, real, table[b * B:b * B + real], plan.windows[b * B:b * B + real], plan)
+        return plan
+
+    def upscale(self, img, whole=False):
+        """HWC uint8 RGB -> HWC uint8 RGB (scale x) on the GPU.  whole=True: one forward of the whole image (parity;
+        refuses images whose activations would reach 2^31 bytes)"""
+        H, W = int(img.shape[0]), int(img.shape[1])
+        out = None
+
+        def sink(y, real, table, wins, plan):
+            nonlocal out
+            if out is None:
+                out = torch.empty(H * self.scale, W * self.scale, 3, dtype=torch.uint8, device=y.device)
+            tile_scatter(y.contiguous(), table, out, max(w[4] for w in wins) * self.scale,
+                         max(w[5] for w in wins) * self.scale)
+
+        self._run(img, whole, sink)
+        return out
+
+    def upscale_float(self, img, whole=False):
+        """the network's fp32 output [3, H*scale, W*scale] before quantisation, assembled from the same window cores
+        as upscale() (torch copies; for parity checks)"""
+        H, W = int(img.shape[0]), int(img.shape[1])
+        s = self.scale
+        out = None
+
+        def sink(y, real, table, wins, plan):
+            nonlocal out
+            if out is None:
+                out = torch.empty(3, H * s, W * s, dtype=torch.float32, device=y.device)
+            for i, (wy, wx, cy, cx, ch, cw) in enumerate(wins):
+                out[:, cy * s:(cy + ch) * s, cx * s:(cx + cw) * s] = \
+                    y[i, :, (cy - wy) * s:(cy - wy + ch) * s, (cx - wx) * s:(cx - wx + cw) * s].float()
+
+        self._run(img, whole, sink)
+        return out
