@@ -45,7 +45,7 @@ def load_static(in_dir):
     return net
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--path", default="exp/sr/eval")
@@ -61,7 +61,11 @@ def main():
                     help="also write the selected sub-network as a static network: DIR/net_config.json + DIR/%s" % STATIC_WEIGHTS)
     ap.add_argument("--static", default=None, metavar="DIR", help="evaluate the static network exported to DIR "
                                                                   "(instead of a supernet sub-network)")
-    a = ap.parse_args()
+    ap.add_argument("--test-sizes", default=None, help="synthetic test HR sizes instead of the Set14-like ones, e.g. 64x64,48x80")
+    ap.add_argument("--ssim", action="store_true", help="also report Y-SSIM (and the exact-luma Y-PSNR), scored on the GPU "
+                                                        "by the HIP metric kernel (SRRunManager.validate_quality)")
+    ap.add_argument("--shave", type=int, default=0, help="with --ssim: border pixels left out of the metric")
+    a = ap.parse_args(argv)
     import torch
     rm = importlib.import_module(PKG + ".imagenet_codebase.run_manager")
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
@@ -73,10 +77,13 @@ def main():
         net = nets.OFAMobileNetS4(ks_list=[3, 5, 7], expand_ratio_list=[3, 4, 6], depth_list=[2, 3, 4],
                                   pixelshuffle_depth_list=[1, 2])
     # Set14-like sizes (HR sides multiples of 4)
+    sizes = [(480, 500), (576, 720), (512, 512), (288, 352), (360, 248), (276, 276), (360, 500), (288, 352),
+             (512, 512), (512, 512), (512, 768), (512, 512), (656, 528), (388, 584)]
+    if a.test_sizes:
+        sizes = [tuple(int(v) for v in s.split("x")) for s in a.test_sizes.split(",")]
     cfg = rm.Div2K_SetXXRunConfig(n_epochs=1, init_lr=1e-3, opt_type="adam", no_decay_keys="bn#bias",
                                   label_smoothing=0.0, train_batch_size=1, test_batch_size=1, image_size=256,
-                                  test_sizes=[(480, 500), (576, 720), (512, 512), (288, 352), (360, 248), (276, 276), (360, 500), (288, 352),
-                                              (512, 512), (512, 512), (512, 768), (512, 512), (656, 528), (388, 584)],
+                                  test_sizes=sizes,
                                   n_train_batches=1, allow_synthetic=True if a.synthetic else None)
     mgr = rm.SRRunManager(a.path, net, cfg, init=a.checkpoint is None and not a.static, mix_prec=a.mix_prec, num_gpus=1)
     if a.static:
@@ -104,6 +111,10 @@ def main():
     dt = time.perf_counter() - t0
     print("loss %.5f  Y-PSNR %.3f dB  (%d images in %d forward calls, %.1f images/s)" % (loss, psnr, n_img, calls,
                                                                                        n_img / dt))
+    if a.ssim:
+        q = mgr.validate_quality(is_test=True, input_key=key, shave=a.shave)
+        print("Y-SSIM %.4f  Y-PSNR %.3f dB  (exact luma, shave %d, scored on the GPU)" % (q["ssim"], q["psnr"], a.shave))
+        return q
 
 
 if __name__ == "__main__":

@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 303 /* + ofasr_tile_gather_u8, ofasr_tile_scatter_u8 */
+#define OFASR_VERSION 304 /* + ofasr_quality_y, ofasr_quality_mse (+ workspace queries) */
 
 typedef enum {
     OFASR_OK = 0,
@@ -417,6 +417,33 @@ int ofasr_tile_gather_u8(const void* img, int64_t H, int64_t W, const int64_t* o
                          void* out, int dtype, void* stream);
 int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table, void* img,
                           int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Y-channel quality metrics: exact SSE (for Y-PSNR) and mean SSIM of two image batches, per image  -- replaces the host
+ * round trip of the reference's logged metric (sr_run_manager.py:567-597: tensor2img -> rgb2y -> psnr on numpy arrays)
+ * and adds the SSIM the reference does not have.  Each operand has a format: OFASR_F32 / OFASR_F16 / OFASR_BF16 = planar
+ * NCHW [N, 3, H, W] with values meant in [0, 1]; OFASR_U8_HWC = one interleaved uint8 RGB image [H, W, 3] (N = 1).  The
+ * two operands may differ in format.
+ *   quantise: float -> uint8 as ofasr_tile_scatter_u8 does: round_half_even(clamp(v, 0, 1) * 255) in fp32
+ *   luma:     Y = round_half_even((65481 R + 128553 G + 24966 B) / 255000 + 16), exact integer arithmetic
+ *   shave:    pixels dropped from every side of both images first (>= 0; both shaved sides must stay >= 11)
+ *   sse[n]:   sum over the shaved image of (Ya - Yb)^2, exact.  PSNR = 20 log10(255 / sqrt(sse / ((H-2s)(W-2s)))).
+ *   ssim[n]:  mean over the (H-2s-10) x (W-2s-10) "valid" positions of the SSIM of Wang et al. 2004: 11x11 Gaussian
+ *             window, sigma 1.5, C1 = (0.01*255)^2, C2 = (0.03*255)^2, all in fp64.
+ * One tile kernel + one finishing kernel on `stream`; partial sums are added in a fixed order (no atomics), so two calls
+ * give identical bits.  workspace: ofasr_quality_y_workspace bytes (host-only query; 0 for a shape the call refuses),
+ * 16-byte aligned.  N <= 65535.
+ * ------------------------------------------------------------------------------------------- */
+#define OFASR_U8_HWC 3 /* operand format of ofasr_quality_y, beside the ofasr_dtype codes */
+size_t ofasr_quality_y_workspace(int64_t N, int64_t H, int64_t W, int64_t shave);
+int ofasr_quality_y(const void* a, int fmt_a, const void* b, int fmt_b, int64_t N, int64_t H, int64_t W, int64_t shave,
+                    int64_t* sse, double* ssim, void* workspace, size_t workspace_bytes, void* stream);
+/* The evaluation loss beside the metric, per image: mse[n] = mean over the `elems` values of image n of
+ * ((float)a - (float)b)^2 (difference and square rounded to fp32 as nn.MSELoss's element-wise steps are, the sum in
+ * fp64 in a fixed order).  a, b: [N, elems] contiguous, f32 / f16 / bf16 each.  workspace: 8-byte aligned. */
+size_t ofasr_quality_mse_workspace(int64_t N, int64_t elems);
+int ofasr_quality_mse(const void* a, int fmt_a, const void* b, int fmt_b, int64_t N, int64_t elems, double* mse,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (tests and bench.py; nothing on the product path calls these).

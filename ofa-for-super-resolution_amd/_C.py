@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OFASR_LIB_PATH") or os.path.join(_HERE, "csrc", "libofasr_hip.so")   # override: A/B of two builds on one box
 
 F32, F16, BF16 = 0, 1, 2
+U8_HWC = 3   # operand format of ofasr_quality_y: one interleaved uint8 RGB image
 
 _lib = None
 
@@ -121,6 +122,11 @@ SIGNATURES = {
     "ofasr_tile_gather_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_int, _c_vp]),
     "ofasr_tile_scatter_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64,
                                        _c_vp]),
+    "ofasr_quality_y_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    "ofasr_quality_y": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_sz,
+                                 _c_vp]),
+    "ofasr_quality_mse_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "ofasr_quality_mse": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_vp, _c_vp, _c_sz, _c_vp]),
     "ofasr_debug_mbfused_tile": (_c_int, [_c_int]),
     "ofasr_debug_mbfused_split": (_c_int, [_c_int]),
     "ofasr_debug_mbconv_bn_bwd_stat": (_c_int, [_c_int]),

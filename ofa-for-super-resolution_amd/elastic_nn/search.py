@@ -391,3 +391,23 @@ def psnr_fitness(net, calib_loader, val_loader, run_manager, space, max_calib_ba
             restore_bn_buffers(net, snap)
 
     return fitness
+
+
+def quality_fitness(net, calib_loader, val_loader, run_manager, space, max_calib_batches=None, metric="psnr", shave=0):
+    """psnr_fitness scored on the GPU: fitness(arch) = the Y-PSNR (`metric="psnr"`) or Y-SSIM (`"ssim"`) of
+    SRRunManager.validate_quality -- the HIP metric kernel on the network's output, no host round trip of the images."""
+    if metric not in ("psnr", "ssim"):
+        raise ValueError("metric is 'psnr' or 'ssim', got %r" % (metric,))
+
+    def fitness(arch):
+        snap = bn_buffers(net)
+        try:
+            space.apply(net, arch)
+            key = lr_key(net)
+            recalibrate_bn(net, calib_loader, input_key=key, max_batches=max_calib_batches)
+            return run_manager.validate_quality(net=net, data_loader=val_loader, input_key=key, graphs=False,
+                                                shave=shave)[metric]
+        finally:
+            restore_bn_buffers(net, snap)
+
+    return fitness

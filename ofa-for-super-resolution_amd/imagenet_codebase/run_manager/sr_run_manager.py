@@ -22,7 +22,7 @@ import torch.nn as nn
 from ... import distributed as dd
 from ... import ops
 from ...graphed import GraphedEval
-from ...utils import AverageMeter, bucket_by_size, device_batch, psnr_y, psnr_y_per_image
+from ...utils import AverageMeter, bucket_by_size, device_batch, psnr_from_sse, psnr_y, psnr_y_per_image
 from ..utils import get_net_info
 
 
@@ -359,6 +359,56 @@ class SRRunManager(object):
                 for v in psnr_y_per_image(output, images):
                     psnrs.update(v, 1)
         return losses.avg, psnrs.avg, calls
+
+    def validate_quality(self, net=None, data_loader=None, is_test=True, input_key="2x_down_image", max_batch=None,
+                         graphs=None, shave=0):
+        """`validate_batched` (same size buckets, same forwards) scored on the GPU: Y-PSNR and Y-SSIM by the HIP metric
+        kernel (ops.quality_y: exact integer luma, `shave` border pixels dropped) and the per-image MSE loss by
+        ops.quality_mse, straight from the network's output.  No image goes to the host and no ATen kernel runs between
+        the forwards and the ONE read-back of the per-image numbers at the end.  PSNR equals validate_batched's unless an
+        image holds one of the 194 colours whose exact luma is a rounding tie (utils.y_exact).
+        Returns {"loss", "psnr", "ssim", "calls"} (means over the images; "psnr_per_image" / "ssim_per_image" beside)."""
+        if net is None:
+            net = self.net
+        if graphs is None:
+            graphs = (os.environ.get("OFASR_EVAL_GRAPHS", "1") != "0" and str(self.device).startswith("cuda")
+                      and self.mix_prec in ("bf16", "f16"))
+        fwd = self.graphed(net) if graphs else None
+        if data_loader is None:
+            data_loader = self.run_config.test_loader if is_test else self.run_config.valid_loader
+        net.eval()
+        items = []
+        for mini_batch in data_loader:
+            mini_batch = device_batch(mini_batch, self.device)
+            for i in range(mini_batch["image"].shape[0]):
+                items.append({k: v[i:i + 1] for k, v in mini_batch.items() if torch.is_tensor(v)})
+        calls = 0
+        with torch.no_grad():
+            groups = list(bucket_by_size(items, key=lambda it: it[input_key], max_batch=max_batch))
+            lrs = [torch.cat([it[input_key] for it in group]).to(self.device) for group in groups]
+            hrs = [torch.cat([it["image"] for it in group]).to(self.device) for group in groups]
+            # rows: sse (int64), the bits of ssim (fp64), the bits of the mse (fp64); one column per image
+            res = torch.empty((3, len(items)), dtype=torch.int64, device=self.device)
+            counts, at = [], 0
+            outs = fwd.call_many(lrs) if (fwd is not None and lrs) else None
+            for gi, group in enumerate(groups):
+                if outs is not None:
+                    output = outs[gi]
+                else:
+                    with self.autocast():
+                        output = net(lrs[gi])
+                calls += 1
+                n = len(group)
+                _, _, count = ops.quality_y(output, hrs[gi], shave, out=res[:2, at:at + n])
+                ops.quality_mse(output, hrs[gi], out=res[2, at:at + n].view(torch.float64))
+                counts += [count] * n
+                at += n
+            host = res.cpu()
+        sse, ssim, mse = host[0].tolist(), host[1].view(torch.float64).tolist(), host[2].view(torch.float64).tolist()
+        psnr = [psnr_from_sse(s, c) for s, c in zip(sse, counts)]
+        mean = lambda v: sum(v) / len(v) if v else 0.0
+        return {"loss": mean(mse), "psnr": mean(psnr), "ssim": mean(ssim), "calls": calls, "psnr_per_image": psnr,
+                "ssim_per_image": ssim}
 
     def train_one_epoch(self, args, epoch, warmup_epochs=0, warmup_lr=0, input_key="2x_down_image"):
         """fixed-architecture ("teacher") epoch: BatchNorm layers run in eval mode (frozen statistics,

@@ -194,6 +194,66 @@ def lr_images_from_u8(hr_u8):
     return out
 
 
+# ------------------------------------------------------------------------------ Y-PSNR / Y-SSIM on the GPU
+def _quality_operand(t, what):
+    """(contiguous tensor, format code, N, H, W) of one operand of quality_y"""
+    _gpu(t)
+    if t.dtype == torch.uint8:
+        if t.dim() != 3 or t.size(2) != 3:
+            raise _C.OfasrError("quality_y: a uint8 %s is one HWC RGB image [H, W, 3], got %s" % (what, tuple(t.shape)))
+        return t.contiguous(), _C.U8_HWC, 1, t.size(0), t.size(1)
+    if t.dim() != 4 or t.size(1) != 3:
+        raise _C.OfasrError("quality_y: a float %s is an NCHW RGB batch [N, 3, H, W], got %s" % (what, tuple(t.shape)))
+    return t.detach().contiguous(), _dt(t), t.size(0), t.size(2), t.size(3)
+
+
+def quality_y(output, target, shave=0, out=None):
+    """(sse int64 [N], ssim fp64 [N], count) of the Y channels of two image batches, computed where they are
+    (ofasr_quality_y, csrc/quality.hip; the definition is utils.y_exact / utils.ssim_y).  Each operand is an NCHW
+    f32 / f16 / bf16 batch with values meant in [0, 1] or one HWC uint8 image; `shave` pixels are dropped from every
+    side first.  sse and ssim stay on the GPU (no host sync); count = (H - 2 shave) * (W - 2 shave) pixels per image.
+    `out`: a contiguous int64 [2, N] GPU tensor to write into -- row 0 the sse, row 1 the bits of the ssim (the returned
+    tensors are views of it), so that a caller scoring many batches reads everything back with one copy."""
+    a, fa, Na, Ha, Wa = _quality_operand(output, "output")
+    b, fb, Nb, Hb, Wb = _quality_operand(target, "target")
+    if (Na, Ha, Wa) != (Nb, Hb, Wb):
+        raise _C.OfasrError("quality_y: output is %d x %dx%d, target is %d x %dx%d" % (Na, Ha, Wa, Nb, Hb, Wb))
+    if a.device != b.device:
+        raise _C.OfasrError("quality_y: operands on different devices")
+    shave = int(shave)
+    L = _C.lib()
+    if out is None:
+        out = torch.empty((2, Na), dtype=torch.int64, device=a.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (2, Na) or out.device != a.device or out.stride(1) != 1:
+        raise _C.OfasrError("quality_y: out must be an int64 [2, %d] tensor on %s with unit inner stride" % (Na, a.device))
+    sse, ssim = out[0], out[1].view(torch.float64)
+    wst, wsp, wsn = _ws(L.ofasr_quality_y_workspace(Na, Ha, Wa, shave), a.device)
+    with _timed("quality_y", a.numel() * a.element_size() + b.numel() * b.element_size()):
+        _C.check(L.ofasr_quality_y(_p(a), fa, _p(b), fb, Na, Ha, Wa, shave, _p(sse), _p(ssim), wsp, wsn, _stream()),
+                 "quality_y")
+    return sse, ssim, (Ha - 2 * shave) * (Wa - 2 * shave)
+
+
+def quality_mse(output, target, out=None):
+    """per-image mean squared error of two float batches of equal shape as an fp64 [N] GPU tensor (ofasr_quality_mse):
+    the evaluation loss (nn.MSELoss per image) without an ATen kernel or a host sync.  `out`: fp64 [N] to write into."""
+    _gpu(output, target)
+    if output.shape != target.shape or output.dim() < 2:
+        raise _C.OfasrError("quality_mse: shapes %s / %s" % (tuple(output.shape), tuple(target.shape)))
+    a, b = output.detach().contiguous(), target.detach().contiguous()
+    N = a.size(0)
+    elems = a.numel() // N
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=a.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (N,) or not out.is_contiguous() or out.device != a.device:
+        raise _C.OfasrError("quality_mse: out must be a contiguous fp64 [%d] tensor on %s" % (N, a.device))
+    L = _C.lib()
+    wst, wsp, wsn = _ws(L.ofasr_quality_mse_workspace(N, elems), a.device)
+    with _timed("quality_mse", a.numel() * a.element_size() + b.numel() * b.element_size()):
+        _C.check(L.ofasr_quality_mse(_p(a), _dt(a), _p(b), _dt(b), N, elems, _p(out), wsp, wsn, _stream()), "quality_mse")
+    return out
+
+
 # --------------------------------------------------------------------------- kernel transform
 def _kt_args(chain, mats):
     ks = (ctypes.c_int * len(chain))(*chain)

@@ -359,3 +359,129 @@ def psnr_y_device(output, target):
         count = ((h + 2) * ymaps + 2) * ((w + 2) * xmaps + 2)
     mse = sq / count
     return 20.0 * torch.log10(255.0 / torch.sqrt(mse))
+
+
+# ------------------------------------------------------------------ Y-PSNR / Y-SSIM: the exact definition
+# The host (numpy) statement of what ops.quality_y computes on the GPU (csrc/quality.hip).  rgb2y / psnr_y /
+# psnr_y_device above are the reference's logged metric and stay as they are; they differ from y_exact only at colours
+# whose exact luma is a rounding tie (194 of the 2^24), where the fp64 summation order decides their result.
+SSIM_WINDOW = 11
+SSIM_SIGMA = 1.5
+
+
+def y_exact(img_u8):
+    """BT.601 luma of uint8 RGB [..., 3]: round_half_even((65481 R + 128553 G + 24966 B) / 255000 + 16) in integer
+    arithmetic -- the mathematically exact value of rgb2y's expression, a function of the colour alone."""
+    assert img_u8.dtype == np.uint8 and img_u8.shape[-1] >= 3
+    c = img_u8[..., :3].astype(np.int64)
+    num = 65481 * c[..., 0] + 128553 * c[..., 1] + 24966 * c[..., 2]
+    q, rem = num // 255000, num % 255000
+    y = q + 16
+    up = (rem > 127500) | ((rem == 127500) & (y % 2 == 1))
+    return (y + up).astype(np.uint8)
+
+
+def _quantise_u8(x):
+    """an operand of the metric as HWC uint8 images [N, H, W, 3]: an NCHW float batch (torch or numpy) is quantised as
+    tensor2img_np does (clamp, * 255 in fp32, round half to even), a uint8 HWC image is taken as it is"""
+    if torch.is_tensor(x):
+        x = x.detach().cpu()
+        x = x.numpy() if x.dtype == torch.uint8 else x.float().numpy()
+    x = np.asarray(x)
+    if x.dtype == np.uint8:
+        assert x.ndim == 3 and x.shape[2] == 3, "a uint8 operand is one HWC RGB image"
+        return x[None]
+    assert x.ndim == 4 and x.shape[1] == 3, "a float operand is an NCHW RGB batch"
+    q = np.rint(np.clip(x.astype(np.float32), np.float32(0), np.float32(1)) * np.float32(255.0))
+    return np.transpose(q, (0, 2, 3, 1)).astype(np.uint8)
+
+
+def _shaved_y(output, target, shave):
+    a, b = _quantise_u8(output), _quantise_u8(target)
+    if a.shape != b.shape:
+        raise ValueError("output %s and target %s differ in shape" % (a.shape, b.shape))
+    shave = int(shave)
+    if shave < 0:
+        raise ValueError("negative shave %d" % shave)
+    h, w = a.shape[1] - 2 * shave, a.shape[2] - 2 * shave
+    if h < SSIM_WINDOW or w < SSIM_WINDOW:
+        raise ValueError("a %dx%d image shaved by %d has a side below the %d-pixel SSIM window"
+                         % (a.shape[1], a.shape[2], shave, SSIM_WINDOW))
+    crop = (slice(None), slice(shave, shave + h), slice(shave, shave + w))
+    return y_exact(a)[crop], y_exact(b)[crop]
+
+
+def _gauss_valid(x, g):
+    """separable 'valid' correlation of [N, H, W] fp64 with the 1-D window g along W, then along H"""
+    k = len(g)
+    w = x.shape[2] - k + 1
+    t = sum(g[i] * x[:, :, i:i + w] for i in range(k))
+    h = x.shape[1] - k + 1
+    return sum(g[i] * t[:, i:i + h, :] for i in range(k))
+
+
+def ssim_y(output, target, shave=0):
+    """[mean SSIM of the Y channels, per image]: Wang et al. 2004 on the exact uint8 luma taken as fp64 -- 11x11 Gaussian
+    window (sigma 1.5, normalised, separable), positions where the window lies inside the shaved image only,
+    C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, sigma^2 = G*x^2 - mu^2, sigma12 = G*xy - mu1 mu2."""
+    ya, yb = _shaved_y(output, target, shave)
+    a, b = ya.astype(np.float64), yb.astype(np.float64)
+    g = np.exp(-((np.arange(SSIM_WINDOW) - SSIM_WINDOW // 2) ** 2) / (2.0 * SSIM_SIGMA ** 2))
+    g = g / g.sum()
+    c1, c2 = (0.01 * 255.0) ** 2, (0.03 * 255.0) ** 2
+    m1, m2 = _gauss_valid(a, g), _gauss_valid(b, g)
+    s1 = _gauss_valid(a * a, g) - m1 * m1
+    s2 = _gauss_valid(b * b, g) - m2 * m2
+    s12 = _gauss_valid(a * b, g) - m1 * m2
+    ssim = ((2.0 * m1 * m2 + c1) * (2.0 * s12 + c2)) / ((m1 * m1 + m2 * m2 + c1) * (s1 + s2 + c2))
+    return [float(v) for v in ssim.mean(axis=(1, 2))]
+
+
+def sse_y(output, target, shave=0):
+    """([exact integer sum of squared Y differences, per image], pixels per image) under the same definition"""
+    ya, yb = _shaved_y(output, target, shave)
+    d = ya.astype(np.int64) - yb.astype(np.int64)
+    return [int(v) for v in (d * d).sum(axis=(1, 2))], ya.shape[1] * ya.shape[2]
+
+
+def psnr_from_sse(sse, count):
+    """utils.psnr's expression on (sum of squared differences, pixel count)"""
+    mse = np.float64(sse) / np.float64(count)
+    if mse == 0:
+        return float("inf")
+    return 20 * math.log10(255.0 / math.sqrt(mse))
+
+
+class QualityResult(object):
+    """what quality_y_device returns: `sse` (int64 [N]) and `ssim` (fp64 [N]) on the GPU, `count` pixels per image.
+    The two are rows of one buffer; sse_list() / psnr() / ssim_list() read it back with one copy, once."""
+
+    def __init__(self, buf, count):
+        self.buf, self.count = buf, count
+        self.sse, self.ssim = buf[0], buf[1].view(torch.float64)
+        self._host = None
+
+    def _read(self):
+        if self._host is None:
+            h = self.buf.cpu()
+            self._host = (h[0].tolist(), h[1].view(torch.float64).tolist())
+        return self._host
+
+    def sse_list(self):
+        return list(self._read()[0])
+
+    def psnr(self):
+        return [psnr_from_sse(s, self.count) for s in self._read()[0]]
+
+    def ssim_list(self):
+        return list(self._read()[1])
+
+
+def quality_y_device(output, target, shave=0):
+    """Y-PSNR and Y-SSIM of a batch on the GPU, by the HIP kernel (ops.quality_y): no host round trip of the images and no
+    sync until psnr() / ssim_list() is asked of the result."""
+    ops._gpu(output, target)   # the host statement of the metric is ssim_y / sse_y
+    n = 1 if output.dtype == torch.uint8 else output.shape[0]
+    buf = torch.empty((2, n), dtype=torch.int64, device=output.device)
+    _, _, count = ops.quality_y(output, target, shave, out=buf)
+    return QualityResult(buf, count)

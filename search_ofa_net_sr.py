@@ -44,6 +44,10 @@ def parse_args(argv=None):
     ap.add_argument("--image-size", type=int, default=256, help="HR training patch size of the calibration images")
     ap.add_argument("--test-sizes", default=None, help="synthetic validation HR sizes, e.g. 64x64,48x80")
     ap.add_argument("--export", default=None, metavar="DIR")
+    ap.add_argument("--fitness", default="psnr", choices=["psnr", "ssim", "psnr-gpu"],
+                    help="what a candidate is scored by: psnr = the host Y-PSNR (the default), psnr-gpu / ssim = Y-PSNR / "
+                         "Y-SSIM by the HIP metric kernel (search.quality_fitness)")
+    ap.add_argument("--shave", type=int, default=0, help="border pixels the GPU metric leaves out")
     a = ap.parse_args(argv)
     if a.test_sizes:
         a.test_sizes = [tuple(int(v) for v in s.split("x")) for s in a.test_sizes.split(",")]
@@ -87,25 +91,42 @@ def main(argv=None):
         efficiency, budget = table.predict, a.budget_ms
     else:
         efficiency, budget = (lambda arch: space.macs(net, arch, lr_hw) / 1e9), a.budget_gmacs
-    fitness = search.psnr_fitness(net, calib, cfg.test_loader, mgr, space, max_calib_batches=n_batches)
+    if a.fitness == "psnr":
+        fitness = search.psnr_fitness(net, calib, cfg.test_loader, mgr, space, max_calib_batches=n_batches)
+    else:
+        fitness = search.quality_fitness(net, calib, cfg.test_loader, mgr, space, max_calib_batches=n_batches,
+                                         metric="ssim" if a.fitness == "ssim" else "psnr", shave=a.shave)
     es = search.EvolutionSearch(space, fitness, efficiency, budget, a.population, a.generations, a.parent_ratio,
                                 a.mutation_ratio, a.mutate_prob, seed=a.seed)
     best, history = es.run()
-    psnr = es.cache[space.key(best)]
+    score = es.cache[space.key(best)]
     gmacs = space.macs(net, best, lr_hw) / 1e9
-    print("best arch: %s\nY-PSNR %.3f dB  %.3f GMACs  (%d archs evaluated)" % (json.dumps(best), psnr, gmacs,
+    if a.fitness == "ssim":
+        psnr = None
+        print("best arch: %s\nY-SSIM %.4f  %.3f GMACs  (%d archs evaluated)" % (json.dumps(best), score, gmacs,
                                                                               len(es.evaluated)))
+    else:
+        psnr = score
+        print("best arch: %s\nY-PSNR %.3f dB  %.3f GMACs  (%d archs evaluated)" % (json.dumps(best), psnr, gmacs,
+                                                                                  len(es.evaluated)))
     if a.export:
         snap = search.bn_buffers(net)
         space.apply(net, best)
         eutils.recalibrate_bn(net, calib, input_key=search.lr_key(net), max_batches=n_batches)
         static = ev.export_static(net, a.export)
+        quality = None
+        if a.fitness != "psnr":      # the winner's numbers by the GPU metric, on the re-calibrated supernet path
+            quality = mgr.validate_quality(net=net, data_loader=cfg.test_loader, input_key=search.lr_key(net), graphs=False,
+                                           shave=a.shave)
+            psnr = quality["psnr"]
         search.restore_bn_buffers(net, snap)
         result = {"arch": best, "psnr": psnr, "gmacs": gmacs, "lr_size": list(lr_hw),
                   "predicted_ms": table.predict(best) if table is not None else None,
                   "measured_ms": search.measure(static, a.lat_batch, lr_hw[0], lr_hw[1]) if table is not None else None,
                   "history": history, "evaluated": len(es.evaluated), "seed": a.seed, "budget": budget,
                   "budget_kind": "ms" if a.budget_ms is not None else "gmacs"}
+        if quality is not None:
+            result.update({"ssim": quality["ssim"], "fitness": a.fitness, "shave": a.shave})
         with open(os.path.join(a.export, "search.json"), "w") as f:
             json.dump(result, f, indent=1)
         print("exported to %s" % a.export)

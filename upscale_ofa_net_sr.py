@@ -5,7 +5,9 @@ The network is a static SRNetS4 / SRNetX4 exported with `search_ofa_net_sr.py --
 `eval_ofa_net_sr.py --export DIR` (DIR/net_config.json + DIR/static_state_dict.pth); a supernet checkpoint is not loaded
 here: export its sub-network first.  Inputs are image files or directories of them; grayscale and RGBA images become RGB,
 and every output is written as OUTDIR/<name>.png.  The next image is decoded (and the previous one encoded) on a small
-host thread pool while the GPU upscales the current one.  Prints output megapixels per second at the end."""
+host thread pool while the GPU upscales the current one.  Prints output megapixels per second at the end.
+--reference DIR scores every output against the equally named ground-truth image in DIR on the GPU (Y-PSNR and Y-SSIM by
+the HIP metric kernel, --shave border pixels left out), prints the numbers and writes them to OUTDIR/quality.json."""
 import argparse
 import collections
 import concurrent.futures
@@ -33,6 +35,9 @@ def parse_args(argv=None):
                     help="core tile side in input pixels (default: the largest that keeps every activation < 2 GiB)")
     ap.add_argument("--batch", type=int, default=None, help="windows per forward call (default: as many as fit)")
     ap.add_argument("--whole", action="store_true", help="run each image as one forward call (small images only)")
+    ap.add_argument("--reference", default=None, metavar="PATH",
+                    help="directory of ground-truth HR images named as the inputs: report Y-PSNR / Y-SSIM per image")
+    ap.add_argument("--shave", type=int, default=0, help="with --reference: border pixels left out of the metric")
     ap.add_argument("inputs", nargs="+", metavar="INPUT", help="image files or directories")
     return ap.parse_args(argv)
 
@@ -74,6 +79,16 @@ def out_path(out_dir, path, taken):
     return p
 
 
+def reference_path(ref_dir, path):
+    """the ground-truth image of input `path`: the file of the same stem in ref_dir"""
+    stem = os.path.splitext(os.path.basename(path))[0]
+    for ext in (os.path.splitext(path)[1],) + EXTS:
+        p = os.path.join(ref_dir, stem + ext)
+        if os.path.isfile(p):
+            return p
+    raise SystemExit("no reference image for %s in %s" % (path, ref_dir))
+
+
 def main(argv=None):
     a = parse_args(argv)
     files = list_inputs(a.inputs)
@@ -92,6 +107,12 @@ def main(argv=None):
     taken = set()
     mpix = 0.0
     saves = []
+    scores = []
+    if a.reference is not None:
+        utils = importlib.import_module(PKG + ".utils")
+        if not os.path.isdir(a.reference):
+            raise SystemExit("--reference %s is not a directory" % a.reference)
+        refs = [reference_path(a.reference, f) for f in files]
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(WORKERS, len(files) + 1)) as pool:
         pending = collections.deque(pool.submit(decode, f) for f in files[:2])
         t0 = time.perf_counter()
@@ -100,7 +121,18 @@ def main(argv=None):
             if i + 2 < len(files):
                 pending.append(pool.submit(decode, files[i + 2]))
             plan = None if a.whole else up.plan(img.shape[0], img.shape[1])
-            out = up.upscale(torch.from_numpy(img), whole=a.whole).cpu().numpy()
+            out_gpu = up.upscale(torch.from_numpy(img), whole=a.whole)
+            if a.reference is not None:
+                ref = decode(refs[i])
+                if ref.shape != tuple(out_gpu.shape):
+                    raise SystemExit("%s is %dx%d, the upscaled %s is %dx%d: the reference must have the output's size"
+                                     % (refs[i], ref.shape[1], ref.shape[0], f, out_gpu.shape[1], out_gpu.shape[0]))
+                if min(ref.shape[:2]) - 2 * a.shave < 11 or a.shave < 0:
+                    raise SystemExit("%s: a %dx%d image shaved by %d has a side below the 11-pixel SSIM window"
+                                     % (refs[i], ref.shape[1], ref.shape[0], a.shave))
+                scores.append((f, refs[i], utils.quality_y_device(out_gpu, torch.from_numpy(ref).to(out_gpu.device),
+                                                                  a.shave)))
+            out = out_gpu.cpu().numpy()
             dst = out_path(a.out, f, taken)
             saves.append(pool.submit(encode, out, dst))
             mpix += out.shape[0] * out.shape[1] / 1e6
@@ -112,6 +144,17 @@ def main(argv=None):
         for s in saves:
             s.result()
     dt_all = time.perf_counter() - t0
+    if a.reference is not None:
+        import json
+        recs = []
+        for f, r, q in scores:
+            recs.append({"input": f, "reference": r, "psnr": q.psnr()[0], "ssim": q.ssim_list()[0], "sse": q.sse_list()[0],
+                         "count": q.count})
+            print("%s: Y-PSNR %.3f dB  Y-SSIM %.4f" % (f, recs[-1]["psnr"], recs[-1]["ssim"]))
+        mean = {"psnr": sum(x["psnr"] for x in recs) / len(recs), "ssim": sum(x["ssim"] for x in recs) / len(recs)}
+        print("mean of %d images: Y-PSNR %.3f dB  Y-SSIM %.4f  (shave %d)" % (len(recs), mean["psnr"], mean["ssim"], a.shave))
+        with open(os.path.join(a.out, "quality.json"), "w") as fh:
+            json.dump({"shave": a.shave, "images": recs, "mean": mean}, fh, indent=1)
     print("%d images, %.2f output MP in %.3f s: %.2f MP/s (%.2f MP/s with PNG encoding)" % (
         len(files), mpix, dt, mpix / dt, mpix / dt_all))
 
