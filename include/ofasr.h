@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 304 /* + ofasr_quality_y, ofasr_quality_mse (+ workspace queries) */
+#define OFASR_VERSION 305 /* + ofasr_aug_gather_u8 */
 
 typedef enum {
     OFASR_OK = 0,
@@ -417,6 +417,29 @@ int ofasr_tile_gather_u8(const void* img, int64_t H, int64_t W, const int64_t* o
                          void* out, int dtype, void* stream);
 int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table, void* img,
                           int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training augmentation on GPU-resident images: RandomCrop(S) -> RandomHorizontalFlip -> RandomRotation (nearest, same
+ * canvas, zero fill) of the host provider (data_providers/div2k_setxx.py) as one integer gather, bit-equal to the PIL
+ * calls (host statement: data_providers/augment.py).  One launch per batch.
+ *   pool:    device uint8 buffer of pool_bytes bytes holding decoded HWC RGB images.
+ *   table:   device int64 [n][12] = (offset, H, W, i, j, flip, a0, a1, a2, a3, a4, a5): offset = byte offset of an
+ *            [H, W, 3] image in pool, (i, j) = top-left corner of the S x S crop, a* = the 16.16 fixed-point affine
+ *            coefficients of Pillow's Image.rotate(angle, NEAREST) on an S x S canvas (augment.rotate_coeffs).
+ *   out_u8:  NCHW [n, 3, S, S] uint8.   out_f32: NULL, or the same batch as fp32, (float)v / 255.0f (correctly rounded
+ *            fp32 division: bit-equal to the host's .float().div_(255.0), i.e. torchvision's ToTensor).
+ *   per output (n, c, y, x):  xin = (a2 + y*a1 + x*a0) >> 16,  yin = (a5 + y*a4 + x*a3) >> 16   (int32, arithmetic shift)
+ *            xin or yin outside [0, S): 0.  Otherwise col = flip ? S-1-xin : xin (crop, then flip, then rotate: the flip
+ *            applies to the rotation's source) and the value is pool[offset + ((i+yin)*W + j+col)*3 + c].
+ * Table entries are clamped in the kernel: S <= H, W <= 2^24, 0 <= i <= H-S, 0 <= j <= W-S, 0 <= offset <= pool_bytes, and
+ * every pixel's byte address to [0, pool_bytes-3], so no table content makes an access leave pool.
+ * OFASR_ERR_UNSUPPORTED: S > 4096 (with S <= 4096 and |a0|+|a1| <= 65536 sqrt 2 the sums stay below 7.1e8 < 2^31),
+ * n > 65535, pool_bytes < 3*S*S (no image with H, W >= S fits).  The table is device memory, so H, W >= S per row is
+ * the caller's contract (augment.make_table refuses it on the host); the clamps above hold regardless.
+ * Plain loads and stores, no atomics: two calls give identical bytes.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_aug_gather_u8(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, void* out_u8,
+                        void* out_f32, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Y-channel quality metrics: exact SSE (for Y-PSNR) and mean SSIM of two image batches, per image  -- replaces the host

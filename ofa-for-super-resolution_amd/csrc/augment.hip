@@ -1,0 +1,141 @@
+// augment.hip -- the training augmentation on GPU-resident images (ofasr_aug_gather_u8).
+//
+// The DIV2K training sample is RandomCrop(S) -> RandomHorizontalFlip -> RandomRotation((-90, 90)) of a decoded RGB image
+// (data_providers/div2k_setxx.py).  With the decoded images resident in one uint8 pool, the three transforms are one
+// integer gather per output pixel, bit-equal to the PIL calls of the host provider (host statement and the derivation of
+// the coefficients: data_providers/augment.py; Pillow's Image.rotate(angle, NEAREST) walks its 2x3 matrix in 16.16 fixed
+// point for images below 32768 pixels per side -- affine_fixed in Geometry.c):
+//   xin = (a2 + y * a1 + x * a0) >> 16,  yin = (a5 + y * a4 + x * a3) >> 16        (arithmetic shift)
+//   out[n, c, y, x] = 0 <= xin, yin < S ? pool[offset + ((i + yin) * W + j + (flip ? S - 1 - xin : xin)) * 3 + c] : 0
+// per sample n from the device table row (offset, H, W, i, j, flip, a0 .. a5): the flip applies to the rotation's source
+// because the pipeline flips before it rotates.  One launch per batch; the optional second output is the same batch as
+// fp32, (float)v / 255.0f with fp32 division (ToTensor, bit for bit).
+//
+// int32 is enough.  |a0| + |a1| <= 65536 * sqrt 2 (a cosine and a sine of one angle, rounded), x, y <= S - 1 <= 4095, so
+// |y * a1 + x * a0| <= 4095 * 92682 < 3.80e8; a2 = FIX(S/2 * (1 - m0 - m1) + (m0 + m1) / 2) has |a2| <= 65536 * (2048 *
+// (1 + sqrt 2) + 0.71) < 3.25e8.  The sum stays below 7.1e8 < 2^31; the same holds for the second row.  The kernel adds
+// in uint32 all the same, so a table of garbage wraps instead of being undefined, and what it yields is clamped.
+//
+// Nothing leaves the pool whatever the table holds: H and W are clamped to [S, 2^24], (i, j) to [0, H - S] x [0, W - S],
+// offset to [0, pool_bytes], and the byte address of every pixel to [0, pool_bytes - 3].  Addresses are 64-bit.
+//
+// Access.  A lane owns 4 adjacent output columns of one row.  Its 12 source bytes are 12 byte loads: after a rotation
+// neighbouring output pixels are not neighbours in the source, and a pixel's 3 bytes have no alignment.  Every load is
+// issued unconditionally from a clamped address and the zero fill is selected afterwards, so no load waits under a
+// lane-dependent branch: the 12 loads are in flight together (the only guard is the exit of lanes past the end of the
+// plane, before any address is formed).  Stores: one dword per plane for the uint8 batch and one 16-byte vector per
+// plane for the fp32 batch when S % 4 == 0 and the outputs are aligned for them; element stores otherwise (S = 30: rows
+// are not dword-aligned).
+#include "ofasr_common.h"
+
+namespace ofasr {
+
+// grid: (x: lanes over S * ceil(S / 4) groups, y: sample)
+template <bool VEC, bool F32>
+__global__ void __launch_bounds__(256) aug_gather_u8_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                            const long long* __restrict__ table, int S,
+                                                            uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
+    const long long n = blockIdx.y;
+    const long long* t = table + 12 * n;
+    long long off = t[0], H = t[1], W = t[2], ci = t[3], cj = t[4];
+    const bool flip = t[5] != 0;
+    const uint32_t a0 = (uint32_t)t[6], a1 = (uint32_t)t[7], a2 = (uint32_t)t[8];
+    const uint32_t a3 = (uint32_t)t[9], a4 = (uint32_t)t[10], a5 = (uint32_t)t[11];
+    const long long lim = 1LL << 24;
+    H = H < S ? S : (H > lim ? lim : H);
+    W = W < S ? S : (W > lim ? lim : W);
+    ci = ci < 0 ? 0 : (ci > H - S ? H - S : ci);
+    cj = cj < 0 ? 0 : (cj > W - S ? W - S : cj);
+    off = off < 0 ? 0 : (off > pool_bytes ? pool_bytes : off);
+    const long long last = pool_bytes - 3;
+    const int gw = (S + 3) >> 2;
+    const int total = S * gw;
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= total) return;   // whole lanes past the end of the plane; nothing below branches around a load
+    const int y = e / gw;
+    const int x0 = (e - y * gw) * 4;
+    uint32_t fx = a2 + (uint32_t)y * a1 + (uint32_t)x0 * a0;
+    uint32_t fy = a5 + (uint32_t)y * a4 + (uint32_t)x0 * a3;
+    uint32_t v[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xin = (int)fx >> 16, yin = (int)fy >> 16;
+        const bool ok = xin >= 0 && xin < S && yin >= 0 && yin < S;
+        const int xc = xin < 0 ? 0 : (xin > S - 1 ? S - 1 : xin);
+        const int yc = yin < 0 ? 0 : (yin > S - 1 ? S - 1 : yin);
+        const int col = flip ? S - 1 - xc : xc;
+        long long b = off + ((ci + yc) * W + cj + col) * 3;
+        b = b > last ? last : b;
+        const uint8_t* p = pool + b;
+        const uint32_t r0 = p[0], r1 = p[1], r2 = p[2];
+        v[k][0] = ok ? r0 : 0u;
+        v[k][1] = ok ? r1 : 0u;
+        v[k][2] = ok ? r2 : 0u;
+        fx += a0;
+        fy += a3;
+    }
+    const long long plane = (long long)S * S;
+    const long long o = n * 3 * plane + (long long)y * S + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        uint8_t* d8 = out_u8 + o + c * plane;
+        if (VEC) {
+            *reinterpret_cast<uint32_t*>(d8) = v[0][c] | v[1][c] << 8 | v[2][c] << 16 | v[3][c] << 24;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < S) d8[k] = (uint8_t)v[k][c];
+        }
+        if (F32) {
+            float f[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) f[k] = __fdiv_rn((float)v[k][c], 255.0f);
+            float* df = out_f32 + o + c * plane;
+            if (VEC) {
+                *reinterpret_cast<float4*>(df) = make_float4(f[0], f[1], f[2], f[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x0 + k < S) df[k] = f[k];
+            }
+        }
+    }
+}
+
+template <bool VEC, bool F32>
+static void aug_launch(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, void* out_u8,
+                       void* out_f32, hipStream_t st) {
+    const dim3 grid((unsigned)cdiv(S * cdiv(S, 4), 256), (unsigned)n);
+    prof_note((double)n * (double)(S * S) * 3.0 * (F32 ? 6.0 : 2.0), 0.0);
+    OFASR_LAUNCH((aug_gather_u8_kernel<VEC, F32>), grid, dim3(256), 0, st, (const uint8_t*)pool, (long long)pool_bytes,
+                 (const long long*)table, (int)S, (uint8_t*)out_u8, (float*)out_f32);
+}
+
+}  // namespace ofasr
+
+using namespace ofasr;
+
+OFASR_EXPORT int ofasr_aug_gather_u8(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S,
+                                     void* out_u8, void* out_f32, void* stream) {
+    const char* name = "ofasr_aug_gather_u8";
+    OFASR_REQUIRE(pool && table && out_u8, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE(n > 0 && S > 0 && pool_bytes > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
+    OFASR_REQUIRE(S <= 4096, OFASR_ERR_UNSUPPORTED, "%s: crop side %lld above 4096 (the fixed-point walk is int32)", name,
+                  (long long)S);
+    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: %lld samples in one launch (at most 65535)", name, (long long)n);
+    // the table lives on the device: the smallest pool that can hold one H, W >= S image is what the host can check
+    OFASR_REQUIRE(pool_bytes >= 3 * S * S, OFASR_ERR_UNSUPPORTED,
+                  "%s: a pool of %lld bytes holds no image of at least %lldx%lld (H, W >= S)", name, (long long)pool_bytes,
+                  (long long)S, (long long)S);
+    hipStream_t st = as_stream(stream);
+    const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(out_u8) % 4 == 0 &&
+                     reinterpret_cast<uintptr_t>(out_f32) % 16 == 0;
+    if (out_f32) {
+        if (vec) aug_launch<true, true>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
+        else aug_launch<false, true>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
+    } else {
+        if (vec) aug_launch<true, false>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
+        else aug_launch<false, false>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
+    }
+    return check_launch(name);
+}

@@ -239,14 +239,19 @@ class Div2K_SetXXDataProvider(DataProvider):
     Sharding under data parallelism (num_replicas given): the TRAINING indices are split over the ranks by
     RankShardSampler; the validation / test images are NOT split -- every rank evaluates the whole (14-image) set in
     file order, so the logged PSNR, `best_acc` and `model_best` are the same on every rank count.  (The reference
-    wraps the test set in a shuffling, padding DistributedSampler with drop_last and never reduces the metric.)"""
+    wraps the test set in a shuffling, padding DistributedSampler with drop_last and never reduces the metric.)
+
+    `resident=True`: the training images are decoded once into GPU memory and `train` (and the batches of
+    `build_sub_train_loader`) come from augment.ResidentTrainLoader -- the same crop / flip / rotation, bit for bit, as
+    one HIP gather per batch; the batches are {'image_u8'[, 'image']} on the GPU.  `valid` / `test` are unchanged."""
     DEFAULT_PATH = "/SSD/div2k_setxx"
 
     def __init__(self, save_path=None, train_batch_size=256, test_batch_size=512, valid_size=None, n_worker=32,
                  resize_scale=0.08, distort_color=None, image_size=32, num_replicas=None, rank=None,
-                 lr_on_device=False):
+                 lr_on_device=False, resident=False, resident_max_bytes=32 << 30):
         warnings.filterwarnings("ignore")
         self.lr_on_device = bool(lr_on_device)
+        self.resident = bool(resident)
         if Image is None:
             raise ImportError("Div2K_SetXXDataProvider needs PIL")
         self._save_path = save_path
@@ -275,7 +280,14 @@ class Div2K_SetXXDataProvider(DataProvider):
             train_sampler = torch.utils.data.SubsetRandomSampler(train_idx)
         else:
             train_sampler = torch.utils.data.RandomSampler(train_set)
-        self.train = self._loader(train_set, train_batch_size, train_sampler, drop_last=True)
+        if self.resident:
+            from .augment import ResidentTrainLoader, ResidentTrainSet
+            self.resident_set = ResidentTrainSet(train_set.paths, torch.device("cuda", torch.cuda.current_device()),
+                                                 max_bytes=resident_max_bytes)
+            self.train = ResidentTrainLoader(self.resident_set, train_batch_size, train_sampler, self.active_img_size,
+                                             drop_last=True, want_f32=True)
+        else:
+            self.train = self._loader(train_set, train_batch_size, train_sampler, drop_last=True)
         self.test = self._loader(self.test_dataset(eval_tf), test_batch_size, None, drop_last=False)
         if valid_idx is None:
             self.valid = self.test
@@ -358,6 +370,11 @@ class Div2K_SetXXDataProvider(DataProvider):
             else:
                 sampler = torch.utils.data.SubsetRandomSampler(chosen)
             workers = self._workers if num_worker is None else num_worker
-            cache[key] = list(torch.utils.data.DataLoader(ds, batch_size=batch_size, sampler=sampler,
-                                                          num_workers=workers, pin_memory=True))
+            if self.__dict__.get("resident", False):
+                from .augment import ResidentTrainLoader
+                cache[key] = list(ResidentTrainLoader(self.resident_set, batch_size, sampler, self.active_img_size,
+                                                      drop_last=False))
+            else:
+                cache[key] = list(torch.utils.data.DataLoader(ds, batch_size=batch_size, sampler=sampler,
+                                                              num_workers=workers, pin_memory=True))
         return cache[key]

@@ -44,7 +44,8 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                  dataset="div2k_setxx", train_batch_size=256, test_batch_size=500, valid_size=None, opt_type="sgd",
                  opt_param=None, weight_decay=4e-5, label_smoothing=0.1, no_decay_keys=None, mixup_alpha=None,
                  model_init="he_fout", validation_frequency=1, print_frequency=10, n_worker=32,
-                 resize_scale=0.08, distort_color=None, image_size=32, allow_synthetic=None, **kwargs):
+                 resize_scale=0.08, distort_color=None, image_size=32, allow_synthetic=None, resident=False,
+                 **kwargs):
         super().__init__(n_epochs, init_lr, lr_schedule_type, lr_schedule_param, dataset, train_batch_size,
                          test_batch_size, valid_size, opt_type, opt_param, weight_decay, label_smoothing,
                          no_decay_keys, mixup_alpha, model_init, validation_frequency, print_frequency,
@@ -53,6 +54,7 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                                                                      "data_seed", "test_sizes")})
         self.resize_scale = resize_scale
         self.distort_color = distort_color
+        self.resident = bool(resident)
         self.dataset_root = os.environ.get("OFASR_DIV2K_ROOT", "/SSD/div2k_setxx")
         self.allow_synthetic = (os.environ.get("OFASR_ALLOW_SYNTHETIC_DATA", "0") == "1") if allow_synthetic is None \
             else bool(allow_synthetic)
@@ -69,7 +71,8 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                     save_path=root, train_batch_size=self.train_batch_size, test_batch_size=self.test_batch_size,
                     valid_size=self.valid_size, n_worker=self.n_worker, resize_scale=self.resize_scale,
                     distort_color=self.distort_color, image_size=self.image_size,
-                    num_replicas=ws if ws > 1 else None, rank=dd.rank() if ws > 1 else None)
+                    num_replicas=ws if ws > 1 else None, rank=dd.rank() if ws > 1 else None,
+                    resident=self.resident)
             elif self.allow_synthetic:
                 from ... import distributed as dd
                 if dd.rank() == 0:

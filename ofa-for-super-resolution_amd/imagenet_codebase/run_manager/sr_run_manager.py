@@ -31,7 +31,7 @@ class RunConfig(object):
 
     def __init__(self, n_epochs, init_lr, lr_schedule_type, lr_schedule_param, dataset, train_batch_size,
                  test_batch_size, valid_size, opt_type, opt_param, weight_decay, label_smoothing, no_decay_keys,
-                 mixup_alpha, model_init, validation_frequency, print_frequency):
+                 mixup_alpha, model_init, validation_frequency, print_frequency, resident=False):
         self.n_epochs = n_epochs
         self.init_lr = init_lr
         self.lr_schedule_type = lr_schedule_type
@@ -49,6 +49,7 @@ class RunConfig(object):
         self.model_init = model_init
         self.validation_frequency = validation_frequency
         self.print_frequency = print_frequency
+        self.resident = bool(resident)   # DIV2K provider: training set resident on the GPU (data_providers/augment.py)
 
     @property
     def config(self):

@@ -182,16 +182,57 @@ def bicubic_resize_u8(img, out_h, out_w):
     return out
 
 
-def lr_images_from_u8(hr_u8):
+def lr_images_from_u8(hr_u8, image=None):
     """{'image', '2x_down_image', '4x_down_image'} (float32 in [0, 1], the loader contract of the reference's
     Div2K_SetXXDataset.__getitem__, div2k_setxx.py:288-298) from a uint8 HR batch [N, 3, H, W] already on the GPU:
-    Scale(1/2) and Scale(1/4) as PIL computes them (output size int(h/f) x int(w/f)), then ToTensor's /255."""
+    Scale(1/2) and Scale(1/4) as PIL computes them (output size int(h/f) x int(w/f)), then ToTensor's /255.
+    `image`: the fp32 HR batch where the caller already has it (aug_gather_u8's second output: u8 / 255 with a correctly
+    rounded division, ToTensor's bits), reused as it is; the LR images are then divided exactly as well."""
     _, _, H, W = hr_u8.shape
-    out = {"image": hr_u8.float().div_(255.0)}
+    if image is not None and (image.dtype != torch.float32 or image.shape != hr_u8.shape or image.device != hr_u8.device):
+        raise _C.OfasrError("lr_images_from_u8: image= must be the float32 batch of hr_u8 (%s on %s), got %s %s on %s"
+                            % (tuple(hr_u8.shape), hr_u8.device, image.dtype, tuple(image.shape), image.device))
+    out = {"image": hr_u8.float().div_(255.0) if image is None else image}
     for f in (2, 4):
         lr = bicubic_resize_u8(hr_u8, int(H * (1.0 / f)), int(W * (1.0 / f)))
-        out["%dx_down_image" % f] = lr.float().div_(255.0)
+        # ATen's GPU division by a host scalar multiplies by the rounded reciprocal: up to 1 ulp from ToTensor's v / 255.
+        # Beside an exact `image` the LR images are exact too (a table of the 256 quotients), so the whole batch equals
+        # the host provider's bit for bit; without `image` the values stay what they were.
+        out["%dx_down_image" % f] = lr.float().div_(255.0) if image is None else _unit_lut(lr.device)[lr.long()]
     return out
+
+
+_UNIT_LUT = {}
+
+
+def _unit_lut(device):
+    """v / 255 for v = 0 .. 255 with a correctly rounded fp32 division (formed on the host), on `device`"""
+    t = _UNIT_LUT.get(device)
+    if t is None:
+        t = _UNIT_LUT[device] = torch.arange(256, dtype=torch.float32).div_(255.0).to(device)
+    return t
+
+
+# ------------------------------------------------------------- training augmentation on resident images
+def aug_gather_u8(pool, table, n, S, want_f32=False):
+    """The augmented HR batch [n, 3, S, S] (uint8; with `want_f32` the pair (uint8, float32 = u8 / 255)) gathered from a
+    resident uint8 image pool: crop -> horizontal flip -> nearest rotation with zero fill per row of the int64 [n, 12]
+    device table (offset, H, W, i, j, flip, a0 .. a5), bit-equal to the PIL transforms of div2k_setxx.py
+    (ofasr_aug_gather_u8, csrc/augment.hip; the table is made by data_providers/augment.make_table)."""
+    _gpu(pool, table)
+    n, S = int(n), int(S)
+    if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
+        raise _C.OfasrError("aug_gather_u8: pool is a contiguous 1-D uint8 tensor, got %s %s" % (pool.dtype, tuple(pool.shape)))
+    if table.dtype != torch.int64 or table.dim() != 2 or table.size(1) != 12 or table.size(0) < n or \
+            not table.is_contiguous() or table.device != pool.device:
+        raise _C.OfasrError("aug_gather_u8: table is a contiguous int64 [>= %d, 12] tensor on %s, got %s %s on %s"
+                            % (n, pool.device, table.dtype, tuple(table.shape), table.device))
+    out = torch.empty((max(n, 0), 3, max(S, 0), max(S, 0)), dtype=torch.uint8, device=pool.device)
+    f32 = torch.empty(out.shape, dtype=torch.float32, device=pool.device) if want_f32 else None
+    with _timed("aug_gather_u8", out.numel() * (6 if want_f32 else 2)):
+        _C.check(_C.lib().ofasr_aug_gather_u8(_p(pool), pool.numel(), _p(table), n, S, _p(out),
+                                              _p(f32) if want_f32 else None, _stream()), "aug_gather_u8")
+    return (out, f32) if want_f32 else out
 
 
 # ------------------------------------------------------------------------------ Y-PSNR / Y-SSIM on the GPU

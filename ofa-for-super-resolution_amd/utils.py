@@ -221,9 +221,12 @@ def bucket_by_size(items, key=None, max_batch=None):
 def device_batch(mini_batch, device):
     """a loader batch on `device` under the reference's keys.  Batches of a provider built with lr_on_device=True carry
     only 'image_u8' (uint8 HR): the LR images are then made on the GPU with PIL's exact bicubic arithmetic
-    (ops.lr_images_from_u8) instead of by the host-side PIL calls of div2k_setxx.py:288-298."""
+    (ops.lr_images_from_u8) instead of by the host-side PIL calls of div2k_setxx.py:288-298.  A resident loader
+    (data_providers/augment.py) may hand over the fp32 HR batch beside it ('image'), which is then reused."""
     if "image_u8" in mini_batch:
-        return ops.lr_images_from_u8(mini_batch["image_u8"].to(device, non_blocking=True))
+        image = mini_batch.get("image")
+        return ops.lr_images_from_u8(mini_batch["image_u8"].to(device, non_blocking=True),
+                                     image=None if image is None else image.to(device, non_blocking=True))
     return {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in mini_batch.items()}
 
 

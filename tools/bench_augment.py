@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Training input path on resident images (ops.aug_gather_u8, csrc/augment.hip, data_providers/augment.py):
+ * kernel time at N=16, S=256 with and without the fp32 output (library per-launch events) against the byte floor --
+   bytes written plus source bytes touched (one 3-byte pixel per output pixel) at the measured 6.3 TB/s copy rate;
+ * loader throughput in img/s over >= 200 batches after a warm-up: the resident loader (augmented batch + the LR images
+   of utils.device_batch, GPU time included) and the DataLoader path of the same provider with n_worker=16 (batch on the
+   device, LR images included), both on a directory of synthetic PNGs the tool writes itself (32 files of 2040x1356
+   under 256 names).
+Prints one JSON line.
+usage: python tools/bench_augment.py [--files 32] [--entries 256] [--height 1356] [--width 2040] [--batches 200]
+                                     [--warmup 10] [--host-batches 200] [--workers 16] [--skip-host]"""
+import argparse
+import importlib
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "ofa-for-super-resolution_amd"
+COPY_TBPS = 6.3
+
+
+def write_pngs(root, files, entries, h, w):
+    """`files` distinct PNGs and links to them up to `entries` names, so that an epoch is long enough to keep every
+    DataLoader worker busy (a worker makes a whole batch) without writing hundreds of large files"""
+    import numpy as np
+    from PIL import Image
+    os.makedirs(os.path.join(root, "train"))
+    os.makedirs(os.path.join(root, "val"))
+    rng = np.random.RandomState(0)
+    yy, xx = np.mgrid[0:h, 0:w]
+    # a smooth colour field with mild noise: compresses like a photograph rather than like white noise
+    base = np.stack([127 + 120 * np.sin(yy / 37.0 + c) * np.cos(xx / 53.0 - c) for c in range(3)], -1)
+    for k in range(files):
+        a = np.clip(np.roll(base, 61 * k, axis=1) + rng.randint(-6, 7, (h, w, 3)), 0, 255).astype(np.uint8)
+        Image.fromarray(a).save(os.path.join(root, "train", "img%04d.png" % k), compress_level=3)
+    for k in range(files, entries):
+        os.symlink("img%04d.png" % (k % files), os.path.join(root, "train", "img%04d.png" % k))
+    Image.fromarray(np.zeros((64, 64, 3), np.uint8)).save(os.path.join(root, "val", "v.png"))
+
+
+def loader_rate(loader, batches, warmup, step, sync):
+    """img/s over `batches` batches after `warmup`, cycling through epochs; `step` consumes a batch on the GPU"""
+    done, images, t0 = 0, 0, None
+    while done < warmup + batches:
+        for b in loader:
+            n = step(b)
+            done += 1
+            if done == warmup:
+                sync()
+                t0 = time.perf_counter()
+            elif done > warmup:
+                images += n
+            if done >= warmup + batches:
+                break
+    sync()
+    return images / (time.perf_counter() - t0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=32)
+    ap.add_argument("--entries", type=int, default=256, help="names in train/ (links to the files beyond --files)")
+    ap.add_argument("--height", type=int, default=1356)
+    ap.add_argument("--width", type=int, default=2040)
+    ap.add_argument("--batches", type=int, default=200)
+    ap.add_argument("--host-batches", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--skip-host", action="store_true")
+    a = ap.parse_args()
+    import torch
+    C = importlib.import_module(PKG + "._C")
+    ops = importlib.import_module(PKG + ".ops")
+    utils = importlib.import_module(PKG + ".utils")
+    aug = importlib.import_module(PKG + ".imagenet_codebase.data_providers.augment")
+    dp = importlib.import_module(PKG + ".imagenet_codebase.data_providers.div2k_setxx")
+    L = C.lib()
+    sync = torch.cuda.synchronize
+    dev = torch.device("cuda", 0)
+    N, S = 16, 256
+    out = {"N": N, "S": S, "copy_TBps": COPY_TBPS, "files": a.files, "entries": max(a.entries, a.files),
+           "file_hw": [a.height, a.width]}
+    root = tempfile.mkdtemp(prefix="bench_augment_")
+    try:
+        t0 = time.perf_counter()
+        write_pngs(root, a.files, max(a.entries, a.files), a.height, a.width)
+        out["write_pngs_s"] = time.perf_counter() - t0
+        kw = dict(save_path=root, train_batch_size=N, test_batch_size=1, image_size=S)
+        t0 = time.perf_counter()
+        prov = dp.Div2K_SetXXDataProvider(n_worker=0, resident=True, **kw)
+        sync()
+        out["resident_decode_upload_s"] = time.perf_counter() - t0
+        out["resident_bytes"] = prov.resident_set.nbytes
+        loader = prov.train
+
+        # ---- the kernel: library per-launch events over `reps` launches with freshly drawn tables
+        torch.manual_seed(0)
+        ds = prov.resident_set
+        tables = []
+        for r in range(a.reps):
+            idx = torch.randint(0, len(ds), (N,)).tolist()
+            rows = [ds.entries[k] + (aug.draw_train_params(ds.entries[k][1], ds.entries[k][2], S),) for k in idx]
+            tables.append(aug.make_table(rows, S).to(dev))
+        for want_f32 in (False, True):
+            ops.aug_gather_u8(ds.pool, tables[0], N, S, want_f32=want_f32)
+            sync()
+            L.ofasr_profile_enable(1)
+            C.profile_read()
+            for t in tables:
+                ops.aug_gather_u8(ds.pool, t, N, S, want_f32=want_f32)
+            prof = C.profile_read()
+            L.ofasr_profile_enable(0)
+            us = sum(v["total_us"] for k, v in prof.items() if "aug_gather_u8_kernel" in k) / a.reps
+            floor_bytes = N * 3 * S * S * (2 + (4 if want_f32 else 0))
+            floor_us = floor_bytes / (COPY_TBPS * 1e12) * 1e6
+            out["kernel_f32" if want_f32 else "kernel_u8"] = {
+                "kernel_us": us, "floor_bytes": floor_bytes, "floor_us": floor_us, "fraction_of_floor": floor_us / us,
+                "launches": a.reps}
+
+        # ---- the loaders: a batch counts when its HR + LR images are on the device
+        def step(b):
+            d = utils.device_batch(b, dev)
+            return d["image"].size(0)
+
+        out["resident_img_per_s"] = loader_rate(loader, a.batches, a.warmup, step, sync)
+        plain = aug.ResidentTrainLoader(ds, N, loader.sampler, S, want_f32=False)
+        out["resident_u8_only_img_per_s"] = loader_rate(plain, a.batches, a.warmup, lambda b: b["image_u8"].size(0), sync)
+        if not a.skip_host:
+            for name, lr_on_device in (("dataloader_img_per_s", False), ("dataloader_lr_on_device_img_per_s", True)):
+                host = dp.Div2K_SetXXDataProvider(n_worker=a.workers, lr_on_device=lr_on_device, **kw)
+                out[name] = loader_rate(host.train, a.host_batches, min(a.warmup, 2), step, sync)
+                del host
+            out["dataloader_workers"] = a.workers
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--image-size", type=int, default=256)
     ap.add_argument("--n-train-batches", type=int, default=8)
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic images when DIV2K is absent")
+    ap.add_argument("--resident", action="store_true",
+                    help="keep the decoded training images on the GPU and augment them there")
     args = ap.parse_args()
 
     import numpy as np
