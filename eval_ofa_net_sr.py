@@ -64,8 +64,13 @@ def main(argv=None):
     ap.add_argument("--test-sizes", default=None, help="synthetic test HR sizes instead of the Set14-like ones, e.g. 64x64,48x80")
     ap.add_argument("--ssim", action="store_true", help="also report Y-SSIM (and the exact-luma Y-PSNR), scored on the GPU "
                                                         "by the HIP metric kernel (SRRunManager.validate_quality)")
-    ap.add_argument("--shave", type=int, default=0, help="with --ssim: border pixels left out of the metric")
+    ap.add_argument("--shave", type=int, default=0, help="with --ssim / --self-ensemble: border pixels left out of the metric")
+    ap.add_argument("--self-ensemble", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
+                    help="with --static: also score the geometric self-ensemble, the fp32 mean of the outputs under the "
+                         "first K of the 8 flips / transposes (2: + horizontal flip, 4: + vertical flips, 8: + transposes)")
     a = ap.parse_args(argv)
+    if a.self_ensemble != 1 and not a.static:
+        ap.error("--self-ensemble needs an exported static network (--static DIR)")
     import torch
     rm = importlib.import_module(PKG + ".imagenet_codebase.run_manager")
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
@@ -111,10 +116,15 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     print("loss %.5f  Y-PSNR %.3f dB  (%d images in %d forward calls, %.1f images/s)" % (loss, psnr, n_img, calls,
                                                                                        n_img / dt))
+    q = None
     if a.ssim:
         q = mgr.validate_quality(is_test=True, input_key=key, shave=a.shave)
         print("Y-SSIM %.4f  Y-PSNR %.3f dB  (exact luma, shave %d, scored on the GPU)" % (q["ssim"], q["psnr"], a.shave))
-        return q
+    if a.self_ensemble != 1:
+        q = mgr.validate_quality(is_test=True, input_key=key, shave=a.shave, self_ensemble=a.self_ensemble)
+        print("self-ensemble x%d: Y-SSIM %.4f  Y-PSNR %.3f dB  loss %.5f  (exact luma, shave %d, %d forward calls)"
+              % (a.self_ensemble, q["ssim"], q["psnr"], q["loss"], a.shave, q["calls"]))
+    return q
 
 
 if __name__ == "__main__":

@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 305 /* + ofasr_aug_gather_u8 */
+#define OFASR_VERSION 306 /* + ofasr_d4_apply, ofasr_d4_accumulate, ofasr_add */
 
 typedef enum {
     OFASR_OK = 0,
@@ -417,6 +417,31 @@ int ofasr_tile_gather_u8(const void* img, int64_t H, int64_t W, const int64_t* o
                          void* out, int dtype, void* stream);
 int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table, void* img,
                           int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Geometric self-ensemble: the 8 flips / transposes (the dihedral group D4) of an NCHW batch and the fp32 merge of the
+ * 8 network outputs, for upscale.py's TiledUpscaler(self_ensemble=k) and ops.self_ensemble (csrc/d4.hip; host statement:
+ * upscale.d4_transform / d4_inverse).  With b_i = bit i of t (0 <= t < 8), on the last two axes:
+ *   T_t(x) = transpose^{b2}(flip_H^{b1}(flip_W^{b0}(x)))      (flip_W reverses a row, flip_H the order of the rows)
+ *   apply:      src [N, C, H, W] of `dtype`; dst = T_t(src), the same dtype, [N, C, W, H] when t >= 4.  A permutation:
+ *               bit-exact.
+ *   accumulate: acc fp32 [N, C, H, W]; src of `dtype`, [N, C, H, W], or [N, C, W, H] when t >= 4:
+ *               acc[n,c,y,x] = ((first ? 0 : acc[n,c,y,x]) + (float)T_t^{-1}(src)[n,c,y,x]) * scale
+ *               (fp32 add, fp32 multiply).  An ensemble of k outputs is k calls, t = 0 .. k-1 in this order, `first` on
+ *               the first, scale = 1 on all but the last and 1 / k there: ((((v0 + v1) + v2) + ...) + v_{k-1}) / k.
+ * Any H, W >= 1 and any element-aligned base pointers (vector access only where width and pointers allow it); 64-bit
+ * addressing across planes, N * C not limited by the grid.  src and dst / acc must not overlap.  Plain loads and stores,
+ * no atomics: two calls give identical bits.  OFASR_ERR_UNSUPPORTED: (H + 64) * (W + 64) >= 2^31 or more than 2^40
+ * elements.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_d4_apply(const void* src, void* dst, int64_t N, int64_t C, int64_t H, int64_t W, int t, int dtype, void* stream);
+int ofasr_d4_accumulate(const void* src, float* acc, int64_t N, int64_t C, int64_t H, int64_t W, int t, int dtype, int first,
+                        float scale, void* stream);
+
+/* y = a + b over n elements of `dtype` (fp32 add, one RNE cast on store for the 16-bit types: the bits of ATen's a + b)
+ * -- the long skip connection of the static networks in an eval-mode forward (ops.skip_add).  y may be a or b; any
+ * element-aligned pointers (vector access only when all three are aligned for it); n <= 2^40. */
+int ofasr_add(const void* a, const void* b, void* y, int64_t n, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training augmentation on GPU-resident images: RandomCrop(S) -> RandomHorizontalFlip -> RandomRotation (nearest, same

@@ -127,7 +127,7 @@ class SRNetS4(_StaticSRNet):
             for i, conv in enumerate(self.dec_final_conv_blocks):
                 x = conv(x)
                 if i == 0:
-                    x = x + skip
+                    x = ops.skip_add(x, skip)
             for blk in self.blocks[self.n_mb:]:
                 x = blk(x)
             return self.dec_final_output_conv_block(x)
@@ -185,14 +185,14 @@ class SRNetX4(_StaticSRNet):
             for i, c in enumerate(self.enc_final_conv_blocks):
                 x = c(x)
                 if i == 0:
-                    x = x + skip
+                    x = ops.skip_add(x, skip)
             x = self.dec_first_conv_block(x)
             skip = x
             x = run_mb_blocks(x, list(self.blocks[u + e:u + e + d]))
             for i, c in enumerate(self.dec_final_conv_blocks):
                 x = c(x)
                 if i == 0:
-                    x = x + skip
+                    x = ops.skip_add(x, skip)
             for blk in self.blocks[u + e + d:]:
                 x = blk(x)
             return self.dec_final_output_conv_block(x)

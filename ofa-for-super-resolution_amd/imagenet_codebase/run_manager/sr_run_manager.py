@@ -362,15 +362,21 @@ class SRRunManager(object):
         return losses.avg, psnrs.avg, calls
 
     def validate_quality(self, net=None, data_loader=None, is_test=True, input_key="2x_down_image", max_batch=None,
-                         graphs=None, shave=0):
+                         graphs=None, shave=0, self_ensemble=1):
         """`validate_batched` (same size buckets, same forwards) scored on the GPU: Y-PSNR and Y-SSIM by the HIP metric
         kernel (ops.quality_y: exact integer luma, `shave` border pixels dropped) and the per-image MSE loss by
         ops.quality_mse, straight from the network's output.  No image goes to the host and no ATen kernel runs between
         the forwards and the ONE read-back of the per-image numbers at the end.  PSNR equals validate_batched's unless an
         image holds one of the 194 colours whose exact luma is a rounding tie (utils.y_exact).
+        `self_ensemble` = k in {2, 4, 8}: every bucket is scored on the fp32 mean of the network's outputs under the first
+        k flips / transposes (ops.self_ensemble); with graphs, the transformed inputs of all buckets run as one replay.
+        "calls" then counts k forwards per bucket.
         Returns {"loss", "psnr", "ssim", "calls"} (means over the images; "psnr_per_image" / "ssim_per_image" beside)."""
         if net is None:
             net = self.net
+        k = self_ensemble
+        if isinstance(k, bool) or k not in ops.ENSEMBLE_SIZES:
+            raise ValueError("self_ensemble must be one of %s, got %r" % (ops.ENSEMBLE_SIZES, k))
         if graphs is None:
             graphs = (os.environ.get("OFASR_EVAL_GRAPHS", "1") != "0" and str(self.device).startswith("cuda")
                       and self.mix_prec in ("bf16", "f16"))
@@ -382,8 +388,12 @@ class SRRunManager(object):
         for mini_batch in data_loader:
             mini_batch = device_batch(mini_batch, self.device)
             for i in range(mini_batch["image"].shape[0]):
-                items.append({k: v[i:i + 1] for k, v in mini_batch.items() if torch.is_tensor(v)})
+                items.append({k_: v[i:i + 1] for k_, v in mini_batch.items() if torch.is_tensor(v)})
         calls = 0
+
+        def eager(x):
+            with self.autocast():
+                return net(x)
         with torch.no_grad():
             groups = list(bucket_by_size(items, key=lambda it: it[input_key], max_batch=max_batch))
             lrs = [torch.cat([it[input_key] for it in group]).to(self.device) for group in groups]
@@ -391,14 +401,28 @@ class SRRunManager(object):
             # rows: sse (int64), the bits of ssim (fp64), the bits of the mse (fp64); one column per image
             res = torch.empty((3, len(items)), dtype=torch.int64, device=self.device)
             counts, at = [], 0
-            outs = fwd.call_many(lrs) if (fwd is not None and lrs) else None
+            if k > 1:
+                lrs = [x.contiguous() for x in lrs]
+            if fwd is not None and lrs:
+                # with the ensemble: T_t of every bucket, t = 0 .. k-1, in the one captured graph
+                outs = fwd.call_many([x if t == 0 else ops.d4_apply(x, t) for x in lrs for t in range(k)])
+            else:
+                outs = None
             for gi, group in enumerate(groups):
-                if outs is not None:
+                if k > 1 and outs is not None:
+                    output = None
+                    for t in range(k):
+                        y = outs[gi * k + t].contiguous()
+                        if output is None:
+                            output = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+                        ops.d4_accumulate(y, t, output, t == 0, 1.0 / k if t == k - 1 else 1.0)
+                elif k > 1:
+                    output = ops.self_ensemble(eager, lrs[gi], k)
+                elif outs is not None:
                     output = outs[gi]
                 else:
-                    with self.autocast():
-                        output = net(lrs[gi])
-                calls += 1
+                    output = eager(lrs[gi])
+                calls += k
                 n = len(group)
                 _, _, count = ops.quality_y(output, hrs[gi], shave, out=res[:2, at:at + n])
                 ops.quality_mse(output, hrs[gi], out=res[2, at:at + n].view(torch.float64))

@@ -295,6 +295,94 @@ def quality_mse(output, target, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------ geometric self-ensemble
+ENSEMBLE_SIZES = (1, 2, 4, 8)
+
+
+def _d4_operand(x, t, what):
+    _gpu(x)
+    if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 8:
+        raise ValueError("%s: the transform index must be an integer in 0..7, got %r" % (what, t))
+    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("%s needs a contiguous, non-empty NCHW tensor, got shape %s strides %s"
+                         % (what, tuple(x.shape), tuple(x.stride())))
+    return _dt(x)
+
+
+def d4_apply(x, t, out=None):
+    """T_t(x) of an NCHW f32 / f16 / bf16 batch: bit 0 of t flips W, bit 1 flips H, bit 2 transposes, in that order
+    (ofasr_d4_apply, csrc/d4.hip; the definition is upscale.d4_transform).  The result is [N, C, W, H] when t >= 4.
+    `out`: a contiguous tensor of that shape and x's dtype to write into (not x itself)."""
+    code = _d4_operand(x, t, "d4_apply")
+    N, C, H, W = x.shape
+    shape = (N, C, W, H) if t & 4 else (N, C, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    elif (tuple(out.shape) != shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous()
+          or out.data_ptr() == x.data_ptr()):
+        raise ValueError("d4_apply: out must be another contiguous %s %s tensor on %s" % (shape, x.dtype, x.device))
+    with _timed("d4_apply", 2 * x.numel() * x.element_size()):
+        _C.check(_C.lib().ofasr_d4_apply(_p(x), _p(out), N, C, H, W, t, code, _stream()), "ofasr_d4_apply")
+    return out
+
+
+def d4_accumulate(y, t, acc, first, scale):
+    """acc = ((0 if first else acc) + float(T_t^{-1}(y))) * scale, in place (ofasr_d4_accumulate): acc is a contiguous fp32
+    [N, C, H, W] GPU tensor, y an f32 / f16 / bf16 tensor of that shape ([N, C, W, H] when t >= 4).  One call per
+    ensemble member, in the order t = 0 .. k-1, scale = 1 on all but the last; returns acc."""
+    code = _d4_operand(y, t, "d4_accumulate")
+    _gpu(acc)
+    if acc.dtype != torch.float32 or acc.dim() != 4 or not acc.is_contiguous() or acc.device != y.device:
+        raise ValueError("d4_accumulate: acc must be a contiguous fp32 NCHW tensor on %s" % y.device)
+    N, C, H, W = acc.shape
+    if tuple(y.shape) != ((N, C, W, H) if t & 4 else (N, C, H, W)):
+        raise ValueError("d4_accumulate: the output of transform %d has shape %s, the accumulator %s"
+                         % (t, tuple(y.shape), tuple(acc.shape)))
+    with _timed("d4_accumulate", y.numel() * (y.element_size() + (4 if first else 8))):
+        _C.check(_C.lib().ofasr_d4_accumulate(_p(y), _p(acc), N, C, H, W, t, code, 1 if first else 0, float(scale),
+                                              _stream()), "ofasr_d4_accumulate")
+    return acc
+
+
+def self_ensemble(fn, x, k, out=None):
+    """geometric self-ensemble of `fn` (a network forward, NCHW -> NCHW) over the first k of the 8 flips / transposes:
+        (1 / k) * ((((v_0 + v_1) + v_2) + ...) + v_{k-1}),   v_t = float32(T_t^{-1}(fn(T_t(x))))
+    k in {1, 2, 4, 8}: the identity, + the horizontal flip, + the vertical flips, + the transposes.  Every output is merged
+    into the one fp32 result before the next forward runs (fn may return the same buffer each time, as a replayed graph
+    does), so no k-fold tensor exists; the transforms and the merge are HIP kernels (d4_apply / d4_accumulate), the adds
+    fp32 in exactly this order.  Returns the fp32 mean (written into `out` when given)."""
+    if isinstance(k, bool) or k not in ENSEMBLE_SIZES:
+        raise ValueError("self-ensemble size must be one of %s, got %r" % (ENSEMBLE_SIZES, k))
+    _d4_operand(x, 0, "self_ensemble")
+    acc = out
+    bufs = {}
+    for t in range(k):
+        if t == 0:
+            xt = x
+        else:
+            xt = bufs[t & 4] = d4_apply(x, t, out=bufs.get(t & 4))
+        y = fn(xt)
+        if not y.is_contiguous():
+            y = y.contiguous()
+        if t == 0 and acc is None:
+            acc = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+        d4_accumulate(y, t, acc, t == 0, 1.0 / k if t == k - 1 else 1.0)
+    return acc
+
+
+def skip_add(x, skip):
+    """x + skip, the long skip connection of the static SR networks.  In an inference forward (no gradients, two
+    contiguous GPU tensors of one shape and f32 / f16 / bf16 dtype) the sum is one HIP kernel (ofasr_add, the same bits as
+    ATen's add); with gradients it stays the autograd add."""
+    if (torch.is_grad_enabled() or not x.is_cuda or not skip.is_cuda or x.dtype != skip.dtype or x.dtype not in _DT
+            or x.shape != skip.shape or not x.is_contiguous() or not skip.is_contiguous() or x.numel() == 0):
+        return x + skip
+    y = torch.empty_like(x)
+    with _timed("skip_add", 3 * x.numel() * x.element_size()):
+        _C.check(_C.lib().ofasr_add(_p(x), _p(skip), _p(y), x.numel(), _dt(x), _stream()), "ofasr_add")
+    return y
+
+
 # --------------------------------------------------------------------------- kernel transform
 def _kt_args(chain, mats):
     ks = (ctypes.c_int * len(chain))(*chain)

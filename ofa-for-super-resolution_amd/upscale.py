@@ -15,6 +15,12 @@ each core is given a halo of `receptive_radius(config)` input pixels, and the eq
 The 8-bit image <-> tile batch moves are the HIP kernels ofasr_tile_gather_u8 / ofasr_tile_scatter_u8 (csrc/tile_io.hip:
 ToTensor's / 255 and tensor2img_np's clamp * 255 round, one launch per batch); the network runs on its own HIP kernels,
 replayed from one captured graph per window shape (graphed.GraphedEval).
+
+Geometric self-ensemble (`self_ensemble=k`, the "+" of EDSR+ / RCAN+): every batch of windows is run under the first k of
+the 8 flips / transposes T_t and the outputs, mapped back, are averaged in fp32 (ops.self_ensemble: csrc/d4.hip).  Tiling
+stays exact: T_t of a window that was shifted into the image is the window of T_t(image) at the transformed place, so every
+outer window edge is still an image edge or at least `halo` from the core, and the tiled ensemble equals the ensemble of
+the whole image.  d4_transform / d4_inverse below are the host definition of T_t.
 """
 import math
 from fractions import Fraction
@@ -156,11 +162,12 @@ def _axis(L, core, halo, align, mult):
     return win, out
 
 
-def plan_windows(H, W, core, halo, align=1, scale=4, px_elems=None):
+def plan_windows(H, W, core, halo, align=1, scale=4, px_elems=None, height8=False):
     """the tile plan of an H x W input: cores of at most core x core input pixels that tile the image exactly once, each in
     a window of the core plus `halo` on every side, shifted into the image (never padded).  Window sides are multiples
     of `align` (input sides must be, too) and, where the image is wide enough, widths are multiples of 8.  `px_elems` is
-    activation_elems_per_pixel(config): it bounds the batch."""
+    activation_elems_per_pixel(config): it bounds the batch.  `height8`: heights are multiples of 8 too, where the image is
+    tall enough (the 8-fold self-ensemble runs the transposed windows as well)."""
     H, W, core, halo, align = int(H), int(W), int(core), int(halo), int(align)
     if H <= 0 or W <= 0:
         raise ValueError("empty image %dx%d" % (H, W))
@@ -171,8 +178,9 @@ def plan_windows(H, W, core, halo, align=1, scale=4, px_elems=None):
         raise ValueError("core %d is smaller than the alignment %d" % (core, align))
     core = core // align * align
     halo = _up(max(halo, 0), align)
-    win_h, rows = _axis(H, core, halo, align, align)
-    win_w, cols = _axis(W, core, halo, align, align * 8 // math.gcd(align, 8))
+    m8 = align * 8 // math.gcd(align, 8)
+    win_h, rows = _axis(H, core, halo, align, m8 if height8 else align)
+    win_w, cols = _axis(W, core, halo, align, m8)
     windows = [(wy, wx, cy, cx, ch, cw) for (wy, cy, ch) in rows for (wx, cx, cw) in cols]
     px = px_elems if px_elems is not None else max(384, 64 * scale * scale, 3 * scale * scale)
     batch = max(1, min(MAX_WINDOWS, (LIMIT - 1) // (px * win_h * win_w)))
@@ -224,6 +232,38 @@ def tile_scatter(src, table, img, max_eh, max_ew):
     return img
 
 
+# ---------------------------------------------------------------------------------------------- self-ensemble
+def _d4_index(t):
+    if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 8:
+        raise ValueError("the transform index must be an integer in 0..7, got %r" % (t,))
+    return t
+
+
+def d4_transform(x, t):
+    """T_t(x) on the last two axes: bit 0 of t flips W, bit 1 flips H, bit 2 transposes, applied in that order.  Pure torch:
+    the definition the HIP kernels (ops.d4_apply / ops.d4_accumulate) are tested against."""
+    t = _d4_index(t)
+    if t & 1:
+        x = x.flip(-1)
+    if t & 2:
+        x = x.flip(-2)
+    if t & 4:
+        x = x.transpose(-1, -2)
+    return x.contiguous()
+
+
+def d4_inverse(x, t):
+    """T_t^{-1}(x): the steps of d4_transform undone in reverse order"""
+    t = _d4_index(t)
+    if t & 4:
+        x = x.transpose(-1, -2)
+    if t & 2:
+        x = x.flip(-2)
+    if t & 1:
+        x = x.flip(-1)
+    return x.contiguous()
+
+
 # ---------------------------------------------------------------------------------------------- upscaler
 class TiledUpscaler(object):
     """Tiled inference of a static SR network (SRNetS4 / SRNetX4 on the GPU; put into eval mode here).
@@ -232,11 +272,17 @@ class TiledUpscaler(object):
     GPU.  Per batch of windows: gather (HIP), the network (replayed from one captured graph per window shape when
     `graphed`; the last batch is padded by repeating a window), scatter of the cores (HIP).  `core` = None: the largest
     core that keeps every fp32 activation of a window below 2^31 bytes; `batch` = None: as many windows per batch as
-    keep every batched tensor below 2^31 elements, spread evenly over the batches."""
+    keep every batched tensor below 2^31 elements, spread evenly over the batches.  `self_ensemble` = k in {1, 2, 4, 8}:
+    every batch runs under the first k flips / transposes and the fp32 mean of the mapped-back outputs is what is
+    scattered (ops.self_ensemble); k = 8 plans window heights as multiples of 8 as well and replays two graphs, one per
+    window orientation."""
 
-    def __init__(self, net, core=None, batch=None, mix_prec="f32", graphed=True):
+    def __init__(self, net, core=None, batch=None, mix_prec="f32", graphed=True, self_ensemble=1):
         if mix_prec not in _DTYPES:
             raise ValueError("mix_prec must be one of %s" % sorted(_DTYPES))
+        if isinstance(self_ensemble, bool) or self_ensemble not in ops.ENSEMBLE_SIZES:
+            raise ValueError("self_ensemble must be one of %s, got %r" % (ops.ENSEMBLE_SIZES, self_ensemble))
+        self.self_ensemble = int(self_ensemble)
         self.net = net.eval()
         self.config = net.config
         self.scale = int(self.config["upscale"])
@@ -253,7 +299,8 @@ class TiledUpscaler(object):
         self.graphed = GraphedEval(net, autocast_dtype=self.autocast_dtype, copy_output=False) if graphed else None
 
     def plan(self, H, W):
-        return plan_windows(H, W, self.core, self.halo, self.align, self.scale, self.px_elems)
+        return plan_windows(H, W, self.core, self.halo, self.align, self.scale, self.px_elems,
+                            height8=self.self_ensemble == 8)
 
     def _whole_plan(self, H, W):
         if H % self.align or W % self.align:
@@ -296,7 +343,10 @@ class TiledUpscaler(object):
         with torch.no_grad():
             for b in range(nb):
                 x = tile_gather(img, origins[b * B:(b + 1) * B], plan.win_h, plan.win_w, self.dtype)
-                y = self._forward(x)
+                if self.self_ensemble == 1:
+                    y = self._forward(x)
+                else:
+                    y = ops.self_ensemble(self._forward, x, self.self_ensemble)
                 real = min(B, n - b * B)
                 sink(y, real, table[b * B:b * B + real], plan.windows[b * B:b * B + real], plan)
         return plan

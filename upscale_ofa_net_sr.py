@@ -35,6 +35,9 @@ def parse_args(argv=None):
                     help="core tile side in input pixels (default: the largest that keeps every activation < 2 GiB)")
     ap.add_argument("--batch", type=int, default=None, help="windows per forward call (default: as many as fit)")
     ap.add_argument("--whole", action="store_true", help="run each image as one forward call (small images only)")
+    ap.add_argument("--self-ensemble", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
+                    help="geometric self-ensemble: average the outputs under the first K of the 8 flips / transposes "
+                         "(K times the network time; 2: + horizontal flip, 4: + vertical flips, 8: + transposes)")
     ap.add_argument("--reference", default=None, metavar="PATH",
                     help="directory of ground-truth HR images named as the inputs: report Y-PSNR / Y-SSIM per image")
     ap.add_argument("--shave", type=int, default=0, help="with --reference: border pixels left out of the metric")
@@ -100,10 +103,11 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("upscaling runs on the GPU")
     net = evals.load_static(a.static).cuda()
-    up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec)
+    up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble)
     os.makedirs(a.out, exist_ok=True)
-    print("%s x%d: receptive radius %d px, halo %d, core %d, %s" % (net.name(), up.scale, up.radius, up.halo, up.core,
-                                                                  a.mix_prec))
+    print("%s x%d: receptive radius %d px, halo %d, core %d, %s%s" % (
+        net.name(), up.scale, up.radius, up.halo, up.core, a.mix_prec,
+        "" if a.self_ensemble == 1 else ", self-ensemble x%d" % a.self_ensemble))
     taken = set()
     mpix = 0.0
     saves = []
@@ -154,7 +158,7 @@ def main(argv=None):
         mean = {"psnr": sum(x["psnr"] for x in recs) / len(recs), "ssim": sum(x["ssim"] for x in recs) / len(recs)}
         print("mean of %d images: Y-PSNR %.3f dB  Y-SSIM %.4f  (shave %d)" % (len(recs), mean["psnr"], mean["ssim"], a.shave))
         with open(os.path.join(a.out, "quality.json"), "w") as fh:
-            json.dump({"shave": a.shave, "images": recs, "mean": mean}, fh, indent=1)
+            json.dump({"shave": a.shave, "self_ensemble": a.self_ensemble, "images": recs, "mean": mean}, fh, indent=1)
     print("%d images, %.2f output MP in %.3f s: %.2f MP/s (%.2f MP/s with PNG encoding)" % (
         len(files), mpix, dt, mpix / dt, mpix / dt_all))
 
