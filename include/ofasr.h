@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 306 /* + ofasr_d4_apply, ofasr_d4_accumulate, ofasr_add */
+#define OFASR_VERSION 307 /* + ofasr_yuv420_to_rgb_u8, ofasr_rgb_to_yuv420_u8, ofasr_tile_gather_yuv420, ofasr_tile_scatter_yuv420 */
 
 typedef enum {
     OFASR_OK = 0,
@@ -417,6 +417,53 @@ int ofasr_tile_gather_u8(const void* img, int64_t H, int64_t W, const int64_t* o
                          void* out, int dtype, void* stream);
 int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table, void* img,
                           int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Planar 8-bit YUV 4:2:0 frames (csrc/yuv.hip; host statement: video.py yuv420_to_rgb_host / rgb_to_yuv420_host) -- the
+ * colour conversions of the video path, whole-frame and fused into the two tile moves above, so that an upscale of a
+ * video frame holds planar YUV only.  A frame is three contiguous uint8 planes: y [H, W], u and v [H/2, W/2]; H and W
+ * even, >= 2.  All arithmetic is int32 on 14-bit coefficients that the caller passes as a HOST table (read during the
+ * call and handed to the kernel by value; video.yuv_coeffs makes them for bt601 / bt709, limited / full range):
+ *   decode table int32[6]  = yo, cy, rv, gu, gv, bu
+ *   encode table int32[10] = yo, yr, yg, yb, ur, ug, ub, vr, vg, vb
+ * With >> the arithmetic (floor) shift and clamp to 0 .. 255:
+ *   decode: chroma to full resolution by the centre-sited 9-3-3-1 filter with edge replication at the FRAME edge:
+ *             cy0 = y >> 1, ny = (y even ? cy0 - 1 : cy0 + 1) clamped to 0 .. H/2 - 1; cx0, nx alike from x;
+ *             c = (9 C[cy0,cx0] + 3 C[cy0,nx] + 3 C[ny,cx0] + C[ny,nx] + 8) >> 4       for C = U and C = V
+ *           and with y' = Y - yo, u = c_U - 128, v = c_V - 128:
+ *             R = clamp((cy y' + rv v + 2^13) >> 14)
+ *             G = clamp((cy y' + gu u + gv v + 2^13) >> 14)
+ *             B = clamp((cy y' + bu u + 2^13) >> 14)
+ *   encode:   Y = clamp(((yr R + yg G + yb B + 2^13) >> 14) + yo)                        per pixel
+ *             U = clamp(((sum over the 2x2 block of (ur R + ug G + ub B) + 2^15) >> 16) + 128),   V alike from vr, vg, vb
+ *   ofasr_yuv420_to_rgb_u8 / ofasr_rgb_to_yuv420_u8: the whole frame, rgb_hwc a HWC uint8 image [H, W, 3].  Any
+ *     byte-aligned pointers (wide access only where an address is aligned for it and the 4-pixel group is whole).
+ *   ofasr_tile_gather_yuv420: as ofasr_tile_gather_u8 on the decoded frame, without the frame:
+ *             out[n,c,r,x] = (dtype)(RGB_c(y0+r, x0+x) / 255.0f)
+ *     with RGB the decode at FRAME coordinates (chroma neighbours come from the frame; the replication is at the frame
+ *     edge, never at a window edge).  origins as there (clamped to 0 <= y0 <= H - h, 0 <= x0 <= W - w); odd origins and
+ *     odd h, w are fine.  Bit-equal to ofasr_tile_gather_u8 of ofasr_yuv420_to_rgb_u8's output.
+ *   ofasr_tile_scatter_yuv420: as ofasr_tile_scatter_u8 followed by the encode: the source values are quantised as there
+ *     (round_half_even(clamp(v, 0, 1) * 255) in fp32) and every 2x2 block of an extent is encoded into y / u / v
+ *     [OH, OW], [OH/2, OW/2].  table rows (sy, sx, dy, dx, eh, ew) are clamped as there, then dy, dx, eh, ew have their
+ *     low bit cleared, so that a chroma sample always belongs to one extent as a whole: with even table entries (an even
+ *     upscale factor) the result equals ofasr_rgb_to_yuv420_u8 of ofasr_tile_scatter_u8's image on the extents.  Bytes
+ *     outside every extent are not written; extents of different windows must not overlap.
+ * Plain loads and stores, no atomics: two calls give identical bytes.  Every access stays inside its tensor whatever
+ * the device tables hold.  64-bit addressing.  OFASR_ERR_INVALID_ARG: a null pointer, an odd or non-positive side, a
+ * window larger than the frame, an extent bound larger than the source window, a bad dtype, a table whose yo is outside
+ * 0 .. 255 or whose coefficients exceed 2^16 in magnitude (beyond it int32 could overflow).  OFASR_ERR_UNSUPPORTED:
+ * n > 65535 or more than 2^40 pixels.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_yuv420_to_rgb_u8(const void* y, const void* u, const void* v, int64_t H, int64_t W, const int32_t* coeffs,
+                           void* rgb_hwc, void* stream);
+int ofasr_rgb_to_yuv420_u8(const void* rgb_hwc, int64_t H, int64_t W, const int32_t* coeffs, void* y, void* u, void* v,
+                           void* stream);
+int ofasr_tile_gather_yuv420(const void* y, const void* u, const void* v, int64_t H, int64_t W, const int32_t* coeffs,
+                             const int64_t* origins, int64_t n, int64_t h, int64_t w, void* out, int dtype, void* stream);
+int ofasr_tile_scatter_yuv420(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
+                              const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW, int64_t max_eh,
+                              int64_t max_ew, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Geometric self-ensemble: the 8 flips / transposes (the dihedral group D4) of an NCHW batch and the fp32 merge of the

@@ -122,6 +122,12 @@ SIGNATURES = {
     "ofasr_tile_gather_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_int, _c_vp]),
     "ofasr_tile_scatter_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64,
                                        _c_vp]),
+    "ofasr_yuv420_to_rgb_u8": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "ofasr_rgb_to_yuv420_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "ofasr_tile_gather_yuv420": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp,
+                                          _c_int, _c_vp]),
+    "ofasr_tile_scatter_yuv420": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64,
+                                           _c_i64, _c_i64, _c_i64, _c_vp]),
     "ofasr_d4_apply": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp]),
     "ofasr_d4_accumulate": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, ctypes.c_float,
                                      _c_vp]),

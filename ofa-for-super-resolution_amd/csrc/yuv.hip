@@ -1,0 +1,455 @@
+// yuv.hip -- planar 8-bit YUV 4:2:0 frames: the whole-frame colour conversions (ofasr_yuv420_to_rgb_u8 /
+// ofasr_rgb_to_yuv420_u8) and the tile moves of tiled inference with the conversion fused in
+// (ofasr_tile_gather_yuv420 / ofasr_tile_scatter_yuv420).  The host statement is video.py (yuv420_to_rgb_host /
+// rgb_to_yuv420_host); everything is integer arithmetic on 14-bit coefficients, so host and device agree bit for bit:
+//   decode: chroma to full resolution by the centre-sited 9-3-3-1 filter, edge replication at the FRAME edge:
+//             c = (9 C[cy0, cx0] + 3 C[cy0, nx] + 3 C[ny, cx0] + C[ny, nx] + 8) >> 4,   cy0 = y >> 1, cx0 = x >> 1,
+//             ny = cy0 - 1 for even y, cy0 + 1 for odd y (nx alike from x), both clamped into the plane;
+//           R = clamp((cy y' + rv v + 2^13) >> 14), G = clamp((cy y' + gu u + gv v + 2^13) >> 14),
+//           B = clamp((cy y' + bu u + 2^13) >> 14)   with y' = Y - yo, u = c_U - 128, v = c_V - 128
+//   encode: Y = clamp(((yr R + yg G + yb B + 2^13) >> 14) + yo) per pixel;
+//           U = clamp(((sum over the 2x2 block of (ur R + ug G + ub B) + 2^15) >> 16) + 128), V alike
+// The tile moves are the ones of tile_io.hip with these in front / behind:
+//   gather:  out[n, c, r, x] = (T)(RGB_c(y0_n + r, x0_n + x) / 255.0f), RGB the decode at frame coordinates
+//   scatter: the 2x2 blocks of tio_quant(src) (clamp, * 255 in fp32, rintf) encoded into the three planes
+// so no RGB frame exists on either side of the network.  Addressing is 64-bit throughout.  Every access stays inside its
+// tensor whatever the device tables hold: origins, offsets and extents are clamped in the kernels.
+//
+// Access widths.  A lane owns a 2-row x 4-column pixel block whose corner is even in both frame coordinates, i.e. two
+// whole chroma samples per plane: a decode fetches the 3 x 4 chroma neighbourhood of the block once per plane (byte loads
+// at clamped indices) and the two luma rows as dwords; an encode writes two luma dwords and one 16-bit chroma pair per
+// plane.  The wide accesses are taken only where the address is aligned for them and the block is whole; blocks cut by
+// the frame's or an extent's edge and unaligned rows go byte by byte (element by element on the tile side).  A window
+// with an odd origin is gathered as the even-aligned superset of the window, the pixels outside it masked.
+#include "ofasr_common.h"
+
+namespace ofasr {
+
+struct YuvDec { int yo, cy, rv, gu, gv, bu; };
+struct YuvEnc { int yo, yr, yg, yb, ur, ug, ub, vr, vg, vb; };
+
+__device__ __forceinline__ int yuv_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+__device__ __forceinline__ long long yuv_clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// RGB of the 2 x 4 block whose corner is the even frame position (by, bx): rgb[row][col][c].  Columns at or past W
+// repeat column W - 1 (the caller masks them); by + 1 < H since H is even.
+__device__ __forceinline__ void yuv_decode_block(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
+                                                 const uint8_t* __restrict__ vp, long long H, long long W, long long by,
+                                                 long long bx, const YuvDec& D, int (&rgb)[2][4][3]) {
+    const long long CH = H >> 1, CW = W >> 1;
+    const long long cy = by >> 1, cx = bx >> 1;
+    long long rows[3], cols[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) rows[i] = yuv_clampll(cy - 1 + i, 0, CH - 1) * CW;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cols[j] = yuv_clampll(cx - 1 + j, 0, CW - 1);
+    int cu[3][4], cv[3][4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cu[i][j] = up[rows[i] + cols[j]];
+            cv[i][j] = vp[rows[i] + cols[j]];
+        }
+    int Y[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint8_t* p = yp + (by + r) * W + bx;
+        if ((reinterpret_cast<uintptr_t>(p) & 3) == 0 && bx + 4 <= W) {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) Y[r][k] = (int)((w >> (8 * k)) & 0xffu);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) Y[r][k] = p[bx + k < W ? k : (int)(W - 1 - bx)];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int nr = r == 0 ? 0 : 2;                   // the other chroma row: above for the even row, below for the odd
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c0 = 1 + (k >> 1);
+            const int nc = (k & 1) ? c0 + 1 : c0 - 1;    // left for the even column, right for the odd
+            const int u = ((9 * cu[1][c0] + 3 * cu[1][nc] + 3 * cu[nr][c0] + cu[nr][nc] + 8) >> 4) - 128;
+            const int v = ((9 * cv[1][c0] + 3 * cv[1][nc] + 3 * cv[nr][c0] + cv[nr][nc] + 8) >> 4) - 128;
+            const int l = D.cy * (Y[r][k] - D.yo) + (1 << 13);
+            rgb[r][k][0] = yuv_clamp8((l + D.rv * v) >> 14);
+            rgb[r][k][1] = yuv_clamp8((l + D.gu * u + D.gv * v) >> 14);
+            rgb[r][k][2] = yuv_clamp8((l + D.bu * u) >> 14);
+        }
+    }
+}
+
+// luma of the 2 x 4 block rgb (columns < valid, valid = 2 or 4) and its one or two chroma pairs
+__device__ __forceinline__ void yuv_encode_block(const int (&rgb)[2][4][3], const YuvEnc& E, int (&Y)[2][4], int (&U)[2],
+                                                 int (&V)[2]) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            Y[r][k] = yuv_clamp8(((E.yr * rgb[r][k][0] + E.yg * rgb[r][k][1] + E.yb * rgb[r][k][2] + (1 << 13)) >> 14) + E.yo);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        int su = 0, sv = 0;
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 2 * j; k < 2 * j + 2; ++k) {
+                su += E.ur * rgb[r][k][0] + E.ug * rgb[r][k][1] + E.ub * rgb[r][k][2];
+                sv += E.vr * rgb[r][k][0] + E.vg * rgb[r][k][1] + E.vb * rgb[r][k][2];
+            }
+        U[j] = yuv_clamp8(((su + (1 << 15)) >> 16) + 128);
+        V[j] = yuv_clamp8(((sv + (1 << 15)) >> 16) + 128);
+    }
+}
+
+// the planes' bytes of one encoded block at the even position (by, bx) of an [OH, OW] frame; valid = 2 or 4 columns
+__device__ __forceinline__ void yuv_store_block(uint8_t* __restrict__ yp, uint8_t* __restrict__ up, uint8_t* __restrict__ vp,
+                                                long long OW, long long by, long long bx, int valid, const int (&Y)[2][4],
+                                                const int (&U)[2], const int (&V)[2]) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        uint8_t* p = yp + (by + r) * OW + bx;
+        if ((reinterpret_cast<uintptr_t>(p) & 3) == 0 && valid == 4) {
+            *reinterpret_cast<uint32_t*>(p) = (uint32_t)Y[r][0] | (uint32_t)Y[r][1] << 8 | (uint32_t)Y[r][2] << 16 |
+                                              (uint32_t)Y[r][3] << 24;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < valid) p[k] = (uint8_t)Y[r][k];
+        }
+    }
+    const long long co = (by >> 1) * (OW >> 1) + (bx >> 1);
+    uint8_t* pu = up + co;
+    uint8_t* pv = vp + co;
+    if ((reinterpret_cast<uintptr_t>(pu) & 1) == 0 && valid == 4) *reinterpret_cast<uint16_t*>(pu) = (uint16_t)(U[0] | U[1] << 8);
+    else {
+        pu[0] = (uint8_t)U[0];
+        if (valid == 4) pu[1] = (uint8_t)U[1];
+    }
+    if ((reinterpret_cast<uintptr_t>(pv) & 1) == 0 && valid == 4) *reinterpret_cast<uint16_t*>(pv) = (uint16_t)(V[0] | V[1] << 8);
+    else {
+        pv[0] = (uint8_t)V[0];
+        if (valid == 4) pv[1] = (uint8_t)V[1];
+    }
+}
+
+// ---- whole frame ---------------------------------------------------------------------------------------------------
+// grid: lanes over (H / 2) * ceil(W / 4) blocks in a grid-stride loop
+__global__ void __launch_bounds__(256) yuv420_to_rgb_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
+                                                            const uint8_t* __restrict__ vp, long long H, long long W, YuvDec D,
+                                                            uint8_t* __restrict__ rgb_out) {
+    const long long G = (W + 3) >> 2;
+    const long long total = (H >> 1) * G;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        const long long br = e / G;
+        const long long by = br * 2, bx = (e - br * G) * 4;
+        int rgb[2][4][3];
+        yuv_decode_block(yp, up, vp, H, W, by, bx, D, rgb);
+        const int valid = bx + 4 <= W ? 4 : 2;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            uint8_t* d = rgb_out + ((by + r) * W + bx) * 3;
+            if ((reinterpret_cast<uintptr_t>(d) & 3) == 0 && valid == 4) {
+                uint32_t b[12];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) b[3 * k + c] = (uint32_t)rgb[r][k][c];
+                uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) d4[q] = b[4 * q] | b[4 * q + 1] << 8 | b[4 * q + 2] << 16 | b[4 * q + 3] << 24;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < valid) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) d[3 * k + c] = (uint8_t)rgb[r][k][c];
+                    }
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) rgb_to_yuv420_kernel(const uint8_t* __restrict__ rgb_in, long long H, long long W,
+                                                            YuvEnc E, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
+                                                            uint8_t* __restrict__ vp) {
+    const long long G = (W + 3) >> 2;
+    const long long total = (H >> 1) * G;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        const long long br = e / G;
+        const long long by = br * 2, bx = (e - br * G) * 4;
+        const int valid = bx + 4 <= W ? 4 : 2;
+        int rgb[2][4][3];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const uint8_t* s = rgb_in + ((by + r) * W + bx) * 3;
+            if ((reinterpret_cast<uintptr_t>(s) & 3) == 0 && valid == 4) {
+                const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+                const uint32_t w[3] = {s4[0], s4[1], s4[2]};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const int i = 3 * k + c;
+                        rgb[r][k][c] = (int)((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
+                    }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) rgb[r][k][c] = k < valid ? (int)s[3 * k + c] : 0;
+            }
+        }
+        int Y[2][4], U[2], V[2];
+        yuv_encode_block(rgb, E, Y, U, V);
+        yuv_store_block(yp, up, vp, W, by, bx, valid, Y, U, V);
+    }
+}
+
+// ---- tiles ---------------------------------------------------------------------------------------------------------
+template <typename T> struct yuv_vec4;
+template <> struct yuv_vec4<float> { typedef float4 type; };
+template <> struct yuv_vec4<bf16_t> { typedef uint2 type; };
+template <> struct yuv_vec4<f16_t> { typedef uint2 type; };
+
+template <typename T> __device__ __forceinline__ typename yuv_vec4<T>::type yuv_pack4(const float* v);
+template <> __device__ __forceinline__ float4 yuv_pack4<float>(const float* v) { return make_float4(v[0], v[1], v[2], v[3]); }
+template <> __device__ __forceinline__ uint2 yuv_pack4<bf16_t>(const float* v) {
+    return make_uint2(pack2<bf16_t>(v[0], v[1]), pack2<bf16_t>(v[2], v[3]));
+}
+template <> __device__ __forceinline__ uint2 yuv_pack4<f16_t>(const float* v) {
+    return make_uint2(pack2<f16_t>(v[0], v[1]), pack2<f16_t>(v[2], v[3]));
+}
+template <typename T> __device__ __forceinline__ void yuv_unpack4(typename yuv_vec4<T>::type p, float* v);
+template <> __device__ __forceinline__ void yuv_unpack4<float>(float4 p, float* v) {
+    v[0] = p.x, v[1] = p.y, v[2] = p.z, v[3] = p.w;
+}
+template <> __device__ __forceinline__ void yuv_unpack4<bf16_t>(uint2 p, float* v) {
+    unpack2<bf16_t>(p.x, v[0], v[1]);
+    unpack2<bf16_t>(p.y, v[2], v[3]);
+}
+template <> __device__ __forceinline__ void yuv_unpack4<f16_t>(uint2 p, float* v) {
+    unpack2<f16_t>(p.x, v[0], v[1]);
+    unpack2<f16_t>(p.y, v[2], v[3]);
+}
+
+// grid: (x: lanes over (h / 2 + 1) * (w / 4 + 1) blocks of the even-aligned superset of the window, y: window).
+// vec_ok: w % 4 == 0 and `out` aligned for 4-element stores (then a window with an even x0 stores whole rows of a block)
+template <typename T>
+__global__ void __launch_bounds__(256) tile_gather_yuv420_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
+                                                                 const uint8_t* __restrict__ vp, long long H, long long W,
+                                                                 YuvDec D, const long long* __restrict__ origins, long long h,
+                                                                 long long w, T* __restrict__ out, int vec_ok) {
+    const long long n = blockIdx.y;
+    const long long y0 = yuv_clampll(origins[2 * n], 0, H - h), x0 = yuv_clampll(origins[2 * n + 1], 0, W - w);
+    const long long ey0 = y0 & ~1LL, ex0 = x0 & ~1LL;
+    const long long G = (w >> 2) + 1;                 // ceil((w + 1) / 4) <= w / 4 + 1 columns of blocks
+    const long long R = (h >> 1) + 1;
+    const long long plane = h * w;
+    T* on = out + n * 3 * plane;
+    const bool vec = vec_ok && x0 == ex0;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < R * G; e += (long long)gridDim.x * blockDim.x) {
+        const long long br = e / G;
+        const long long by = ey0 + br * 2, bx = ex0 + (e - br * G) * 4;
+        if (by >= y0 + h || bx >= x0 + w) continue;
+        int rgb[2][4][3];
+        yuv_decode_block(yp, up, vp, H, W, by, bx, D, rgb);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const long long wr = by + r - y0;           // window row
+            if (wr < 0 || wr >= h) continue;
+            const long long wx = bx - x0;               // window column of the block's first pixel (-1 for an odd x0)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = __fdiv_rn((float)rgb[r][k][c], 255.0f);
+                T* dst = on + c * plane + wr * w + wx;
+                if (vec) {                              // x0 even and w % 4 == 0: wx % 4 == 0 and the block is whole
+                    *reinterpret_cast<typename yuv_vec4<T>::type*>(dst) = yuv_pack4<T>(v);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (wx + k >= 0 && wx + k < w) dst[k] = from_float<T>(v[k]);
+                }
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ int yuv_quant(float v) {
+    const float f = fminf(fmaxf(v, 0.0f), 1.0f);
+    return (int)rintf(__fmul_rn(f, 255.0f));
+}
+
+// table[6 n ..]: sy, sx, dy, dx, eh, ew (dy, dx, eh, ew made even after the clamps).
+// grid: (x: lanes over ceil(max_eh / 2) * ceil(max_ew / 4) blocks, y: window)
+template <typename T>
+__global__ void __launch_bounds__(256) tile_scatter_yuv420_kernel(const T* __restrict__ src, long long sh_, long long sw,
+                                                                  const long long* __restrict__ table, YuvEnc E,
+                                                                  uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
+                                                                  uint8_t* __restrict__ vp, long long OH, long long OW,
+                                                                  long long max_eh, long long max_ew) {
+    const long long n = blockIdx.y;
+    const long long* t = table + 6 * n;
+    long long sy = t[0], sx = t[1], dy = t[2], dx = t[3], eh = t[4], ew = t[5];
+    sy = sy < 0 ? 0 : (sy > sh_ ? sh_ : sy);
+    sx = sx < 0 ? 0 : (sx > sw ? sw : sx);
+    dy = dy < 0 ? 0 : (dy > OH ? OH : dy);
+    dx = dx < 0 ? 0 : (dx > OW ? OW : dx);
+    eh = eh < 0 ? 0 : eh;
+    ew = ew < 0 ? 0 : ew;
+    eh = eh > max_eh ? max_eh : eh;
+    ew = ew > max_ew ? max_ew : ew;
+    eh = eh > sh_ - sy ? sh_ - sy : eh;
+    eh = eh > OH - dy ? OH - dy : eh;
+    ew = ew > sw - sx ? sw - sx : ew;
+    ew = ew > OW - dx ? OW - dx : ew;
+    dy &= ~1LL, dx &= ~1LL, eh &= ~1LL, ew &= ~1LL;      // whole 2 x 2 blocks only: no chroma sample is half-owned
+    const long long G = (max_ew + 3) >> 2;
+    const long long plane = sh_ * sw;
+    const T* sn = src + n * 3 * plane;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < (eh >> 1) * G; e += (long long)gridDim.x * blockDim.x) {
+        const long long br = e / G;
+        const long long r0 = br * 2, c0 = (e - br * G) * 4;   // the block inside the extent
+        if (c0 >= ew) continue;
+        const int valid = c0 + 4 <= ew ? 4 : 2;
+        int rgb[2][4][3];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const T* s = sn + c * plane + (sy + r0 + r) * sw + sx + c0;
+                float v[4];
+                if (valid == 4 && (reinterpret_cast<uintptr_t>(s) & (4 * sizeof(T) - 1)) == 0) {
+                    yuv_unpack4<T>(*reinterpret_cast<const typename yuv_vec4<T>::type*>(s), v);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] = k < valid ? to_float(s[k]) : 0.0f;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rgb[r][k][c] = yuv_quant(v[k]);
+            }
+        int Y[2][4], U[2], V[2];
+        yuv_encode_block(rgb, E, Y, U, V);
+        yuv_store_block(yp, up, vp, OW, dy + r0, dx + c0, valid, Y, U, V);
+    }
+}
+
+static unsigned yuv_blocks(long long work) {
+    const long long b = cdiv(work, 256);
+    return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
+}
+
+static YuvDec yuv_dec(const int32_t* c) { return YuvDec{c[0], c[1], c[2], c[3], c[4], c[5]}; }
+static YuvEnc yuv_enc(const int32_t* c) { return YuvEnc{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]}; }
+
+// the 14-bit tables of every matrix / range stay below these bounds, which keep each sum below 2^24 (2^26 for the
+// four-pixel chroma sum): int32 cannot overflow whatever the caller passes
+static bool yuv_coeffs_ok(const int32_t* c, int n) {
+    if (c[0] < 0 || c[0] > 255) return false;
+    for (int i = 1; i < n; ++i)
+        if (c[i] < -(1 << 16) || c[i] > (1 << 16)) return false;
+    return true;
+}
+
+template <typename T>
+static void yuv_gather(const void* y, const void* u, const void* v, int64_t H, int64_t W, YuvDec D, const int64_t* origins,
+                       int64_t n, int64_t h, int64_t w, void* out, hipStream_t st) {
+    const size_t al = sizeof(T) == 4 ? 16 : 8;
+    const int vec = w % 4 == 0 && reinterpret_cast<uintptr_t>(out) % al == 0;
+    const dim3 grid(yuv_blocks((h / 2 + 1) * (w / 4 + 1)), (unsigned)n);
+    prof_note((double)n * (double)(h * w) * (1.5 + 3.0 * sizeof(T)), 0.0);
+    OFASR_LAUNCH((tile_gather_yuv420_kernel<T>), grid, dim3(256), 0, st, (const uint8_t*)y, (const uint8_t*)u,
+                 (const uint8_t*)v, (long long)H, (long long)W, D, (const long long*)origins, (long long)h, (long long)w,
+                 (T*)out, vec);
+}
+
+template <typename T>
+static void yuv_scatter(const void* src, int64_t n, int64_t sh, int64_t sw, const int64_t* table, YuvEnc E, void* y, void* u,
+                        void* v, int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, hipStream_t st) {
+    const dim3 grid(yuv_blocks(cdiv(max_eh, 2) * cdiv(max_ew, 4)), (unsigned)n);
+    prof_note((double)n * (double)(max_eh * max_ew) * (1.5 + 3.0 * sizeof(T)), 0.0);
+    OFASR_LAUNCH((tile_scatter_yuv420_kernel<T>), grid, dim3(256), 0, st, (const T*)src, (long long)sh, (long long)sw,
+                 (const long long*)table, E, (uint8_t*)y, (uint8_t*)u, (uint8_t*)v, (long long)OH, (long long)OW,
+                 (long long)max_eh, (long long)max_ew);
+}
+
+}  // namespace ofasr
+
+using namespace ofasr;
+
+#define YUV_REQUIRE_FRAME(H, W)                                                                                          \
+    OFASR_REQUIRE((H) >= 2 && (W) >= 2, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);                          \
+    OFASR_REQUIRE((H) % 2 == 0 && (W) % 2 == 0, OFASR_ERR_INVALID_ARG, "%s: a 4:2:0 frame needs even sides, got %lldx%lld", \
+                  name, (long long)(H), (long long)(W));                                                                 \
+    OFASR_REQUIRE((H) <= (1LL << 40) / (W), OFASR_ERR_UNSUPPORTED, "%s: too large a frame", name)
+
+OFASR_EXPORT int ofasr_yuv420_to_rgb_u8(const void* y, const void* u, const void* v, int64_t H, int64_t W,
+                                        const int32_t* coeffs, void* rgb_hwc, void* stream) {
+    const char* name = "ofasr_yuv420_to_rgb_u8";
+    OFASR_REQUIRE(y && u && v && coeffs && rgb_hwc, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    YUV_REQUIRE_FRAME(H, W);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    prof_note((double)(H * W) * 4.5, 0.0);
+    OFASR_LAUNCH(yuv420_to_rgb_kernel, dim3(yuv_blocks((H / 2) * cdiv(W, 4))), dim3(256), 0, as_stream(stream),
+                 (const uint8_t*)y, (const uint8_t*)u, (const uint8_t*)v, (long long)H, (long long)W, yuv_dec(coeffs),
+                 (uint8_t*)rgb_hwc);
+    return check_launch(name);
+}
+
+OFASR_EXPORT int ofasr_rgb_to_yuv420_u8(const void* rgb_hwc, int64_t H, int64_t W, const int32_t* coeffs, void* y, void* u,
+                                        void* v, void* stream) {
+    const char* name = "ofasr_rgb_to_yuv420_u8";
+    OFASR_REQUIRE(y && u && v && coeffs && rgb_hwc, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    YUV_REQUIRE_FRAME(H, W);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 10), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    prof_note((double)(H * W) * 4.5, 0.0);
+    OFASR_LAUNCH(rgb_to_yuv420_kernel, dim3(yuv_blocks((H / 2) * cdiv(W, 4))), dim3(256), 0, as_stream(stream),
+                 (const uint8_t*)rgb_hwc, (long long)H, (long long)W, yuv_enc(coeffs), (uint8_t*)y, (uint8_t*)u, (uint8_t*)v);
+    return check_launch(name);
+}
+
+OFASR_EXPORT int ofasr_tile_gather_yuv420(const void* y, const void* u, const void* v, int64_t H, int64_t W,
+                                          const int32_t* coeffs, const int64_t* origins, int64_t n, int64_t h, int64_t w,
+                                          void* out, int dtype, void* stream) {
+    const char* name = "ofasr_tile_gather_yuv420";
+    OFASR_REQUIRE(y && u && v && coeffs && origins && out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE(n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
+    YUV_REQUIRE_FRAME(H, W);
+    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
+                  name);
+    OFASR_REQUIRE(h <= H && w <= W, OFASR_ERR_INVALID_ARG, "%s: window %lldx%lld larger than the frame %lldx%lld", name,
+                  (long long)h, (long long)w, (long long)H, (long long)W);
+    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    hipStream_t st = as_stream(stream);
+    const YuvDec D = yuv_dec(coeffs);
+    if (dtype == OFASR_F32) yuv_gather<float>(y, u, v, H, W, D, origins, n, h, w, out, st);
+    else if (dtype == OFASR_BF16) yuv_gather<bf16_t>(y, u, v, H, W, D, origins, n, h, w, out, st);
+    else yuv_gather<f16_t>(y, u, v, H, W, D, origins, n, h, w, out, st);
+    return check_launch(name);
+}
+
+OFASR_EXPORT int ofasr_tile_scatter_yuv420(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
+                                           const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW,
+                                           int64_t max_eh, int64_t max_ew, void* stream) {
+    const char* name = "ofasr_tile_scatter_yuv420";
+    OFASR_REQUIRE(src && table && coeffs && y && u && v, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
+    YUV_REQUIRE_FRAME(OH, OW);
+    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
+                  name);
+    OFASR_REQUIRE(max_eh <= sh && max_ew <= sw, OFASR_ERR_INVALID_ARG, "%s: extent bound larger than the source window",
+                  name);
+    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 10), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    hipStream_t st = as_stream(stream);
+    const YuvEnc E = yuv_enc(coeffs);
+    if (dtype == OFASR_F32) yuv_scatter<float>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    else if (dtype == OFASR_BF16) yuv_scatter<bf16_t>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    else yuv_scatter<f16_t>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    return check_launch(name);
+}

@@ -295,6 +295,60 @@ def quality_mse(output, target, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------ YUV 4:2:0 frames
+def yuv_table(matrix, full_range, encode):
+    """the decode (encode=False) or encode table of video.yuv_coeffs as the int32 host array the library reads"""
+    from . import video
+    t = video.yuv_coeffs(matrix, bool(full_range))[1 if encode else 0]
+    return (ctypes.c_int32 * len(t))(*t)
+
+
+def yuv420_planes(y, u, v, what):
+    """validate one frame: three contiguous uint8 GPU planes, y [H, W] with even sides, u and v [H/2, W/2] -> (H, W)"""
+    _gpu(y, u, v)
+    for p in (y, u, v):
+        if p.dtype != torch.uint8 or p.dim() != 2 or not p.is_contiguous() or p.device != y.device:
+            raise ValueError("%s needs three contiguous 2-D uint8 planes on one GPU" % what)
+    H, W = y.shape
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError("%s: a YUV 4:2:0 frame needs even sides, got %dx%d" % (what, W, H))
+    if tuple(u.shape) != (H // 2, W // 2) or tuple(v.shape) != (H // 2, W // 2):
+        raise ValueError("%s: chroma planes must be [%d, %d] for a %dx%d frame, got %s and %s"
+                         % (what, H // 2, W // 2, W, H, tuple(u.shape), tuple(v.shape)))
+    return H, W
+
+
+def yuv420_to_rgb_u8(y, u, v, matrix="bt601", full_range=False):
+    """planar YUV 4:2:0 (uint8 GPU planes y [H, W], u, v [H/2, W/2]) -> HWC uint8 RGB [H, W, 3]
+    (ofasr_yuv420_to_rgb_u8, csrc/yuv.hip; the definition is video.yuv420_to_rgb_host)"""
+    H, W = yuv420_planes(y, u, v, "yuv420_to_rgb_u8")
+    rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=y.device)
+    _C.check(_C.lib().ofasr_yuv420_to_rgb_u8(_p(y), _p(u), _p(v), H, W, yuv_table(matrix, full_range, False), _p(rgb),
+                                             _stream()), "ofasr_yuv420_to_rgb_u8")
+    return rgb
+
+
+def rgb_to_yuv420_u8(rgb, matrix="bt601", full_range=False, out=None):
+    """HWC uint8 RGB [H, W, 3] on the GPU (even sides) -> planes (y, u, v) (ofasr_rgb_to_yuv420_u8; the definition is
+    video.rgb_to_yuv420_host).  `out`: three planes to write into."""
+    _gpu(rgb)
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.size(2) != 3 or not rgb.is_contiguous():
+        raise ValueError("rgb_to_yuv420_u8 needs a contiguous HWC uint8 RGB image")
+    H, W = rgb.size(0), rgb.size(1)
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError("rgb_to_yuv420_u8: a YUV 4:2:0 frame needs even sides, got %dx%d" % (W, H))
+    if out is None:
+        out = (torch.empty(H, W, dtype=torch.uint8, device=rgb.device),
+               torch.empty(H // 2, W // 2, dtype=torch.uint8, device=rgb.device),
+               torch.empty(H // 2, W // 2, dtype=torch.uint8, device=rgb.device))
+    y, u, v = out
+    if yuv420_planes(y, u, v, "rgb_to_yuv420_u8") != (H, W) or y.device != rgb.device:
+        raise ValueError("rgb_to_yuv420_u8: the output planes do not match the %dx%d image" % (W, H))
+    _C.check(_C.lib().ofasr_rgb_to_yuv420_u8(_p(rgb), H, W, yuv_table(matrix, full_range, True), _p(y), _p(u), _p(v),
+                                             _stream()), "ofasr_rgb_to_yuv420_u8")
+    return y, u, v
+
+
 # ------------------------------------------------------------------------------ geometric self-ensemble
 ENSEMBLE_SIZES = (1, 2, 4, 8)
 

@@ -21,6 +21,12 @@ the 8 flips / transposes T_t and the outputs, mapped back, are averaged in fp32 
 stays exact: T_t of a window that was shifted into the image is the window of T_t(image) at the transformed place, so every
 outer window edge is still an image edge or at least `halo` from the core, and the tiled ensemble equals the ensemble of
 the whole image.  d4_transform / d4_inverse below are the host definition of T_t.
+
+Video frames (`upscale_yuv420`): a planar 8-bit YUV 4:2:0 frame goes through the same plan with the colour conversion of
+video.py inside the two tile moves (ofasr_tile_gather_yuv420 / ofasr_tile_scatter_yuv420, csrc/yuv.hip), so no RGB frame
+exists on either side of the network.  The gather decodes at frame coordinates (a window edge never replicates chroma) and
+takes the odd origins that a shift by the halo makes; the scatter needs even output rectangles, which an even frame and an
+even upscale factor give.
 """
 import math
 from fractions import Fraction
@@ -232,6 +238,40 @@ def tile_scatter(src, table, img, max_eh, max_ew):
     return img
 
 
+def tile_gather_yuv420(y, u, v, origins, h, w, dtype, matrix="bt601", full_range=False, out=None):
+    """planar YUV 4:2:0 frame (uint8 GPU planes y [H, W], u, v [H/2, W/2]) -> [n, 3, h, w] of dtype: the RGB of the
+    windows at `origins` (int64 [n, 2] on the GPU; odd origins are fine), decoded at frame coordinates, / 255 (fp32), cast
+    -- tile_gather(ops.yuv420_to_rgb_u8(y, u, v)) bit for bit without the RGB frame (ofasr_tile_gather_yuv420)"""
+    H, W = ops.yuv420_planes(y, u, v, "tile_gather_yuv420")
+    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous():
+        raise ValueError("tile_gather_yuv420 needs a contiguous int64 origin table on the GPU")
+    n = origins.size(0)
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=dtype, device=y.device)
+    _C.check(_C.lib().ofasr_tile_gather_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W,
+                                               ops.yuv_table(matrix, full_range, False), origins.data_ptr(), n, h, w,
+                                               out.data_ptr(), _CODES[out.dtype], ops._stream()),
+             "ofasr_tile_gather_yuv420")
+    return out
+
+
+def tile_scatter_yuv420(src, table, y, u, v, max_eh, max_ew, matrix="bt601", full_range=False):
+    """src: network output [n, 3, sh, sw]; table: int64 [n, 6] (sy, sx, dy, dx, eh, ew) on the GPU, dy / dx / eh / ew even
+    (the kernel clears their low bit); quantises as tile_scatter does and encodes every 2x2 block of the extents into the
+    planes y [OH, OW], u, v [OH/2, OW/2] (ofasr_tile_scatter_yuv420)"""
+    ops._gpu(src)
+    if not src.is_contiguous() or src.dim() != 4 or src.size(1) != 3:
+        raise ValueError("tile_scatter_yuv420 needs a contiguous [n, 3, h, w] source")
+    OH, OW = ops.yuv420_planes(y, u, v, "tile_scatter_yuv420")
+    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.size(0) > src.size(0):
+        raise ValueError("tile_scatter_yuv420 needs a contiguous int64 table on the GPU, one row per source window at most")
+    _C.check(_C.lib().ofasr_tile_scatter_yuv420(src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype],
+                                                table.data_ptr(), ops.yuv_table(matrix, full_range, True), y.data_ptr(),
+                                                u.data_ptr(), v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()),
+             "ofasr_tile_scatter_yuv420")
+    return y, u, v
+
+
 # ---------------------------------------------------------------------------------------------- self-ensemble
 def _d4_index(t):
     if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 8:
@@ -329,7 +369,11 @@ class TiledUpscaler(object):
     def _run(self, img, whole, sink):
         """run every batch of the plan; sink(y, real, tables, plan) consumes the network output of a batch"""
         img = self._image(img)
-        H, W = img.size(0), img.size(1)
+        return self._run_windows(img.size(0), img.size(1), img.device, whole, sink,
+                                 lambda origins, h, w: tile_gather(img, origins, h, w, self.dtype))
+
+    def _run_windows(self, H, W, device, whole, sink, gather):
+        """the same for any source of windows: gather(origins, h, w) -> the [n, 3, h, w] batch of self.dtype"""
         plan = self._whole_plan(H, W) if whole else self.plan(H, W)
         s = self.scale
         n = len(plan)
@@ -337,12 +381,12 @@ class TiledUpscaler(object):
         nb = -(-n // cap)
         B = -(-n // nb)
         wins = plan.windows + [plan.windows[-1]] * (nb * B - n)   # pad the last batch by repeating a window
-        origins = torch.tensor([[wy, wx] for (wy, wx, _, _, _, _) in wins], dtype=torch.int64).to(img.device)
+        origins = torch.tensor([[wy, wx] for (wy, wx, _, _, _, _) in wins], dtype=torch.int64).to(device)
         table = torch.tensor([[(cy - wy) * s, (cx - wx) * s, cy * s, cx * s, ch * s, cw * s]
-                              for (wy, wx, cy, cx, ch, cw) in plan.windows], dtype=torch.int64).to(img.device)
+                              for (wy, wx, cy, cx, ch, cw) in plan.windows], dtype=torch.int64).to(device)
         with torch.no_grad():
             for b in range(nb):
-                x = tile_gather(img, origins[b * B:(b + 1) * B], plan.win_h, plan.win_w, self.dtype)
+                x = gather(origins[b * B:(b + 1) * B], plan.win_h, plan.win_w)
                 if self.self_ensemble == 1:
                     y = self._forward(x)
                 else:
@@ -365,6 +409,43 @@ class TiledUpscaler(object):
                          max(w[5] for w in wins) * self.scale)
 
         self._run(img, whole, sink)
+        return out
+
+    def upscale_yuv420(self, y, u, v, matrix="bt601", full_range=False, whole=False):
+        """one planar YUV 4:2:0 frame (uint8 planes y [H, W], u, v [H/2, W/2]; CPU or GPU tensors, or numpy arrays) ->
+        the upscaled planes (Y [H*s, W*s], U, V [H*s/2, W*s/2]) on the GPU.  The same plan, graph replay and self-ensemble
+        as upscale(); the colour conversion is fused into the two tile moves (tile_gather_yuv420 / tile_scatter_yuv420),
+        so no RGB frame exists on either side: the result equals
+        ops.rgb_to_yuv420_u8(upscale(ops.yuv420_to_rgb_u8(y, u, v))) bit for bit."""
+        dev = next(self.net.parameters()).device
+        if dev.type != "cuda":
+            raise _C.OfasrError("TiledUpscaler needs the network on the GPU")
+        planes = []
+        for p in (y, u, v):
+            if not torch.is_tensor(p):
+                p = torch.from_numpy(p)
+            if p.dtype != torch.uint8 or p.dim() != 2:
+                raise ValueError("upscale_yuv420 takes three 2-D uint8 planes, got %s %s" % (tuple(p.shape), p.dtype))
+            planes.append(p.to(dev).contiguous())
+        y, u, v = planes
+        H, W = int(y.shape[0]), int(y.shape[1])
+        s = self.scale
+        if H < 2 or W < 2 or H % 2 or W % 2:
+            raise ValueError("a YUV 4:2:0 frame needs even sides, got %dx%d" % (W, H))
+        if s % 2:
+            raise ValueError("YUV 4:2:0 upscaling needs an even upscale factor (window cores must land on whole chroma "
+                             "samples of the output), this network's is %d" % s)
+        ops.yuv420_planes(y, u, v, "upscale_yuv420")
+        out = (torch.empty(H * s, W * s, dtype=torch.uint8, device=dev),
+               torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev),
+               torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev))
+
+        def sink(t, real, table, wins, plan):
+            tile_scatter_yuv420(t.contiguous(), table, out[0], out[1], out[2], max(w[4] for w in wins) * s,
+                                max(w[5] for w in wins) * s, matrix, full_range)
+
+        self._run_windows(H, W, dev, whole, sink,
+                          lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range))
         return out
 
     def upscale_float(self, img, whole=False):

@@ -1,0 +1,362 @@
+"""Raw 8-bit YUV 4:2:0 video for the upscaling path: the host definition of the colour conversion that the HIP kernels of
+csrc/yuv.hip implement, and streaming readers / writers for Y4M (YUV4MPEG2) and headerless `yuv420p` files.
+
+numpy only: nothing here touches the GPU, and importing this module loads no GPU code.
+
+The conversion is a pinned definition of this project, all of it integer arithmetic (int32 suffices: every sum stays
+below 2^24 in magnitude), so host and device agree bit for bit.  With S = 14, q(v) = int(round(v * 2^S)) and >> the
+arithmetic (floor) shift:
+
+  coefficients   (Kr, Kb) = (0.299, 0.114) for bt601, (0.2126, 0.0722) for bt709, Kg = 1 - Kr - Kb; limited ("tv") range:
+                 yo = 16, ys = 255/219, cs = 255/224, yi = 219/255, ci = 224/255; full ("pc") range: yo = 0, scales 1.
+                 decode: cy = q(ys), rv = q(cs 2(1-Kr)), gu = q(-cs 2(1-Kb) Kb/Kg), gv = q(-cs 2(1-Kr) Kr/Kg),
+                         bu = q(cs 2(1-Kb))
+                 encode: yr, yg, yb = q(yi K*); ur = q(-ci Kr / (2(1-Kb))), ug = q(-ci Kg / (2(1-Kb))), ub = q(ci / 2);
+                         vr = q(ci / 2), vg = q(-ci Kg / (2(1-Kr))), vb = q(-ci Kb / (2(1-Kr)))
+                 (the U row and the V row each sum to exactly 0 in all four matrix x range combinations: grey stays grey)
+  decode         chroma to full resolution by the centre-sited 9-3-3-1 filter, edge replication at the frame edge: for
+                 pixel (y, x), cy0 = y >> 1, the vertical neighbour row is cy0 - 1 for even y and cy0 + 1 for odd y, the
+                 horizontal one alike from x, both clamped into the plane, and
+                     c = (9 C[cy0,cx0] + 3 C[cy0,nx] + 3 C[ny,cx0] + C[ny,nx] + 8) >> 4
+                 then with y' = Y - yo, u = c_U - 128, v = c_V - 128:
+                     R = clamp((cy y' + rv v + 2^13) >> 14), G = clamp((cy y' + gu u + gv v + 2^13) >> 14),
+                     B = clamp((cy y' + bu u + 2^13) >> 14)
+  encode         Y = clamp(((yr R + yg G + yb B + 2^13) >> 14) + yo) per pixel; chroma is the 2x2 box with one rounding:
+                     U = clamp(((sum of the 4 pixels' (ur R + ug G + ub B) + 2^15) >> 16) + 128), V alike.
+
+Chroma siting.  Every accepted 4:2:0 flavour (C420jpeg, C420mpeg2, C420paldv, plain C420) is treated as centre-sited
+(the JPEG / MPEG-1 siting), which is exact for C420jpeg.  MPEG-2 siting puts the chroma sample a quarter of a luma pixel to
+the left, PAL-DV co-sites Cb and Cr on alternating lines; treating them as centred shifts chroma by at most half a chroma
+sample, and the output carries the input's tag, so the same convention applies on both sides of the network.
+"""
+import collections
+import os
+
+import numpy as np
+
+S = 14
+MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+
+DecodeCoeffs = collections.namedtuple("DecodeCoeffs", "yo cy rv gu gv bu")
+EncodeCoeffs = collections.namedtuple("EncodeCoeffs", "yo yr yg yb ur ug ub vr vg vb")
+
+
+def _q(v):
+    return int(round(v * 2 ** S))
+
+
+def yuv_coeffs(matrix="bt601", full_range=False):
+    """(DecodeCoeffs, EncodeCoeffs): the two integer tables of one matrix / range, in the field order the kernels take"""
+    if matrix not in MATRICES:
+        raise ValueError("matrix must be one of %s, got %r" % (sorted(MATRICES), matrix))
+    kr, kb = MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    if full_range:
+        yo, ys, cs, yi, ci = 0, 1.0, 1.0, 1.0, 1.0
+    else:
+        yo, ys, cs, yi, ci = 16, 255.0 / 219.0, 255.0 / 224.0, 219.0 / 255.0, 224.0 / 255.0
+    dec = DecodeCoeffs(yo, _q(ys), _q(cs * 2 * (1 - kr)), _q(-cs * 2 * (1 - kb) * kb / kg),
+                       _q(-cs * 2 * (1 - kr) * kr / kg), _q(cs * 2 * (1 - kb)))
+    enc = EncodeCoeffs(yo, _q(yi * kr), _q(yi * kg), _q(yi * kb),
+                       _q(-ci * kr / (2 * (1 - kb))), _q(-ci * kg / (2 * (1 - kb))), _q(ci / 2),
+                       _q(ci / 2), _q(-ci * kg / (2 * (1 - kr))), _q(-ci * kb / (2 * (1 - kr))))
+    return dec, enc
+
+
+def _planes(y, u, v):
+    y, u, v = (np.asarray(p) for p in (y, u, v))
+    if y.ndim != 2 or y.dtype != np.uint8 or u.dtype != np.uint8 or v.dtype != np.uint8:
+        raise ValueError("a YUV 4:2:0 frame is three 2-D uint8 planes")
+    H, W = y.shape
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError("a YUV 4:2:0 frame needs even sides, got %dx%d" % (W, H))
+    if u.shape != (H // 2, W // 2) or v.shape != (H // 2, W // 2):
+        raise ValueError("chroma planes must be %dx%d for a %dx%d frame, got %s and %s"
+                         % (W // 2, H // 2, W, H, u.shape, v.shape))
+    return y, u, v
+
+
+def upsample_chroma_host(c, H, W):
+    """[H/2, W/2] -> [H, W] int32 by the centre-sited 9-3-3-1 filter with edge replication"""
+    c = np.asarray(c).astype(np.int32)
+    CH, CW = c.shape
+
+    def taps(L, n):
+        p = np.arange(L)
+        c0 = p >> 1
+        return c0, np.clip(np.where(p % 2 == 0, c0 - 1, c0 + 1), 0, n - 1)
+
+    cy0, ny = taps(H, CH)
+    cx0, nx = taps(W, CW)
+    return (9 * c[cy0][:, cx0] + 3 * c[cy0][:, nx] + 3 * c[ny][:, cx0] + c[ny][:, nx] + 8) >> 4
+
+
+def yuv420_to_rgb_host(y, u, v, matrix="bt601", full_range=False):
+    """planes y [H, W], u, v [H/2, W/2] (uint8) -> HWC uint8 RGB [H, W, 3]: the definition of the decode"""
+    y, u, v = _planes(y, u, v)
+    d, _ = yuv_coeffs(matrix, full_range)
+    H, W = y.shape
+    yy = y.astype(np.int32) - d.yo
+    uu = upsample_chroma_host(u, H, W) - 128
+    vv = upsample_chroma_host(v, H, W) - 128
+    half = 1 << (S - 1)
+    r = (d.cy * yy + d.rv * vv + half) >> S
+    g = (d.cy * yy + d.gu * uu + d.gv * vv + half) >> S
+    b = (d.cy * yy + d.bu * uu + half) >> S
+    return np.clip(np.stack([r, g, b], axis=2), 0, 255).astype(np.uint8)
+
+
+def rgb_to_yuv420_host(rgb, matrix="bt601", full_range=False):
+    """HWC uint8 RGB [H, W, 3] (even sides) -> planes (y [H, W], u [H/2, W/2], v [H/2, W/2]): the definition of the encode"""
+    rgb = np.asarray(rgb)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.dtype != np.uint8:
+        raise ValueError("rgb_to_yuv420_host takes an HWC uint8 RGB image")
+    H, W = rgb.shape[:2]
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError("a YUV 4:2:0 frame needs even sides, got %dx%d" % (W, H))
+    _, e = yuv_coeffs(matrix, full_range)
+    p = rgb.astype(np.int32)
+    r, g, b = p[..., 0], p[..., 1], p[..., 2]
+    y = np.clip(((e.yr * r + e.yg * g + e.yb * b + (1 << (S - 1))) >> S) + e.yo, 0, 255).astype(np.uint8)
+
+    def box(cr, cg, cb):
+        s = (cr * r + cg * g + cb * b).reshape(H // 2, 2, W // 2, 2).sum(axis=(1, 3))
+        return np.clip(((s + (1 << (S + 1))) >> (S + 2)) + 128, 0, 255).astype(np.uint8)
+
+    return y, box(e.ur, e.ug, e.ub), box(e.vr, e.vg, e.vb)
+
+
+# ---------------------------------------------------------------------------------------------- files
+Y4M_MAGIC = b"YUV4MPEG2"
+Y4M_CHROMA = ("420jpeg", "420mpeg2", "420paldv", "420")   # 8-bit 4:2:0, all read as centre-sited (see the module text)
+_MAX_LINE = 4096
+
+
+def frame_bytes(width, height):
+    return width * height * 3 // 2
+
+
+def _check_size(width, height, what):
+    if width < 2 or height < 2 or width % 2 or height % 2:
+        raise ValueError("%s: 4:2:0 needs even, positive sides, got W%d H%d" % (what, width, height))
+
+
+def split_frame(buf, width, height):
+    """views (y, u, v) of one frame's bytes (a 1-D uint8 array of frame_bytes(width, height))"""
+    n = width * height
+    return (buf[:n].reshape(height, width), buf[n:n + n // 4].reshape(height // 2, width // 2),
+            buf[n + n // 4:n + n // 2].reshape(height // 2, width // 2))
+
+
+class _FrameReader(object):
+    """one frame in memory at a time; read_frame(out=None) -> (y, u, v) views of `out` (a 1-D uint8 array of
+    frame_bytes, e.g. a view of pinned memory) or of a fresh array, None at the end of the file"""
+    width = height = 0
+
+    def __init__(self, path):
+        self.path = path
+        self._f = open(path, "rb")
+        self.frames_read = 0
+
+    def _before_frame(self):
+        return True
+
+    def _payload(self, out):
+        n = frame_bytes(self.width, self.height)
+        if out is None:
+            out = np.empty(n, dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.ndim != 1 or out.size != n or not out.flags.c_contiguous:
+            raise ValueError("the frame buffer must be a contiguous 1-D uint8 array of %d bytes" % n)
+        got, view = 0, memoryview(out)
+        while got < n:
+            k = self._f.readinto(view[got:])
+            if not k:
+                break
+            got += k
+        return got, out
+
+    def read_frame(self, out=None):
+        if not self._before_frame():
+            return None
+        got, out = self._payload(out)
+        n = frame_bytes(self.width, self.height)
+        if got == 0 and self._eof_ok_without_payload():
+            return None
+        if got != n:
+            raise ValueError("%s: frame %d is truncated (%d of %d bytes)" % (self.path, self.frames_read, got, n))
+        self.frames_read += 1
+        return split_frame(out, self.width, self.height)
+
+    def _eof_ok_without_payload(self):
+        return True
+
+    def skip_frame(self):
+        """advance past one frame without keeping it; False at the end of the file"""
+        return self.read_frame() is not None
+
+    def __iter__(self):
+        while True:
+            fr = self.read_frame()
+            if fr is None:
+                return
+            yield fr
+
+    def close(self):
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Y4MReader(_FrameReader):
+    """streaming YUV4MPEG2 reader.  Header tags: W, H (required), F (frame rate "num:den"), I (interlacing), A (pixel
+    aspect), C (chroma format; absent means 420jpeg), X (comments, kept in order in `xtags`).  The parameters of the
+    FRAME line of the frame read last are in `frame_params`.  Only 8-bit 4:2:0 is accepted."""
+
+    def __init__(self, path):
+        super(Y4MReader, self).__init__(path)
+        try:
+            line = self._line()
+            tags = line.split(b" ")
+            if tags[0] != Y4M_MAGIC:
+                raise ValueError("%s: not a YUV4MPEG2 file" % path)
+            self.fps = self.interlace = self.aspect = None
+            self.chroma = "420jpeg"
+            self.xtags = []
+            width = height = None
+            for t in tags[1:]:
+                if not t:
+                    continue
+                k, val = t[:1], t[1:].decode("ascii", "replace")
+                if k == b"W":
+                    width = int(val)
+                elif k == b"H":
+                    height = int(val)
+                elif k == b"F":
+                    self.fps = val
+                elif k == b"I":
+                    self.interlace = val
+                elif k == b"A":
+                    self.aspect = val
+                elif k == b"C":
+                    self.chroma = val
+                elif k == b"X":
+                    self.xtags.append(val)
+                else:
+                    raise ValueError("%s: unknown header tag %r" % (path, t.decode("ascii", "replace")))
+            if width is None or height is None:
+                raise ValueError("%s: the header has no W / H tag" % path)
+            if self.chroma not in Y4M_CHROMA:
+                raise ValueError("%s: chroma format C%s is not supported (8-bit 4:2:0 only: %s)"
+                                 % (path, self.chroma, ", ".join("C" + c for c in Y4M_CHROMA)))
+            _check_size(width, height, path)
+            self.width, self.height = width, height
+            self.frame_params = ""
+        except Exception:
+            self._f.close()
+            raise
+
+    def _line(self):
+        line = self._f.readline(_MAX_LINE)
+        if line and not line.endswith(b"\n"):
+            raise ValueError("%s: truncated or overlong header line" % self.path)
+        return line[:-1]
+
+    def _before_frame(self):
+        raw = self._f.readline(_MAX_LINE)
+        if not raw:
+            return False
+        if not raw.endswith(b"\n") or not (raw[:-1] == b"FRAME" or raw.startswith(b"FRAME ")):
+            raise ValueError("%s: frame %d: bad or truncated FRAME line %r" % (self.path, self.frames_read, raw[:32]))
+        self.frame_params = raw[6:-1].decode("ascii", "replace")
+        return True
+
+    def _eof_ok_without_payload(self):
+        return False      # a FRAME line was read: its payload must follow
+
+
+class RawYUV420Reader(_FrameReader):
+    """headerless planar yuv420p: frames of width * height * 3 / 2 bytes; the file must hold a whole number of them"""
+
+    def __init__(self, path, width, height):
+        _check_size(width, height, path)
+        size = os.path.getsize(path)
+        n = frame_bytes(width, height)
+        if size == 0 or size % n:
+            raise ValueError("%s: %d bytes is not a whole number of %dx%d yuv420p frames (%d bytes each)"
+                             % (path, size, width, height, n))
+        super(RawYUV420Reader, self).__init__(path)
+        self.width, self.height = width, height
+        self.frames = size // n
+
+    def skip_frame(self):
+        if self.frames_read >= self.frames:
+            return False
+        self._f.seek(frame_bytes(self.width, self.height), os.SEEK_CUR)
+        self.frames_read += 1
+        return True
+
+
+class _FrameWriter(object):
+    def __init__(self, path, width, height):
+        _check_size(width, height, path)
+        self.path, self.width, self.height = path, width, height
+        self._f = open(path, "wb")
+        self.frames_written = 0
+
+    def _plane(self, p, shape):
+        p = np.ascontiguousarray(p)
+        if p.dtype != np.uint8 or p.shape != shape:
+            raise ValueError("%s: expected a uint8 plane of shape %s, got %s %s" % (self.path, shape, p.dtype, p.shape))
+        return p
+
+    def _write_planes(self, y, u, v):
+        H, W = self.height, self.width
+        for p, shape in ((y, (H, W)), (u, (H // 2, W // 2)), (v, (H // 2, W // 2))):
+            self._f.write(memoryview(self._plane(p, shape)).cast("B"))
+        self.frames_written += 1
+
+    def close(self):
+        self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Y4MWriter(_FrameWriter):
+    """streaming YUV4MPEG2 writer; fps / interlace / aspect / chroma / xtags as Y4MReader reports them (None: tag left out)"""
+
+    def __init__(self, path, width, height, fps=None, interlace=None, aspect=None, chroma="420jpeg", xtags=()):
+        if chroma not in Y4M_CHROMA:
+            raise ValueError("chroma format C%s is not supported (8-bit 4:2:0 only)" % chroma)
+        super(Y4MWriter, self).__init__(path, width, height)
+        tags = ["W%d" % width, "H%d" % height]
+        for k, val in (("F", fps), ("I", interlace), ("A", aspect), ("C", chroma)):
+            if val is not None:
+                tags.append(k + str(val))
+        tags += ["X" + str(x) for x in xtags]
+        self._f.write(Y4M_MAGIC + b" " + " ".join(tags).encode("ascii") + b"\n")
+
+    def write_frame(self, y, u, v, params=""):
+        self._f.write(b"FRAME" + ((" " + params).encode("ascii") if params else b"") + b"\n")
+        self._write_planes(y, u, v)
+
+
+class RawYUV420Writer(_FrameWriter):
+    def write_frame(self, y, u, v, params=""):
+        self._write_planes(y, u, v)
+
+
+def open_reader(path, size=None):
+    """Y4MReader for *.y4m; RawYUV420Reader otherwise (size = (width, height) required)"""
+    if path.lower().endswith(".y4m"):
+        return Y4MReader(path)
+    if size is None:
+        raise ValueError("%s: a headerless yuv420p file needs its frame size (WxH)" % path)
+    return RawYUV420Reader(path, size[0], size[1])
