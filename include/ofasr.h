@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 307 /* + ofasr_yuv420_to_rgb_u8, ofasr_rgb_to_yuv420_u8, ofasr_tile_gather_yuv420, ofasr_tile_scatter_yuv420 */
+#define OFASR_VERSION 308 /* + ofasr_window_diff_slabs, ofasr_window_diff_yuv420, ofasr_window_compact */
 
 typedef enum {
     OFASR_OK = 0,
@@ -464,6 +464,42 @@ int ofasr_tile_gather_yuv420(const void* y, const void* u, const void* v, int64_
 int ofasr_tile_scatter_yuv420(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
                               const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW, int64_t max_eh,
                               int64_t max_ew, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Window reuse between video frames (csrc/reuse.hip; host statement: video.py window_support / changed_windows_host) --
+ * for upscale.py's YUV420Stream: a window of the tile plan whose input bytes equal the previous frame's keeps the previous
+ * frame's output core, so only the changed windows go through the network.
+ *   support of window n, (y0, x0) = origins[n] clamped to 0 <= y0 <= H - h, 0 <= x0 <= W - w as ofasr_tile_gather_yuv420
+ *   clamps it:
+ *     luma    rows y0 .. y0 + h - 1,                                      columns x0 .. x0 + w - 1
+ *     chroma  rows max(0, (y0 - 1) >> 1) .. min(H/2 - 1, (y0 + h) >> 1),  columns alike from x0, w, W
+ *   -- every sample the gather's decode of the window depends on, the 9-3-3-1 filter's neighbour tap included.
+ *   ofasr_window_diff_yuv420: y, u, v the current frame, py, pu, pv the previous one (planes as above, [H, W] and
+ *     [H/2, W/2] uint8; H, W even).  flags is a device int32 table [n][S], S = ofasr_window_diff_slabs(h, w) (a host-only
+ *     query, 1 <= S <= 64; 0 for non-positive sizes): flags[n][s] = 1 if any byte of row slab s of the window's support
+ *     differs between the two frames in y, u or v, else 0.  Window n is changed iff any of its S flags is set.  Every
+ *     flag is written by every call.  Odd origins and odd h, w are fine; any byte-aligned plane pointers (16-byte loads
+ *     only where both planes' addresses are aligned for them, bytes elsewhere).
+ *   ofasr_window_compact: ONE workgroup.  From flags [n][slabs], the plan's origins [n][2] and scatter table [n][6]
+ *     (device int64) and the batch size `batch`, with m the number of changed windows and i_0 < i_1 < ... < i_{m-1} their
+ *     indices (stable, plan order):
+ *       out_index[j] = i_j, out_table[j][:] = table[i_j][:], out_origins[j][:] = origins[i_j][:]     for j < m
+ *       out_origins[j][:] = origins[i_{m-1}][:]        for m <= j < ceil(m / batch) * batch   (the last batch filled up
+ *                                                       by repeating the last changed window)
+ *       count[0] = m                                   (one int64 in device memory)
+ *     out_origins holds ceil(n / batch) * batch rows, out_table and out_index n; rows past the ones named are not written.
+ *     The call does not synchronise: the caller reads `count` back when it needs m on the host.
+ * Plain loads and stores, no atomics: two calls give identical bytes.  Every access stays inside its plane or table
+ * whatever the origin table holds.  64-bit addressing.  OFASR_ERR_INVALID_ARG: a null pointer, an odd or non-positive
+ * side, a window larger than the frame, slabs > 64.  OFASR_ERR_UNSUPPORTED: n or batch > 65535, more than 2^40 pixels.
+ * ------------------------------------------------------------------------------------------- */
+int64_t ofasr_window_diff_slabs(int64_t h, int64_t w);
+int ofasr_window_diff_yuv420(const void* y, const void* u, const void* v, const void* py, const void* pu, const void* pv,
+                             int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h, int64_t w, int32_t* flags,
+                             void* stream);
+int ofasr_window_compact(const int32_t* flags, int64_t slabs, const int64_t* origins, const int64_t* table, int64_t n,
+                         int64_t batch, int64_t* out_origins, int64_t* out_table, int64_t* out_index, int64_t* count,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Geometric self-ensemble: the 8 flips / transposes (the dihedral group D4) of an NCHW batch and the fp32 merge of the

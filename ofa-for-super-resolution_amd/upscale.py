@@ -27,6 +27,15 @@ video.py inside the two tile moves (ofasr_tile_gather_yuv420 / ofasr_tile_scatte
 exists on either side of the network.  The gather decodes at frame coordinates (a window edge never replicates chroma) and
 takes the odd origins that a shift by the halo makes; the scatter needs even output rectangles, which an even frame and an
 even upscale factor give.
+
+Video streams (`yuv420_stream`): consecutive frames often repeat bytes exactly (screen recordings, animation, letterbox
+bars, duplicated frames, a codec's skip blocks).  The core of a window's output depends only on the input bytes of that
+window, so a window whose support (video.window_support) is unchanged keeps the previous frame's output bytes.
+YUV420Stream keeps the previous input planes and the output planes on the GPU, finds the changed windows with
+ofasr_window_diff_yuv420, compacts their table rows with ofasr_window_compact (csrc/reuse.hip) and runs only those,
+in batches of the full plan's batch size, so that every forward has the shape of the non-reuse path and replays the
+same captured graph: the output equals upscale_yuv420's bit for bit.  The comparison is exact, so it does nothing for
+camera noise.
 """
 import math
 from fractions import Fraction
@@ -272,6 +281,66 @@ def tile_scatter_yuv420(src, table, y, u, v, max_eh, max_ew, matrix="bt601", ful
     return y, u, v
 
 
+def window_diff_slabs(h, w):
+    """row slabs per window of window_diff_yuv420's flag table (ofasr_window_diff_slabs; host only)"""
+    return int(_C.lib().ofasr_window_diff_slabs(h, w))
+
+
+def window_diff_yuv420(y, u, v, py, pu, pv, origins, h, w, flags=None):
+    """two planar YUV 4:2:0 frames of one size (current y, u, v and previous py, pu, pv: uint8 GPU planes) and the
+    int64 origin table [n, 2] of h x w windows on the GPU -> int32 flags [n, window_diff_slabs(h, w)]: a window's row is
+    non-zero iff any byte of its support (video.window_support) differs between the frames (ofasr_window_diff_yuv420;
+    host definition: video.changed_windows_host)"""
+    H, W = ops.yuv420_planes(y, u, v, "window_diff_yuv420")
+    if ops.yuv420_planes(py, pu, pv, "window_diff_yuv420") != (H, W):
+        raise ValueError("window_diff_yuv420 needs two frames of one size")
+    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous() or origins.dim() != 2 \
+            or origins.size(1) != 2:
+        raise ValueError("window_diff_yuv420 needs a contiguous int64 origin table [n, 2] on the GPU")
+    n = origins.size(0)
+    S = window_diff_slabs(h, w)
+    if flags is None:
+        flags = torch.empty(n, max(S, 1), dtype=torch.int32, device=y.device)
+    elif flags.dtype != torch.int32 or not flags.is_cuda or not flags.is_contiguous() or flags.numel() != n * S:
+        raise ValueError("window_diff_yuv420 needs contiguous int32 flags [n, %d] on the GPU" % S)
+    _C.check(_C.lib().ofasr_window_diff_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), py.data_ptr(), pu.data_ptr(),
+                                               pv.data_ptr(), H, W, origins.data_ptr(), n, h, w, flags.data_ptr(),
+                                               ops._stream()), "ofasr_window_diff_yuv420")
+    return flags
+
+
+def window_compact(flags, origins, table, batch, out=None):
+    """flags: int32 [n, S] from window_diff_yuv420; origins [n, 2] and table [n, 6]: the plan's int64 tables on the GPU ->
+    (origins of the changed windows in plan order, filled up to a multiple of `batch` by repeating the last one
+    [ceil(n / batch) * batch, 2]; their table rows [n, 6]; their plan indices [n]; their number, int64 [1]), all on the
+    GPU; rows past the count (past the filled count for the origins) are not written.  One workgroup, no
+    synchronisation (ofasr_window_compact)."""
+    ops._gpu(flags)
+    n = origins.size(0)
+    batch = int(batch)
+    for t, cols in ((origins, 2), (table, 6)):
+        if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or tuple(t.shape) != (n, cols):
+            raise ValueError("window_compact needs contiguous int64 tables [n, 2] and [n, 6] on the GPU")
+    if flags.dtype != torch.int32 or not flags.is_contiguous() or flags.dim() != 2 or flags.size(0) != n:
+        raise ValueError("window_compact needs contiguous int32 flags [n, S]")
+    if batch < 1:
+        raise ValueError("window_compact needs a positive batch size")
+    rows = -(-n // batch) * batch
+    if out is None:
+        out = (torch.zeros(rows, 2, dtype=torch.int64, device=flags.device),
+               torch.zeros(n, 6, dtype=torch.int64, device=flags.device),
+               torch.zeros(n, dtype=torch.int64, device=flags.device),
+               torch.zeros(1, dtype=torch.int64, device=flags.device))
+    o, t, idx, count = out
+    if (tuple(o.shape), tuple(t.shape), tuple(idx.shape), tuple(count.shape)) != ((rows, 2), (n, 6), (n,), (1,)) or \
+            any(b.dtype != torch.int64 or not b.is_cuda or not b.is_contiguous() for b in out):
+        raise ValueError("window_compact needs contiguous int64 outputs [%d, 2], [%d, 6], [%d], [1] on the GPU" % (rows, n, n))
+    _C.check(_C.lib().ofasr_window_compact(flags.data_ptr(), flags.size(1), origins.data_ptr(), table.data_ptr(), n, batch,
+                                           o.data_ptr(), t.data_ptr(), idx.data_ptr(), count.data_ptr(), ops._stream()),
+             "ofasr_window_compact")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- self-ensemble
 def _d4_index(t):
     if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 8:
@@ -372,27 +441,43 @@ class TiledUpscaler(object):
         return self._run_windows(img.size(0), img.size(1), img.device, whole, sink,
                                  lambda origins, h, w: tile_gather(img, origins, h, w, self.dtype))
 
-    def _run_windows(self, H, W, device, whole, sink, gather):
-        """the same for any source of windows: gather(origins, h, w) -> the [n, 3, h, w] batch of self.dtype"""
-        plan = self._whole_plan(H, W) if whole else self.plan(H, W)
-        s = self.scale
+    def _batching(self, plan):
+        """(batches, windows per batch) of a plan: as many windows per batch as the plan and `batch` allow, spread evenly"""
         n = len(plan)
         cap = min(plan.batch, int(self.batch)) if self.batch else plan.batch
         nb = -(-n // cap)
-        B = -(-n // nb)
-        wins = plan.windows + [plan.windows[-1]] * (nb * B - n)   # pad the last batch by repeating a window
+        return nb, -(-n // nb)
+
+    def _tables(self, plan, device):
+        """the plan's device tables: window origins [nb * B, 2], the last batch padded by repeating a window, and the
+        scatter rows [n, 6] = (sy, sx, dy, dx, eh, ew) in output pixels"""
+        s = self.scale
+        nb, B = self._batching(plan)
+        wins = plan.windows + [plan.windows[-1]] * (nb * B - len(plan))
         origins = torch.tensor([[wy, wx] for (wy, wx, _, _, _, _) in wins], dtype=torch.int64).to(device)
         table = torch.tensor([[(cy - wy) * s, (cx - wx) * s, cy * s, cx * s, ch * s, cw * s]
                               for (wy, wx, cy, cx, ch, cw) in plan.windows], dtype=torch.int64).to(device)
+        return origins, table
+
+    def _run_batches(self, plan, origins, table, n, B, sink, gather, wins=None):
+        """the batch loop: the first n rows of `origins` (padded to a multiple of B) / `table` in batches of B windows.
+        `wins`: the plan windows behind the rows, where the host knows them (sink gets the batch's slice, or None)"""
         with torch.no_grad():
-            for b in range(nb):
+            for b in range(-(-n // B)):
                 x = gather(origins[b * B:(b + 1) * B], plan.win_h, plan.win_w)
                 if self.self_ensemble == 1:
                     y = self._forward(x)
                 else:
                     y = ops.self_ensemble(self._forward, x, self.self_ensemble)
                 real = min(B, n - b * B)
-                sink(y, real, table[b * B:b * B + real], plan.windows[b * B:b * B + real], plan)
+                sink(y, real, table[b * B:b * B + real], wins[b * B:b * B + real] if wins is not None else None, plan)
+
+    def _run_windows(self, H, W, device, whole, sink, gather):
+        """the same for any source of windows: gather(origins, h, w) -> the [n, 3, h, w] batch of self.dtype"""
+        plan = self._whole_plan(H, W) if whole else self.plan(H, W)
+        _, B = self._batching(plan)
+        origins, table = self._tables(plan, device)
+        self._run_batches(plan, origins, table, len(plan), B, sink, gather, plan.windows)
         return plan
 
     def upscale(self, img, whole=False):
@@ -411,12 +496,8 @@ class TiledUpscaler(object):
         self._run(img, whole, sink)
         return out
 
-    def upscale_yuv420(self, y, u, v, matrix="bt601", full_range=False, whole=False):
-        """one planar YUV 4:2:0 frame (uint8 planes y [H, W], u, v [H/2, W/2]; CPU or GPU tensors, or numpy arrays) ->
-        the upscaled planes (Y [H*s, W*s], U, V [H*s/2, W*s/2]) on the GPU.  The same plan, graph replay and self-ensemble
-        as upscale(); the colour conversion is fused into the two tile moves (tile_gather_yuv420 / tile_scatter_yuv420),
-        so no RGB frame exists on either side: the result equals
-        ops.rgb_to_yuv420_u8(upscale(ops.yuv420_to_rgb_u8(y, u, v))) bit for bit."""
+    def _yuv420_frame(self, y, u, v):
+        """(device, the three planes on it, H, W) of one frame for the YUV paths; refuses what they cannot take"""
         dev = next(self.net.parameters()).device
         if dev.type != "cuda":
             raise _C.OfasrError("TiledUpscaler needs the network on the GPU")
@@ -429,13 +510,22 @@ class TiledUpscaler(object):
             planes.append(p.to(dev).contiguous())
         y, u, v = planes
         H, W = int(y.shape[0]), int(y.shape[1])
-        s = self.scale
         if H < 2 or W < 2 or H % 2 or W % 2:
             raise ValueError("a YUV 4:2:0 frame needs even sides, got %dx%d" % (W, H))
-        if s % 2:
+        if self.scale % 2:
             raise ValueError("YUV 4:2:0 upscaling needs an even upscale factor (window cores must land on whole chroma "
-                             "samples of the output), this network's is %d" % s)
+                             "samples of the output), this network's is %d" % self.scale)
         ops.yuv420_planes(y, u, v, "upscale_yuv420")
+        return dev, (y, u, v), H, W
+
+    def upscale_yuv420(self, y, u, v, matrix="bt601", full_range=False, whole=False):
+        """one planar YUV 4:2:0 frame (uint8 planes y [H, W], u, v [H/2, W/2]; CPU or GPU tensors, or numpy arrays) ->
+        the upscaled planes (Y [H*s, W*s], U, V [H*s/2, W*s/2]) on the GPU.  The same plan, graph replay and self-ensemble
+        as upscale(); the colour conversion is fused into the two tile moves (tile_gather_yuv420 / tile_scatter_yuv420),
+        so no RGB frame exists on either side: the result equals
+        ops.rgb_to_yuv420_u8(upscale(ops.yuv420_to_rgb_u8(y, u, v))) bit for bit."""
+        dev, (y, u, v), H, W = self._yuv420_frame(y, u, v)
+        s = self.scale
         out = (torch.empty(H * s, W * s, dtype=torch.uint8, device=dev),
                torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev),
                torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev))
@@ -447,6 +537,11 @@ class TiledUpscaler(object):
         self._run_windows(H, W, dev, whole, sink,
                           lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range))
         return out
+
+    def yuv420_stream(self, matrix="bt601", full_range=False):
+        """a YUV420Stream on this upscaler: upscale_yuv420 for the consecutive frames of one video, re-running only the
+        windows whose input bytes changed since the previous frame; the same output bit for bit"""
+        return YUV420Stream(self, matrix, full_range)
 
     def upscale_float(self, img, whole=False):
         """the network's fp32 output [3, H*scale, W*scale] before quantisation, assembled from the same window cores
@@ -464,4 +559,124 @@ class TiledUpscaler(object):
                     y[i, :, (cy - wy) * s:(cy - wy + ch) * s, (cx - wx) * s:(cx - wx + cw) * s].float()
 
         self._run(img, whole, sink)
+        return out
+
+
+# ---------------------------------------------------------------------------------------------- video stream
+class StreamStats(object):
+    """windows / run / batches: the plan's windows, the windows that went through the network and the forward batches of
+    the last frame; frames, frames_unchanged (no window run), total_windows, total_run, total_batches: since the stream
+    was made"""
+
+    def __init__(self):
+        self.windows = self.run = self.batches = 0
+        self.frames = self.frames_unchanged = self.total_windows = self.total_run = self.total_batches = 0
+
+    def _frame(self, windows, run, batches):
+        self.windows, self.run, self.batches = windows, run, batches
+        self.frames += 1
+        self.frames_unchanged += run == 0
+        self.total_windows += windows
+        self.total_run += run
+        self.total_batches += batches
+
+
+class YUV420Stream(object):
+    """TiledUpscaler.upscale_yuv420 for the consecutive frames of one video, with exact reuse of unchanged windows.
+
+    upscale(y, u, v) takes a frame as upscale_yuv420 does and returns the upscaled planes (Y, U, V) on the GPU, equal to
+    upscale_yuv420's bit for bit.  THE RETURNED PLANES ARE THE STREAM'S OWN BUFFERS: they are valid until the next call
+    of upscale() and are overwritten by it; copy them if they must outlive it.
+
+    The stream keeps the previous input planes, the output planes and the plan's tables on the GPU.  Per frame:
+    ofasr_window_diff_yuv420 flags the windows whose support (video.window_support) differs from the previous frame's,
+    ofasr_window_compact gathers their table rows, the host reads their number m (one 8-byte read-back, the only
+    synchronisation the stream adds), and ceil(m / B) batches run gather -> network (or self-ensemble) -> scatter into the
+    persistent output planes, where the cores of unchanged windows keep their bytes.  B is the batch size of the full
+    plan, whatever m is: every forward has the shape of the non-reuse path and replays the same captured graph, which
+    is what makes the result bit-equal (a batch of fewer windows would be another graph, free to pick other kernels).
+    Skipping is therefore per batch of B windows of changed content; a smaller `batch` or `core` of the upscaler skips
+    more finely and pays for it with more launches or a larger plan.overhead() (window pixels per core pixel).
+
+    The first frame, a frame of another size and the frame after reset() run every window.  The comparison is exact: it
+    pays off on content that repeats bit for bit and does nothing for camera noise."""
+
+    def __init__(self, upscaler, matrix="bt601", full_range=False):
+        ops.yuv_table(matrix, full_range, False)       # refuses an unknown matrix now rather than at the first frame
+        self.up = upscaler
+        self.matrix, self.full_range = matrix, full_range
+        self.stats = StreamStats()
+        self._size = None
+        self._fresh = self._all = True
+        self._plan = None
+
+    def reset(self):
+        """forget the previous frame: the next one runs every window"""
+        self._fresh = True
+
+    def _setup(self, H, W, dev):
+        up = self.up
+        s = up.scale
+        plan = up.plan(H, W)
+        if len(plan) > MAX_WINDOWS:
+            raise ValueError("a %dx%d frame makes %d windows with core %d; a stream takes at most %d: use a larger core"
+                             % (W, H, len(plan), up.core, MAX_WINDOWS))
+        self._plan = plan
+        _, self._B = up._batching(plan)
+        self._origins, self._table = up._tables(plan, dev)
+        self._max_eh = max(w[4] for w in plan.windows) * s
+        self._max_ew = max(w[5] for w in plan.windows) * s
+        self._prev = (torch.empty(H, W, dtype=torch.uint8, device=dev),
+                      torch.empty(H // 2, W // 2, dtype=torch.uint8, device=dev),
+                      torch.empty(H // 2, W // 2, dtype=torch.uint8, device=dev))
+        self._out = (torch.empty(H * s, W * s, dtype=torch.uint8, device=dev),
+                     torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev),
+                     torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev))
+        n = len(plan)
+        self._flags = torch.zeros(n, window_diff_slabs(plan.win_h, plan.win_w), dtype=torch.int32, device=dev)
+        self._compact = (torch.zeros(self._origins.size(0), 2, dtype=torch.int64, device=dev),
+                         torch.zeros(n, 6, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+                         torch.zeros(1, dtype=torch.int64, device=dev))
+        self._size = (H, W, dev)
+        self._fresh = True
+
+    def changed_windows(self):
+        """plan indices of the windows the last frame ran, in plan order (a read-back; for tests and diagnostics)"""
+        if self._plan is None:
+            return []
+        if self._all:
+            return list(range(len(self._plan)))
+        return self._compact[2][:self.stats.run].tolist()
+
+    def upscale(self, y, u, v):
+        """one frame -> the upscaled planes (Y, U, V): the stream's own buffers, valid until the next call"""
+        up = self.up
+        dev, (y, u, v), H, W = up._yuv420_frame(y, u, v)
+        if self._size != (H, W, dev):
+            self._setup(H, W, dev)
+        plan, B, n = self._plan, self._B, len(self._plan)
+        out = self._out
+
+        def sink(t, real, table, wins, plan):
+            tile_scatter_yuv420(t.contiguous(), table, out[0], out[1], out[2], self._max_eh, self._max_ew, self.matrix,
+                                self.full_range)
+
+        def gather(origins, h, w):
+            return tile_gather_yuv420(y, u, v, origins, h, w, up.dtype, self.matrix, self.full_range)
+
+        self._all = self._fresh
+        self._fresh = True                             # until this frame is complete: a failed frame leaves nothing to reuse
+        if self._all:
+            m = n
+            up._run_batches(plan, self._origins, self._table, n, B, sink, gather)
+        else:
+            window_diff_yuv420(y, u, v, self._prev[0], self._prev[1], self._prev[2], self._origins[:n], plan.win_h,
+                               plan.win_w, self._flags)
+            c_origins, c_table, _, count = window_compact(self._flags, self._origins[:n], self._table, B, self._compact)
+            m = int(count.item())                      # the stream's one synchronisation per frame
+            up._run_batches(plan, c_origins, c_table, m, B, sink, gather)
+        for dst, src in zip(self._prev, (y, u, v)):
+            dst.copy_(src)                             # stream-ordered behind the kernels that read both
+        self._fresh = False
+        self.stats._frame(n, m, -(-m // B))
         return out

@@ -1,5 +1,7 @@
 """Raw 8-bit YUV 4:2:0 video for the upscaling path: the host definition of the colour conversion that the HIP kernels of
-csrc/yuv.hip implement, and streaming readers / writers for Y4M (YUV4MPEG2) and headerless `yuv420p` files.
+csrc/yuv.hip implement, the host definition of "this window's input changed between two frames" that csrc/reuse.hip
+implements (window_support / changed_windows_host), and streaming readers / writers for Y4M (YUV4MPEG2) and headerless
+`yuv420p` files.
 
 numpy only: nothing here touches the GPU, and importing this module loads no GPU code.
 
@@ -124,6 +126,38 @@ def rgb_to_yuv420_host(rgb, matrix="bt601", full_range=False):
         return np.clip(((s + (1 << (S + 1))) >> (S + 2)) + 128, 0, 255).astype(np.uint8)
 
     return y, box(e.ur, e.ug, e.ub), box(e.vr, e.vg, e.vb)
+
+
+# ---------------------------------------------------------------------------------------------- window reuse
+def window_support(y0, x0, h, w, H, W):
+    """((luma row 0, row 1, col 0, col 1), (chroma row 0, row 1, col 0, col 1)), all bounds inclusive: the samples of an
+    H x W frame that the decode of the h x w window at (y0, x0) depends on -- what ofasr_tile_gather_yuv420 reads for
+    it.  The origin is clamped into the frame as the gather clamps it.  Luma is the window itself; a chroma row enters
+    through pixel rows y0 .. y0 + h - 1 as cy0 = y >> 1 or as its neighbour tap (cy0 - 1 for even y, cy0 + 1 for odd y,
+    clamped into the plane), which together are rows max(0, (y0 - 1) >> 1) .. min(H/2 - 1, (y0 + h) >> 1); columns alike."""
+    y0, x0 = min(max(int(y0), 0), H - h), min(max(int(x0), 0), W - w)
+    luma = (y0, y0 + h - 1, x0, x0 + w - 1)
+    chroma = (max(0, (y0 - 1) >> 1), min(H // 2 - 1, (y0 + h) >> 1), max(0, (x0 - 1) >> 1), min(W // 2 - 1, (x0 + w) >> 1))
+    return luma, chroma
+
+
+def changed_windows_host(prev, cur, origins, h, w):
+    """prev, cur: (y, u, v) planes of two equally sized frames; origins: [(y0, x0)] of h x w windows -> a bool array, one
+    per window: True iff any byte of the window's support (window_support) differs between the two frames, in y, u or v.
+    The definition of ofasr_window_diff_yuv420."""
+    prev, cur = _planes(*prev), _planes(*cur)
+    if prev[0].shape != cur[0].shape:
+        raise ValueError("the two frames differ in size: %s and %s" % (prev[0].shape, cur[0].shape))
+    H, W = cur[0].shape
+    if not (0 < h <= H and 0 < w <= W):
+        raise ValueError("window %dx%d does not fit the %dx%d frame" % (w, h, W, H))
+    diff = [a != b for a, b in zip(prev, cur)]
+    out = np.zeros(len(origins), dtype=bool)
+    for i, (y0, x0) in enumerate(origins):
+        (r0, r1, c0, c1), (s0, s1, d0, d1) = window_support(y0, x0, h, w, H, W)
+        out[i] = diff[0][r0:r1 + 1, c0:c1 + 1].any() or diff[1][s0:s1 + 1, d0:d1 + 1].any() or \
+            diff[2][s0:s1 + 1, d0:d1 + 1].any()
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- files

@@ -7,13 +7,22 @@ S4 sub-network in fp32 and bf16, random he_fout weights, graphed, default core a
   (c) network   the forwards of the same batches alone (graph replays on a gathered batch, no tile move)
 Each is timed with a pair of events around --reps runs after one warm-up run.  Prints one JSON line (ms per frame, frames/s
 of (a) and (b), and the peak memory each of (a) and (b) adds over the resident network).
-usage: python tools/bench_video.py [--size 1080 1920] [--reps 3] [--precs f32 bf16]"""
+
+--reuse FRACTION [FRACTION ...] measures window reuse between frames (upscale.YUV420Stream) instead: a synthetic clip of
+two alternating frames that differ in one luma sample at the core centre of every window that is to change, the rest of
+the windows static (about FRACTION of the plan; with small cores a centre can lie in a neighbour's halo too, so the
+fraction of windows that really ran is reported beside the one asked for).  Per fraction: wall-clock frames/s over --reps
+frames of per-frame upscale_yuv420 and of the stream on the same clip in the same process, and once per precision the
+cost of what the stream adds to a frame where nothing is skipped: diff + compaction + the count's read-back, timed alone.
+usage: python tools/bench_video.py [--size 1080 1920] [--reps 3] [--precs f32 bf16] [--reuse 0 0.5 0.9 1.0] [--core N]
+       [--batch N]"""
 import argparse
 import importlib
 import json
 import os
 import random
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -49,11 +58,79 @@ def peak_extra_mb(fn):
     return round(peak / 2 ** 20, 1)
 
 
+def wall_ms(fn, reps):
+    """ms per call by the host's clock: one warm-up call, then `reps` calls and a synchronisation"""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / reps
+
+
+def bench_reuse(up, tu, planes, fractions, reps):
+    """frames/s with and without reuse on two alternating frames, per fraction of static windows"""
+    import torch
+    y, u, v = planes
+    H, W = y.shape
+    plan = tu.plan(H, W)
+    n = len(plan)
+    _, B = tu._batching(plan)
+    rec = {"windows": n, "window": [plan.win_h, plan.win_w], "batch": B, "overhead": round(plan.overhead(), 3), "fractions": {}}
+    stream = tu.yuv420_stream()
+    for frac in fractions:
+        moving = plan.windows[:n - int(round(frac * n))]
+        other = y.clone()
+        for (_, _, cy, cx, ch, cw) in moving:
+            other[cy + ch // 2, cx + cw // 2] ^= 0x40
+        clip = [(y, u, v), (other, u, v)]
+        state = {"i": 0, "run": 0, "frames": 0}
+
+        def plain():
+            state["i"] ^= 1
+            return tu.upscale_yuv420(*clip[state["i"]])
+
+        def reuse():
+            state["i"] ^= 1
+            out = stream.upscale(*clip[state["i"]])
+            state["run"] += stream.stats.run
+            state["frames"] += 1
+            return out
+
+        stream.reset()
+        ms_plain = wall_ms(plain, reps)
+        reuse()                                            # the stream's first frame runs every window: not part of the clip
+        state.update(run=0, frames=0)
+        ms_reuse = wall_ms(reuse, reps)
+        rec["fractions"]["%g" % frac] = {
+            "static_asked": frac, "windows_run_per_frame": round(state["run"] / state["frames"], 2),
+            "static_measured": round(1.0 - state["run"] / float(state["frames"] * n), 4),
+            "ms": {"plain": round(ms_plain, 3), "reuse": round(ms_reuse, 3)},
+            "frames_per_s": {"plain": round(1e3 / ms_plain, 3), "reuse": round(1e3 / ms_reuse, 3)}}
+    # what a frame pays when nothing is skipped: the two kernels and the read-back of the count, alone
+    origins, table = tu._tables(plan, y.device)
+    flags = up.window_diff_yuv420(y, u, v, y, u, v, origins[:n], plan.win_h, plan.win_w)
+    bufs = up.window_compact(flags, origins[:n], table, B)
+
+    def price():
+        up.window_diff_yuv420(y, u, v, other, u, v, origins[:n], plan.win_h, plan.win_w, flags)
+        return int(up.window_compact(flags, origins[:n], table, B, bufs)[3].item())
+
+    rec["diff_compact_readback_ms"] = round(wall_ms(price, max(reps, 20)), 4)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, nargs=2, default=[1080, 1920], metavar=("H", "W"))
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--precs", nargs="+", default=["f32", "bf16"])
+    ap.add_argument("--reuse", type=float, nargs="+", default=None, metavar="FRACTION",
+                    help="measure window reuse with this fraction of static windows instead (several: one run each)")
+    ap.add_argument("--core", type=int, default=None)
+    ap.add_argument("--batch", type=int, default=None)
     a = ap.parse_args()
     import torch
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
@@ -72,8 +149,17 @@ def main():
     net = net.cuda().eval()
     out = {"size": [H, W], "reps": a.reps, "runs": {}}
     for prec in a.precs:
-        tu = up.TiledUpscaler(net, mix_prec=prec)
+        tu = up.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=prec)
         plan = tu.plan(H, W)
+        if a.reuse is not None:
+            if any(not 0.0 <= f <= 1.0 for f in a.reuse):
+                raise SystemExit("--reuse takes fractions in 0 .. 1")
+            rec = bench_reuse(up, tu, (y, u, v), a.reuse, a.reps)
+            out["runs"]["max_" + prec] = rec
+            print(prec, rec, file=sys.stderr, flush=True)
+            del tu
+            torch.cuda.empty_cache()
+            continue
 
         def fused():
             return tu.upscale_yuv420(y, u, v)

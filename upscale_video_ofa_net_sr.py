@@ -11,6 +11,10 @@ otherwise.  An untagged yuv420p file means bt601 / limited range, the default.  
 --dump-png DIR also writes each output frame as DIR/frame_%06d.png (decoded by the whole-frame HIP kernel).
 --reference REF scores every output frame against the equally sized frame of REF: PSNR of the Y, U and V planes from the
 exact integer squared error, per frame and as the mean, printed and written to <OUT>.quality.json.
+--reuse-static re-runs only the windows whose input bytes changed since the previous frame (upscale.YUV420Stream): the
+output file is byte-identical, static content (screen recordings, animation, letterbox bars, repeated frames, a codec's
+skip blocks) costs a byte comparison instead of the network, and noisy camera material gains nothing.  A smaller --batch
+or --core skips more finely.  The summary then also says how many windows ran.
 Prints frames per second and output megapixels per second at the end."""
 import argparse
 import concurrent.futures
@@ -59,6 +63,8 @@ def parse_args(argv=None):
     ap.add_argument("--core", type=int, default=None, help="core tile side in input pixels")
     ap.add_argument("--batch", type=int, default=None, help="windows per forward call")
     ap.add_argument("--self-ensemble", type=int, default=1, choices=[1, 2, 4, 8], metavar="K")
+    ap.add_argument("--reuse-static", action="store_true",
+                    help="keep the output of windows whose input did not change since the previous frame (same output)")
     ap.add_argument("--dump-png", default=None, metavar="DIR", help="also write every output frame as a PNG")
     ap.add_argument("--reference", default=None, metavar="REF", help="ground-truth video of the output's size: PSNR")
     ap.add_argument("input", metavar="INPUT", help="*.y4m, or a headerless yuv420p file (then --size is required)")
@@ -94,6 +100,7 @@ def main(argv=None):
     up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble)
     s = up.scale
     OW, OH = W * s, H * s
+    stream = up.yuv420_stream(matrix=a.matrix, full_range=full) if a.reuse_static else None
     print("%s x%d: %dx%d -> %dx%d, %s %s, receptive radius %d px, halo %d, core %d, %s%s" % (
         net.name(), s, W, H, OW, OH, a.matrix, a.range, up.radius, up.halo, up.core, a.mix_prec,
         "" if a.self_ensemble == 1 else ", self-ensemble x%d" % a.self_ensemble))
@@ -155,7 +162,10 @@ def main(argv=None):
             torch.cuda.current_stream().synchronize()     # the pinned slot is free again once the upload has finished
             nxt = rd.submit(read, (done + 1) % SLOTS) if want is None or done + 1 < want else None
             y, u, v = video.split_frame(dev_in, W, H)
-            Y, U, V = up.upscale_yuv420(y, u, v, matrix=a.matrix, full_range=full)
+            if stream is not None:
+                Y, U, V = stream.upscale(y, u, v)          # the stream's own planes: copied out before the next frame
+            else:
+                Y, U, V = up.upscale_yuv420(y, u, v, matrix=a.matrix, full_range=full)
             if writes[slot] is not None:
                 writes[slot].result()                      # the output slot's previous frame is on disk
             dst = video.split_frame(pin_out[slot], OW, OH)
@@ -199,6 +209,10 @@ def main(argv=None):
                        "frames": scores, "mean": mean}, fh, indent=1)
     mp = done * OW * OH / 1e6
     print("%d frames, %.2f output MP in %.3f s: %.2f frames/s, %.2f MP/s" % (done, mp, dt, done / dt, mp / dt))
+    if stream is not None:
+        st = stream.stats
+        print("windows run %d of %d (%.1f %%), %d frames unchanged" % (
+            st.total_run, st.total_windows, 100.0 * st.total_run / max(st.total_windows, 1), st.frames_unchanged))
 
 
 if __name__ == "__main__":
