@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 308 /* + ofasr_window_diff_slabs, ofasr_window_diff_yuv420, ofasr_window_compact */
+#define OFASR_VERSION 309 /* + ofasr_tile_gather_yuv420p16, ofasr_tile_scatter_yuv420p16, ofasr_window_diff_yuv420p16 */
 
 typedef enum {
     OFASR_OK = 0,
@@ -454,6 +454,24 @@ int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, int64_t sw, in
  * window larger than the frame, an extent bound larger than the source window, a bad dtype, a table whose yo is outside
  * 0 .. 255 or whose coefficients exceed 2^16 in magnitude (beyond it int32 could overflow).  OFASR_ERR_UNSUPPORTED:
  * n > 65535 or more than 2^40 pixels.
+ *
+ * 16-bit planes, depth 10 (host statement: the same functions of video.py with depth=10).  A frame is three contiguous
+ * uint16 planes of the same shapes, a sample in the low 10 bits of a word in host byte order; a stored sample s is read
+ * as min(s, 1023), the top six bits are not trusted.  The definition is the one above with 1023 for 255 (both clamps)
+ * and 512 for 128, on the tables of depth 10 (video.yuv_coeffs(matrix, full_range, 10): limited range yo = 64 and the
+ * scales 1023/876, 1023/896; the same 14 fractional bits, so every sum stays below 6.8e7 in magnitude and the largest
+ * coefficient is 34711: the refusal of tables beyond 2^16 holds unchanged).
+ *   ofasr_tile_gather_yuv420p16: ofasr_tile_gather_yuv420 on such planes,
+ *             out[n,c,r,x] = (dtype)(RGB10_c(y0+r, x0+x) / 1023.0f)
+ *     (an fp32 division, then one round-to-nearest-even cast).  A luma row of a 2 x 4 block is one 8-byte load where its
+ *     address is 8-byte aligned and the block is whole, samples one by one elsewhere; chroma by 16-bit loads at clamped
+ *     indices.
+ *   ofasr_tile_scatter_yuv420p16: ofasr_tile_scatter_yuv420 into such planes; the source values are quantised as
+ *     round_half_even(clamp(v, 0, 1) * 1023) in fp32.  Every stored word is <= 1023; words outside every extent are not
+ *     written.  8-byte luma stores and one 32-bit store per chroma plane where aligned and whole, samples elsewhere.
+ * `depth` must be 10 and the plane pointers 2-byte aligned (OFASR_ERR_INVALID_ARG otherwise); every other refusal and
+ * guarantee is the 8-bit twin's.  The input and output depths of an upscale are independent: the 8-bit gather feeds
+ * the 16-bit scatter as well as its own.
  * ------------------------------------------------------------------------------------------- */
 int ofasr_yuv420_to_rgb_u8(const void* y, const void* u, const void* v, int64_t H, int64_t W, const int32_t* coeffs,
                            void* rgb_hwc, void* stream);
@@ -464,6 +482,12 @@ int ofasr_tile_gather_yuv420(const void* y, const void* u, const void* v, int64_
 int ofasr_tile_scatter_yuv420(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
                               const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW, int64_t max_eh,
                               int64_t max_ew, void* stream);
+int ofasr_tile_gather_yuv420p16(const void* y, const void* u, const void* v, int64_t H, int64_t W, int depth,
+                                const int32_t* coeffs, const int64_t* origins, int64_t n, int64_t h, int64_t w, void* out,
+                                int dtype, void* stream);
+int ofasr_tile_scatter_yuv420p16(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
+                                 int depth, const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW,
+                                 int64_t max_eh, int64_t max_ew, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Window reuse between video frames (csrc/reuse.hip; host statement: video.py window_support / changed_windows_host) --
@@ -480,6 +504,11 @@ int ofasr_tile_scatter_yuv420(const void* src, int64_t n, int64_t sh, int64_t sw
  *     differs between the two frames in y, u or v, else 0.  Window n is changed iff any of its S flags is set.  Every
  *     flag is written by every call.  Odd origins and odd h, w are fine; any byte-aligned plane pointers (16-byte loads
  *     only where both planes' addresses are aligned for them, bytes elsewhere).
+ *   ofasr_window_diff_yuv420p16: the same on 16-bit planes (uint16, as ofasr_tile_gather_yuv420p16 takes them; `depth`
+ *     must be 10 and the six pointers 2-byte aligned, OFASR_ERR_INVALID_ARG otherwise).  The support is the same in
+ *     samples, S and the flag layout are the same.  The stored words are compared as they are, the bits above the tenth
+ *     included: that flags no fewer windows than comparing min(s, 1023) would, and the same bytes in still give the same
+ *     bytes out.
  *   ofasr_window_compact: ONE workgroup.  From flags [n][slabs], the plan's origins [n][2] and scatter table [n][6]
  *     (device int64) and the batch size `batch`, with m the number of changed windows and i_0 < i_1 < ... < i_{m-1} their
  *     indices (stable, plan order):
@@ -497,6 +526,9 @@ int64_t ofasr_window_diff_slabs(int64_t h, int64_t w);
 int ofasr_window_diff_yuv420(const void* y, const void* u, const void* v, const void* py, const void* pu, const void* pv,
                              int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h, int64_t w, int32_t* flags,
                              void* stream);
+int ofasr_window_diff_yuv420p16(const void* y, const void* u, const void* v, const void* py, const void* pu, const void* pv,
+                                int64_t H, int64_t W, int depth, const int64_t* origins, int64_t n, int64_t h, int64_t w,
+                                int32_t* flags, void* stream);
 int ofasr_window_compact(const int32_t* flags, int64_t slabs, const int64_t* origins, const int64_t* table, int64_t n,
                          int64_t batch, int64_t* out_origins, int64_t* out_table, int64_t* out_index, int64_t* count,
                          void* stream);

@@ -128,9 +128,15 @@ SIGNATURES = {
                                           _c_int, _c_vp]),
     "ofasr_tile_scatter_yuv420": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64,
                                            _c_i64, _c_i64, _c_i64, _c_vp]),
+    "ofasr_tile_gather_yuv420p16": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
+                                             _c_vp, _c_int, _c_vp]),
+    "ofasr_tile_scatter_yuv420p16": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
+                                              _c_i64, _c_i64, _c_i64, _c_i64, _c_vp]),
     "ofasr_window_diff_slabs": (_c_i64, [_c_i64, _c_i64]),
     "ofasr_window_diff_yuv420": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64,
                                           _c_vp, _c_vp]),
+    "ofasr_window_diff_yuv420p16": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_i64,
+                                             _c_i64, _c_i64, _c_vp, _c_vp]),
     "ofasr_window_compact": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ofasr_d4_apply": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp]),
     "ofasr_d4_accumulate": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, ctypes.c_float,

@@ -13,6 +13,9 @@
 //          dwordx4 loads when the two planes' addresses are both 16-byte aligned there, every other chunk goes byte by
 //          byte.  A lane touches memory only inside `if (in range)`: there is no load from a masked lane, so no address
 //          needs a clamp beyond the origin's.  64-bit addressing.
+//          16-bit planes (ofasr_window_diff_yuv420p16): the same kernel with BPS = 2 bytes per sample.  The support is the
+//          same in samples; the rectangles are compared as bytes, pitch, first column and width doubled, so the stored
+//          words are compared as they are (bits above the tenth included) and a word is never split across two flags.
 // compact: ONE workgroup.  Per round of 256 windows: fold the S slab flags, ballot + popcount inside the wave, the four
 //          wave totals through LDS; the changed windows' rows go out in plan order.
 #include "ofasr_common.h"
@@ -59,6 +62,7 @@ __device__ __forceinline__ void reuse_slab_rows(long long nrows, long long s, lo
     hi = lo + per < nrows ? lo + per : nrows;
 }
 
+template <int BPS>                                    // bytes per sample: 1, or 2 for the 16-bit planes
 __global__ void __launch_bounds__(REUSE_THREADS) window_diff_yuv420_kernel(
     const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up, const uint8_t* __restrict__ vp,
     const uint8_t* __restrict__ pyp, const uint8_t* __restrict__ pup, const uint8_t* __restrict__ pvp, long long H, long long W,
@@ -70,10 +74,10 @@ __global__ void __launch_bounds__(REUSE_THREADS) window_diff_yuv420_kernel(
     const long long cc0 = reuse_clampll((x0 - 1) >> 1, 0, CW - 1), cc1 = reuse_clampll((x0 + w) >> 1, 0, CW - 1);
     long long lo, hi;
     reuse_slab_rows(h, s, S, lo, hi);
-    unsigned d = reuse_rect_diff(yp, pyp, W, y0 + lo, y0 + hi, x0, w);
+    unsigned d = reuse_rect_diff(yp, pyp, W * BPS, y0 + lo, y0 + hi, x0 * BPS, w * BPS);
     reuse_slab_rows(cr1 - cr0 + 1, s, S, lo, hi);
-    d |= reuse_rect_diff(up, pup, CW, cr0 + lo, cr0 + hi, cc0, cc1 - cc0 + 1);
-    d |= reuse_rect_diff(vp, pvp, CW, cr0 + lo, cr0 + hi, cc0, cc1 - cc0 + 1);
+    d |= reuse_rect_diff(up, pup, CW * BPS, cr0 + lo, cr0 + hi, cc0 * BPS, (cc1 - cc0 + 1) * BPS);
+    d |= reuse_rect_diff(vp, pvp, CW * BPS, cr0 + lo, cr0 + hi, cc0 * BPS, (cc1 - cc0 + 1) * BPS);
     const int any = __syncthreads_or(d != 0);
     if (threadIdx.x == 0) flags[n * S + s] = any ? 1 : 0;
 }
@@ -137,10 +141,10 @@ using namespace ofasr;
 
 OFASR_EXPORT int64_t ofasr_window_diff_slabs(int64_t h, int64_t w) { return reuse_slabs(h, w); }
 
-OFASR_EXPORT int ofasr_window_diff_yuv420(const void* y, const void* u, const void* v, const void* py, const void* pu,
-                                          const void* pv, int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h,
-                                          int64_t w, int32_t* flags, void* stream) {
-    const char* name = "ofasr_window_diff_yuv420";
+template <int BPS>
+static int reuse_window_diff(const char* name, const void* y, const void* u, const void* v, const void* py, const void* pu,
+                             const void* pv, int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h, int64_t w,
+                             int32_t* flags, void* stream) {
     OFASR_REQUIRE(y && u && v && py && pu && pv && origins && flags, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
     OFASR_REQUIRE(H >= 2 && W >= 2, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
@@ -151,12 +155,29 @@ OFASR_EXPORT int ofasr_window_diff_yuv420(const void* y, const void* u, const vo
                   (long long)h, (long long)w, (long long)H, (long long)W);
     OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
     const int64_t S = reuse_slabs(h, w);
-    prof_note((double)n * (double)(h * w) * 3.0, 0.0);
-    OFASR_LAUNCH(window_diff_yuv420_kernel, dim3((unsigned)S, (unsigned)n), dim3(REUSE_THREADS), 0, as_stream(stream),
+    prof_note((double)n * (double)(h * w) * 3.0 * BPS, 0.0);
+    OFASR_LAUNCH(window_diff_yuv420_kernel<BPS>, dim3((unsigned)S, (unsigned)n), dim3(REUSE_THREADS), 0, as_stream(stream),
                  (const uint8_t*)y, (const uint8_t*)u, (const uint8_t*)v, (const uint8_t*)py, (const uint8_t*)pu,
                  (const uint8_t*)pv, (long long)H, (long long)W, (const long long*)origins, (long long)h, (long long)w,
                  (int*)flags);
     return check_launch(name);
+}
+
+OFASR_EXPORT int ofasr_window_diff_yuv420(const void* y, const void* u, const void* v, const void* py, const void* pu,
+                                          const void* pv, int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h,
+                                          int64_t w, int32_t* flags, void* stream) {
+    return reuse_window_diff<1>("ofasr_window_diff_yuv420", y, u, v, py, pu, pv, H, W, origins, n, h, w, flags, stream);
+}
+
+OFASR_EXPORT int ofasr_window_diff_yuv420p16(const void* y, const void* u, const void* v, const void* py, const void* pu,
+                                             const void* pv, int64_t H, int64_t W, int depth, const int64_t* origins, int64_t n,
+                                             int64_t h, int64_t w, int32_t* flags, void* stream) {
+    const char* name = "ofasr_window_diff_yuv420p16";
+    OFASR_REQUIRE(depth == 10, OFASR_ERR_INVALID_ARG, "%s: depth %d is not supported (10 only)", name, depth);
+    uintptr_t bits = 0;
+    for (const void* p : {y, u, v, py, pu, pv}) bits |= reinterpret_cast<uintptr_t>(p);
+    OFASR_REQUIRE((bits & 1) == 0, OFASR_ERR_INVALID_ARG, "%s: a 16-bit plane pointer is not 2-byte aligned", name);
+    return reuse_window_diff<2>(name, y, u, v, py, pu, pv, H, W, origins, n, h, w, flags, stream);
 }
 
 OFASR_EXPORT int ofasr_window_compact(const int32_t* flags, int64_t slabs, const int64_t* origins, const int64_t* table,

@@ -21,6 +21,13 @@
 // plane.  The wide accesses are taken only where the address is aligned for them and the block is whole; blocks cut by
 // the frame's or an extent's edge and unaligned rows go byte by byte (element by element on the tile side).  A window
 // with an odd origin is gathered as the even-aligned superset of the window, the pixels outside it masked.
+//
+// 16-bit planes (ofasr_tile_gather_yuv420p16 / ofasr_tile_scatter_yuv420p16, depth 10).  The same kernels on the sample
+// type uint16_t (yuv_px<P>): a sample s is read as min(s, 1023), 512 takes the place of 128 and 1023 that of 255, in the
+// clamps, in the gather's division and in the scatter's quantisation; the caller's tables are the ones of depth 10.  The
+// widths double in bytes and stay the same in samples: a luma row of a block is one 8-byte access, a chroma pair one
+// 32-bit store, under the same conditions (address aligned for it, block whole), samples one by one elsewhere.  Every
+// stored word is <= 1023.  The 8-bit instantiations are what they were before the sample type became a parameter.
 #include "ofasr_common.h"
 
 namespace ofasr {
@@ -28,14 +35,45 @@ namespace ofasr {
 struct YuvDec { int yo, cy, rv, gu, gv, bu; };
 struct YuvEnc { int yo, yr, yg, yb, ur, ug, ub, vr, vg, vb; };
 
-__device__ __forceinline__ int yuv_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+// the sample type of a plane: its largest value, the chroma midpoint, how a stored sample is read, and the wide accesses
+// (four luma samples of a row, two chroma samples), which the callers take at addresses aligned for them only
+template <typename P> struct yuv_px;
+template <> struct yuv_px<uint8_t> {
+    static constexpr int maxv = 255, mid = 128;
+    static __device__ __forceinline__ int sample(uint8_t s) { return s; }
+    static __device__ __forceinline__ void load4(const uint8_t* p, int* o) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = (int)((w >> (8 * k)) & 0xffu);
+    }
+    static __device__ __forceinline__ void store4(uint8_t* p, const int* Y) {
+        *reinterpret_cast<uint32_t*>(p) = (uint32_t)Y[0] | (uint32_t)Y[1] << 8 | (uint32_t)Y[2] << 16 | (uint32_t)Y[3] << 24;
+    }
+    static __device__ __forceinline__ void store2(uint8_t* p, int a, int b) { *reinterpret_cast<uint16_t*>(p) = (uint16_t)(a | b << 8); }
+};
+template <> struct yuv_px<uint16_t> {
+    static constexpr int maxv = 1023, mid = 512;
+    static __device__ __forceinline__ int sample(unsigned s) { return (int)(s < 1023u ? s : 1023u); }   // the top six bits are not trusted
+    static __device__ __forceinline__ void load4(const uint16_t* p, int* o) {
+        const uint2 w = *reinterpret_cast<const uint2*>(p);
+        o[0] = sample(w.x & 0xffffu), o[1] = sample(w.x >> 16), o[2] = sample(w.y & 0xffffu), o[3] = sample(w.y >> 16);
+    }
+    static __device__ __forceinline__ void store4(uint16_t* p, const int* Y) {
+        *reinterpret_cast<uint2*>(p) = make_uint2((uint32_t)Y[0] | (uint32_t)Y[1] << 16, (uint32_t)Y[2] | (uint32_t)Y[3] << 16);
+    }
+    static __device__ __forceinline__ void store2(uint16_t* p, int a, int b) { *reinterpret_cast<uint32_t*>(p) = (uint32_t)a | (uint32_t)b << 16; }
+};
+
+template <typename P> __device__ __forceinline__ int yuv_clampv(int v) { return v < 0 ? 0 : (v > yuv_px<P>::maxv ? yuv_px<P>::maxv : v); }
 __device__ __forceinline__ long long yuv_clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // RGB of the 2 x 4 block whose corner is the even frame position (by, bx): rgb[row][col][c].  Columns at or past W
 // repeat column W - 1 (the caller masks them); by + 1 < H since H is even.
-__device__ __forceinline__ void yuv_decode_block(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
-                                                 const uint8_t* __restrict__ vp, long long H, long long W, long long by,
-                                                 long long bx, const YuvDec& D, int (&rgb)[2][4][3]) {
+template <typename P>
+__device__ __forceinline__ void yuv_decode_block(const P* __restrict__ yp, const P* __restrict__ up, const P* __restrict__ vp,
+                                                 long long H, long long W, long long by, long long bx, const YuvDec& D,
+                                                 int (&rgb)[2][4][3]) {
+    typedef yuv_px<P> px;
     const long long CH = H >> 1, CW = W >> 1;
     const long long cy = by >> 1, cx = bx >> 1;
     long long rows[3], cols[4];
@@ -48,20 +86,18 @@ __device__ __forceinline__ void yuv_decode_block(const uint8_t* __restrict__ yp,
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            cu[i][j] = up[rows[i] + cols[j]];
-            cv[i][j] = vp[rows[i] + cols[j]];
+            cu[i][j] = px::sample(up[rows[i] + cols[j]]);
+            cv[i][j] = px::sample(vp[rows[i] + cols[j]]);
         }
     int Y[2][4];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        const uint8_t* p = yp + (by + r) * W + bx;
-        if ((reinterpret_cast<uintptr_t>(p) & 3) == 0 && bx + 4 <= W) {
-            const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) Y[r][k] = (int)((w >> (8 * k)) & 0xffu);
+        const P* p = yp + (by + r) * W + bx;
+        if ((reinterpret_cast<uintptr_t>(p) & (4 * sizeof(P) - 1)) == 0 && bx + 4 <= W) {
+            px::load4(p, Y[r]);
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) Y[r][k] = p[bx + k < W ? k : (int)(W - 1 - bx)];
+            for (int k = 0; k < 4; ++k) Y[r][k] = px::sample(p[bx + k < W ? k : (int)(W - 1 - bx)]);
         }
     }
 #pragma unroll
@@ -71,24 +107,25 @@ __device__ __forceinline__ void yuv_decode_block(const uint8_t* __restrict__ yp,
         for (int k = 0; k < 4; ++k) {
             const int c0 = 1 + (k >> 1);
             const int nc = (k & 1) ? c0 + 1 : c0 - 1;    // left for the even column, right for the odd
-            const int u = ((9 * cu[1][c0] + 3 * cu[1][nc] + 3 * cu[nr][c0] + cu[nr][nc] + 8) >> 4) - 128;
-            const int v = ((9 * cv[1][c0] + 3 * cv[1][nc] + 3 * cv[nr][c0] + cv[nr][nc] + 8) >> 4) - 128;
+            const int u = ((9 * cu[1][c0] + 3 * cu[1][nc] + 3 * cu[nr][c0] + cu[nr][nc] + 8) >> 4) - px::mid;
+            const int v = ((9 * cv[1][c0] + 3 * cv[1][nc] + 3 * cv[nr][c0] + cv[nr][nc] + 8) >> 4) - px::mid;
             const int l = D.cy * (Y[r][k] - D.yo) + (1 << 13);
-            rgb[r][k][0] = yuv_clamp8((l + D.rv * v) >> 14);
-            rgb[r][k][1] = yuv_clamp8((l + D.gu * u + D.gv * v) >> 14);
-            rgb[r][k][2] = yuv_clamp8((l + D.bu * u) >> 14);
+            rgb[r][k][0] = yuv_clampv<P>((l + D.rv * v) >> 14);
+            rgb[r][k][1] = yuv_clampv<P>((l + D.gu * u + D.gv * v) >> 14);
+            rgb[r][k][2] = yuv_clampv<P>((l + D.bu * u) >> 14);
         }
     }
 }
 
 // luma of the 2 x 4 block rgb (columns < valid, valid = 2 or 4) and its one or two chroma pairs
+template <typename P>
 __device__ __forceinline__ void yuv_encode_block(const int (&rgb)[2][4][3], const YuvEnc& E, int (&Y)[2][4], int (&U)[2],
                                                  int (&V)[2]) {
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            Y[r][k] = yuv_clamp8(((E.yr * rgb[r][k][0] + E.yg * rgb[r][k][1] + E.yb * rgb[r][k][2] + (1 << 13)) >> 14) + E.yo);
+            Y[r][k] = yuv_clampv<P>(((E.yr * rgb[r][k][0] + E.yg * rgb[r][k][1] + E.yb * rgb[r][k][2] + (1 << 13)) >> 14) + E.yo);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         int su = 0, sv = 0;
@@ -99,39 +136,40 @@ __device__ __forceinline__ void yuv_encode_block(const int (&rgb)[2][4][3], cons
                 su += E.ur * rgb[r][k][0] + E.ug * rgb[r][k][1] + E.ub * rgb[r][k][2];
                 sv += E.vr * rgb[r][k][0] + E.vg * rgb[r][k][1] + E.vb * rgb[r][k][2];
             }
-        U[j] = yuv_clamp8(((su + (1 << 15)) >> 16) + 128);
-        V[j] = yuv_clamp8(((sv + (1 << 15)) >> 16) + 128);
+        U[j] = yuv_clampv<P>(((su + (1 << 15)) >> 16) + yuv_px<P>::mid);
+        V[j] = yuv_clampv<P>(((sv + (1 << 15)) >> 16) + yuv_px<P>::mid);
     }
 }
 
-// the planes' bytes of one encoded block at the even position (by, bx) of an [OH, OW] frame; valid = 2 or 4 columns
-__device__ __forceinline__ void yuv_store_block(uint8_t* __restrict__ yp, uint8_t* __restrict__ up, uint8_t* __restrict__ vp,
-                                                long long OW, long long by, long long bx, int valid, const int (&Y)[2][4],
-                                                const int (&U)[2], const int (&V)[2]) {
+// the planes' samples of one encoded block at the even position (by, bx) of an [OH, OW] frame; valid = 2 or 4 columns
+template <typename P>
+__device__ __forceinline__ void yuv_store_block(P* __restrict__ yp, P* __restrict__ up, P* __restrict__ vp, long long OW,
+                                                long long by, long long bx, int valid, const int (&Y)[2][4], const int (&U)[2],
+                                                const int (&V)[2]) {
+    typedef yuv_px<P> px;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        uint8_t* p = yp + (by + r) * OW + bx;
-        if ((reinterpret_cast<uintptr_t>(p) & 3) == 0 && valid == 4) {
-            *reinterpret_cast<uint32_t*>(p) = (uint32_t)Y[r][0] | (uint32_t)Y[r][1] << 8 | (uint32_t)Y[r][2] << 16 |
-                                              (uint32_t)Y[r][3] << 24;
+        P* p = yp + (by + r) * OW + bx;
+        if ((reinterpret_cast<uintptr_t>(p) & (4 * sizeof(P) - 1)) == 0 && valid == 4) {
+            px::store4(p, Y[r]);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (k < valid) p[k] = (uint8_t)Y[r][k];
+                if (k < valid) p[k] = (P)Y[r][k];
         }
     }
     const long long co = (by >> 1) * (OW >> 1) + (bx >> 1);
-    uint8_t* pu = up + co;
-    uint8_t* pv = vp + co;
-    if ((reinterpret_cast<uintptr_t>(pu) & 1) == 0 && valid == 4) *reinterpret_cast<uint16_t*>(pu) = (uint16_t)(U[0] | U[1] << 8);
+    P* pu = up + co;
+    P* pv = vp + co;
+    if ((reinterpret_cast<uintptr_t>(pu) & (2 * sizeof(P) - 1)) == 0 && valid == 4) px::store2(pu, U[0], U[1]);
     else {
-        pu[0] = (uint8_t)U[0];
-        if (valid == 4) pu[1] = (uint8_t)U[1];
+        pu[0] = (P)U[0];
+        if (valid == 4) pu[1] = (P)U[1];
     }
-    if ((reinterpret_cast<uintptr_t>(pv) & 1) == 0 && valid == 4) *reinterpret_cast<uint16_t*>(pv) = (uint16_t)(V[0] | V[1] << 8);
+    if ((reinterpret_cast<uintptr_t>(pv) & (2 * sizeof(P) - 1)) == 0 && valid == 4) px::store2(pv, V[0], V[1]);
     else {
-        pv[0] = (uint8_t)V[0];
-        if (valid == 4) pv[1] = (uint8_t)V[1];
+        pv[0] = (P)V[0];
+        if (valid == 4) pv[1] = (P)V[1];
     }
 }
 
@@ -203,7 +241,7 @@ __global__ void __launch_bounds__(256) rgb_to_yuv420_kernel(const uint8_t* __res
             }
         }
         int Y[2][4], U[2], V[2];
-        yuv_encode_block(rgb, E, Y, U, V);
+        yuv_encode_block<uint8_t>(rgb, E, Y, U, V);
         yuv_store_block(yp, up, vp, W, by, bx, valid, Y, U, V);
     }
 }
@@ -237,9 +275,9 @@ template <> __device__ __forceinline__ void yuv_unpack4<f16_t>(uint2 p, float* v
 
 // grid: (x: lanes over (h / 2 + 1) * (w / 4 + 1) blocks of the even-aligned superset of the window, y: window).
 // vec_ok: w % 4 == 0 and `out` aligned for 4-element stores (then a window with an even x0 stores whole rows of a block)
-template <typename T>
-__global__ void __launch_bounds__(256) tile_gather_yuv420_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
-                                                                 const uint8_t* __restrict__ vp, long long H, long long W,
+template <typename T, typename P>
+__global__ void __launch_bounds__(256) tile_gather_yuv420_kernel(const P* __restrict__ yp, const P* __restrict__ up,
+                                                                 const P* __restrict__ vp, long long H, long long W,
                                                                  YuvDec D, const long long* __restrict__ origins, long long h,
                                                                  long long w, T* __restrict__ out, int vec_ok) {
     const long long n = blockIdx.y;
@@ -265,7 +303,7 @@ __global__ void __launch_bounds__(256) tile_gather_yuv420_kernel(const uint8_t* 
             for (int c = 0; c < 3; ++c) {
                 float v[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = __fdiv_rn((float)rgb[r][k][c], 255.0f);
+                for (int k = 0; k < 4; ++k) v[k] = __fdiv_rn((float)rgb[r][k][c], (float)yuv_px<P>::maxv);
                 T* dst = on + c * plane + wr * w + wx;
                 if (vec) {                              // x0 even and w % 4 == 0: wx % 4 == 0 and the block is whole
                     *reinterpret_cast<typename yuv_vec4<T>::type*>(dst) = yuv_pack4<T>(v);
@@ -279,19 +317,19 @@ __global__ void __launch_bounds__(256) tile_gather_yuv420_kernel(const uint8_t* 
     }
 }
 
-__device__ __forceinline__ int yuv_quant(float v) {
+template <typename P> __device__ __forceinline__ int yuv_quant(float v) {
     const float f = fminf(fmaxf(v, 0.0f), 1.0f);
-    return (int)rintf(__fmul_rn(f, 255.0f));
+    return (int)rintf(__fmul_rn(f, (float)yuv_px<P>::maxv));
 }
 
 // table[6 n ..]: sy, sx, dy, dx, eh, ew (dy, dx, eh, ew made even after the clamps).
 // grid: (x: lanes over ceil(max_eh / 2) * ceil(max_ew / 4) blocks, y: window)
-template <typename T>
+template <typename T, typename P>
 __global__ void __launch_bounds__(256) tile_scatter_yuv420_kernel(const T* __restrict__ src, long long sh_, long long sw,
                                                                   const long long* __restrict__ table, YuvEnc E,
-                                                                  uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
-                                                                  uint8_t* __restrict__ vp, long long OH, long long OW,
-                                                                  long long max_eh, long long max_ew) {
+                                                                  P* __restrict__ yp, P* __restrict__ up, P* __restrict__ vp,
+                                                                  long long OH, long long OW, long long max_eh,
+                                                                  long long max_ew) {
     const long long n = blockIdx.y;
     const long long* t = table + 6 * n;
     long long sy = t[0], sx = t[1], dy = t[2], dx = t[3], eh = t[4], ew = t[5];
@@ -330,10 +368,10 @@ __global__ void __launch_bounds__(256) tile_scatter_yuv420_kernel(const T* __res
                     for (int k = 0; k < 4; ++k) v[k] = k < valid ? to_float(s[k]) : 0.0f;
                 }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) rgb[r][k][c] = yuv_quant(v[k]);
+                for (int k = 0; k < 4; ++k) rgb[r][k][c] = yuv_quant<P>(v[k]);
             }
         int Y[2][4], U[2], V[2];
-        yuv_encode_block(rgb, E, Y, U, V);
+        yuv_encode_block<P>(rgb, E, Y, U, V);
         yuv_store_block(yp, up, vp, OW, dy + r0, dx + c0, valid, Y, U, V);
     }
 }
@@ -355,26 +393,25 @@ static bool yuv_coeffs_ok(const int32_t* c, int n) {
     return true;
 }
 
-template <typename T>
+template <typename T, typename P>
 static void yuv_gather(const void* y, const void* u, const void* v, int64_t H, int64_t W, YuvDec D, const int64_t* origins,
                        int64_t n, int64_t h, int64_t w, void* out, hipStream_t st) {
     const size_t al = sizeof(T) == 4 ? 16 : 8;
     const int vec = w % 4 == 0 && reinterpret_cast<uintptr_t>(out) % al == 0;
     const dim3 grid(yuv_blocks((h / 2 + 1) * (w / 4 + 1)), (unsigned)n);
-    prof_note((double)n * (double)(h * w) * (1.5 + 3.0 * sizeof(T)), 0.0);
-    OFASR_LAUNCH((tile_gather_yuv420_kernel<T>), grid, dim3(256), 0, st, (const uint8_t*)y, (const uint8_t*)u,
-                 (const uint8_t*)v, (long long)H, (long long)W, D, (const long long*)origins, (long long)h, (long long)w,
-                 (T*)out, vec);
+    prof_note((double)n * (double)(h * w) * (1.5 * sizeof(P) + 3.0 * sizeof(T)), 0.0);
+    OFASR_LAUNCH((tile_gather_yuv420_kernel<T, P>), grid, dim3(256), 0, st, (const P*)y, (const P*)u, (const P*)v,
+                 (long long)H, (long long)W, D, (const long long*)origins, (long long)h, (long long)w, (T*)out, vec);
 }
 
-template <typename T>
+template <typename T, typename P>
 static void yuv_scatter(const void* src, int64_t n, int64_t sh, int64_t sw, const int64_t* table, YuvEnc E, void* y, void* u,
                         void* v, int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, hipStream_t st) {
     const dim3 grid(yuv_blocks(cdiv(max_eh, 2) * cdiv(max_ew, 4)), (unsigned)n);
-    prof_note((double)n * (double)(max_eh * max_ew) * (1.5 + 3.0 * sizeof(T)), 0.0);
-    OFASR_LAUNCH((tile_scatter_yuv420_kernel<T>), grid, dim3(256), 0, st, (const T*)src, (long long)sh, (long long)sw,
-                 (const long long*)table, E, (uint8_t*)y, (uint8_t*)u, (uint8_t*)v, (long long)OH, (long long)OW,
-                 (long long)max_eh, (long long)max_ew);
+    prof_note((double)n * (double)(max_eh * max_ew) * (1.5 * sizeof(P) + 3.0 * sizeof(T)), 0.0);
+    OFASR_LAUNCH((tile_scatter_yuv420_kernel<T, P>), grid, dim3(256), 0, st, (const T*)src, (long long)sh, (long long)sw,
+                 (const long long*)table, E, (P*)y, (P*)u, (P*)v, (long long)OH, (long long)OW, (long long)max_eh,
+                 (long long)max_ew);
 }
 
 }  // namespace ofasr
@@ -386,6 +423,49 @@ using namespace ofasr;
     OFASR_REQUIRE((H) % 2 == 0 && (W) % 2 == 0, OFASR_ERR_INVALID_ARG, "%s: a 4:2:0 frame needs even sides, got %lldx%lld", \
                   name, (long long)(H), (long long)(W));                                                                 \
     OFASR_REQUIRE((H) <= (1LL << 40) / (W), OFASR_ERR_UNSUPPORTED, "%s: too large a frame", name)
+
+// the checks the tile moves share, whatever the sample type
+template <typename P>
+static int yuv_tile_gather(const char* name, const void* y, const void* u, const void* v, int64_t H, int64_t W,
+                           const int32_t* coeffs, const int64_t* origins, int64_t n, int64_t h, int64_t w, void* out, int dtype,
+                           void* stream) {
+    OFASR_REQUIRE(y && u && v && coeffs && origins && out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE(n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
+    YUV_REQUIRE_FRAME(H, W);
+    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
+                  name);
+    OFASR_REQUIRE(h <= H && w <= W, OFASR_ERR_INVALID_ARG, "%s: window %lldx%lld larger than the frame %lldx%lld", name,
+                  (long long)h, (long long)w, (long long)H, (long long)W);
+    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    hipStream_t st = as_stream(stream);
+    const YuvDec D = yuv_dec(coeffs);
+    if (dtype == OFASR_F32) yuv_gather<float, P>(y, u, v, H, W, D, origins, n, h, w, out, st);
+    else if (dtype == OFASR_BF16) yuv_gather<bf16_t, P>(y, u, v, H, W, D, origins, n, h, w, out, st);
+    else yuv_gather<f16_t, P>(y, u, v, H, W, D, origins, n, h, w, out, st);
+    return check_launch(name);
+}
+
+template <typename P>
+static int yuv_tile_scatter(const char* name, const void* src, int64_t n, int64_t sh, int64_t sw, int dtype,
+                            const int64_t* table, const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW,
+                            int64_t max_eh, int64_t max_ew, void* stream) {
+    OFASR_REQUIRE(src && table && coeffs && y && u && v, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
+    YUV_REQUIRE_FRAME(OH, OW);
+    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
+                  name);
+    OFASR_REQUIRE(max_eh <= sh && max_ew <= sw, OFASR_ERR_INVALID_ARG, "%s: extent bound larger than the source window",
+                  name);
+    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 10), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    hipStream_t st = as_stream(stream);
+    const YuvEnc E = yuv_enc(coeffs);
+    if (dtype == OFASR_F32) yuv_scatter<float, P>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    else if (dtype == OFASR_BF16) yuv_scatter<bf16_t, P>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    else yuv_scatter<f16_t, P>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    return check_launch(name);
+}
 
 OFASR_EXPORT int ofasr_yuv420_to_rgb_u8(const void* y, const void* u, const void* v, int64_t H, int64_t W,
                                         const int32_t* coeffs, void* rgb_hwc, void* stream) {
@@ -415,41 +495,34 @@ OFASR_EXPORT int ofasr_rgb_to_yuv420_u8(const void* rgb_hwc, int64_t H, int64_t 
 OFASR_EXPORT int ofasr_tile_gather_yuv420(const void* y, const void* u, const void* v, int64_t H, int64_t W,
                                           const int32_t* coeffs, const int64_t* origins, int64_t n, int64_t h, int64_t w,
                                           void* out, int dtype, void* stream) {
-    const char* name = "ofasr_tile_gather_yuv420";
-    OFASR_REQUIRE(y && u && v && coeffs && origins && out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
-    OFASR_REQUIRE(n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    YUV_REQUIRE_FRAME(H, W);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
-    OFASR_REQUIRE(h <= H && w <= W, OFASR_ERR_INVALID_ARG, "%s: window %lldx%lld larger than the frame %lldx%lld", name,
-                  (long long)h, (long long)w, (long long)H, (long long)W);
-    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
-    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
-    hipStream_t st = as_stream(stream);
-    const YuvDec D = yuv_dec(coeffs);
-    if (dtype == OFASR_F32) yuv_gather<float>(y, u, v, H, W, D, origins, n, h, w, out, st);
-    else if (dtype == OFASR_BF16) yuv_gather<bf16_t>(y, u, v, H, W, D, origins, n, h, w, out, st);
-    else yuv_gather<f16_t>(y, u, v, H, W, D, origins, n, h, w, out, st);
-    return check_launch(name);
+    return yuv_tile_gather<uint8_t>("ofasr_tile_gather_yuv420", y, u, v, H, W, coeffs, origins, n, h, w, out, dtype, stream);
 }
 
 OFASR_EXPORT int ofasr_tile_scatter_yuv420(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
                                            const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW,
                                            int64_t max_eh, int64_t max_ew, void* stream) {
-    const char* name = "ofasr_tile_scatter_yuv420";
-    OFASR_REQUIRE(src && table && coeffs && y && u && v, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
-    OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    YUV_REQUIRE_FRAME(OH, OW);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
-    OFASR_REQUIRE(max_eh <= sh && max_ew <= sw, OFASR_ERR_INVALID_ARG, "%s: extent bound larger than the source window",
-                  name);
-    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
-    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 10), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
-    hipStream_t st = as_stream(stream);
-    const YuvEnc E = yuv_enc(coeffs);
-    if (dtype == OFASR_F32) yuv_scatter<float>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
-    else if (dtype == OFASR_BF16) yuv_scatter<bf16_t>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
-    else yuv_scatter<f16_t>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
-    return check_launch(name);
+    return yuv_tile_scatter<uint8_t>("ofasr_tile_scatter_yuv420", src, n, sh, sw, dtype, table, coeffs, y, u, v, OH, OW, max_eh,
+                                     max_ew, stream);
+}
+
+// 16-bit planes: the one depth this library defines, and plane pointers aligned for their samples
+#define YUV_REQUIRE_P16(depth, y, u, v)                                                                                  \
+    OFASR_REQUIRE((depth) == 10, OFASR_ERR_INVALID_ARG, "%s: depth %d is not supported (10 only)", name, (int)(depth));  \
+    OFASR_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(v)) & 1) == 0, \
+                  OFASR_ERR_INVALID_ARG, "%s: a 16-bit plane pointer is not 2-byte aligned", name)
+
+OFASR_EXPORT int ofasr_tile_gather_yuv420p16(const void* y, const void* u, const void* v, int64_t H, int64_t W, int depth,
+                                             const int32_t* coeffs, const int64_t* origins, int64_t n, int64_t h, int64_t w,
+                                             void* out, int dtype, void* stream) {
+    const char* name = "ofasr_tile_gather_yuv420p16";
+    YUV_REQUIRE_P16(depth, y, u, v);
+    return yuv_tile_gather<uint16_t>(name, y, u, v, H, W, coeffs, origins, n, h, w, out, dtype, stream);
+}
+
+OFASR_EXPORT int ofasr_tile_scatter_yuv420p16(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype,
+                                              const int64_t* table, int depth, const int32_t* coeffs, void* y, void* u, void* v,
+                                              int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, void* stream) {
+    const char* name = "ofasr_tile_scatter_yuv420p16";
+    YUV_REQUIRE_P16(depth, y, u, v);
+    return yuv_tile_scatter<uint16_t>(name, src, n, sh, sw, dtype, table, coeffs, y, u, v, OH, OW, max_eh, max_ew, stream);
 }

@@ -296,19 +296,24 @@ def quality_mse(output, target, out=None):
 
 
 # ------------------------------------------------------------------------------ YUV 4:2:0 frames
-def yuv_table(matrix, full_range, encode):
+YUV_DEPTHS = {torch.uint8: 8, torch.uint16: 10}     # the depth a plane's dtype stands for
+YUV_DTYPES = {8: torch.uint8, 10: torch.uint16}
+
+
+def yuv_table(matrix, full_range, encode, depth=8):
     """the decode (encode=False) or encode table of video.yuv_coeffs as the int32 host array the library reads"""
     from . import video
-    t = video.yuv_coeffs(matrix, bool(full_range))[1 if encode else 0]
+    t = video.yuv_coeffs(matrix, bool(full_range), depth)[1 if encode else 0]
     return (ctypes.c_int32 * len(t))(*t)
 
 
 def yuv420_planes(y, u, v, what):
-    """validate one frame: three contiguous uint8 GPU planes, y [H, W] with even sides, u and v [H/2, W/2] -> (H, W)"""
+    """validate one frame: three contiguous GPU planes of one dtype, uint8 or uint16 (depth 10), y [H, W] with even sides, u
+    and v [H/2, W/2] -> (H, W)"""
     _gpu(y, u, v)
     for p in (y, u, v):
-        if p.dtype != torch.uint8 or p.dim() != 2 or not p.is_contiguous() or p.device != y.device:
-            raise ValueError("%s needs three contiguous 2-D uint8 planes on one GPU" % what)
+        if p.dtype not in YUV_DEPTHS or p.dtype != y.dtype or p.dim() != 2 or not p.is_contiguous() or p.device != y.device:
+            raise ValueError("%s needs three contiguous 2-D planes on one GPU, all uint8 or all uint16" % what)
     H, W = y.shape
     if H < 2 or W < 2 or H % 2 or W % 2:
         raise ValueError("%s: a YUV 4:2:0 frame needs even sides, got %dx%d" % (what, W, H))
@@ -322,6 +327,8 @@ def yuv420_to_rgb_u8(y, u, v, matrix="bt601", full_range=False):
     """planar YUV 4:2:0 (uint8 GPU planes y [H, W], u, v [H/2, W/2]) -> HWC uint8 RGB [H, W, 3]
     (ofasr_yuv420_to_rgb_u8, csrc/yuv.hip; the definition is video.yuv420_to_rgb_host)"""
     H, W = yuv420_planes(y, u, v, "yuv420_to_rgb_u8")
+    if y.dtype != torch.uint8:
+        raise ValueError("yuv420_to_rgb_u8 takes uint8 planes (the whole-frame kernels are 8-bit only)")
     rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=y.device)
     _C.check(_C.lib().ofasr_yuv420_to_rgb_u8(_p(y), _p(u), _p(v), H, W, yuv_table(matrix, full_range, False), _p(rgb),
                                              _stream()), "ofasr_yuv420_to_rgb_u8")
@@ -342,7 +349,7 @@ def rgb_to_yuv420_u8(rgb, matrix="bt601", full_range=False, out=None):
                torch.empty(H // 2, W // 2, dtype=torch.uint8, device=rgb.device),
                torch.empty(H // 2, W // 2, dtype=torch.uint8, device=rgb.device))
     y, u, v = out
-    if yuv420_planes(y, u, v, "rgb_to_yuv420_u8") != (H, W) or y.device != rgb.device:
+    if yuv420_planes(y, u, v, "rgb_to_yuv420_u8") != (H, W) or y.device != rgb.device or y.dtype != torch.uint8:
         raise ValueError("rgb_to_yuv420_u8: the output planes do not match the %dx%d image" % (W, H))
     _C.check(_C.lib().ofasr_rgb_to_yuv420_u8(_p(rgb), H, W, yuv_table(matrix, full_range, True), _p(y), _p(u), _p(v),
                                              _stream()), "ofasr_rgb_to_yuv420_u8")

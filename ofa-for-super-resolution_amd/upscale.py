@@ -26,7 +26,9 @@ Video frames (`upscale_yuv420`): a planar 8-bit YUV 4:2:0 frame goes through the
 video.py inside the two tile moves (ofasr_tile_gather_yuv420 / ofasr_tile_scatter_yuv420, csrc/yuv.hip), so no RGB frame
 exists on either side of the network.  The gather decodes at frame coordinates (a window edge never replicates chroma) and
 takes the odd origins that a shift by the halo makes; the scatter needs even output rectangles, which an even frame and an
-even upscale factor give.
+even upscale factor give.  Planes of uint16 are 10-bit frames (video.py, depth 10) and go through the 16-bit twins of
+the two kernels (ofasr_tile_gather_yuv420p16 / ofasr_tile_scatter_yuv420p16); the output depth is independent of the
+input's (`out_depth`), and 8 -> 10 keeps the precision that the network computed and an 8-bit output rounds away.
 
 Video streams (`yuv420_stream`): consecutive frames often repeat bytes exactly (screen recordings, animation, letterbox
 bars, duplicated frames, a codec's skip blocks).  The core of a window's output depends only on the input bytes of that
@@ -250,34 +252,50 @@ def tile_scatter(src, table, img, max_eh, max_ew):
 def tile_gather_yuv420(y, u, v, origins, h, w, dtype, matrix="bt601", full_range=False, out=None):
     """planar YUV 4:2:0 frame (uint8 GPU planes y [H, W], u, v [H/2, W/2]) -> [n, 3, h, w] of dtype: the RGB of the
     windows at `origins` (int64 [n, 2] on the GPU; odd origins are fine), decoded at frame coordinates, / 255 (fp32), cast
-    -- tile_gather(ops.yuv420_to_rgb_u8(y, u, v)) bit for bit without the RGB frame (ofasr_tile_gather_yuv420)"""
+    -- tile_gather(ops.yuv420_to_rgb_u8(y, u, v)) bit for bit without the RGB frame (ofasr_tile_gather_yuv420).  uint16
+    planes are a 10-bit frame: the decode of depth 10, / 1023 (ofasr_tile_gather_yuv420p16)."""
     H, W = ops.yuv420_planes(y, u, v, "tile_gather_yuv420")
     if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous():
         raise ValueError("tile_gather_yuv420 needs a contiguous int64 origin table on the GPU")
     n = origins.size(0)
     if out is None:
         out = torch.empty(n, 3, h, w, dtype=dtype, device=y.device)
-    _C.check(_C.lib().ofasr_tile_gather_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W,
-                                               ops.yuv_table(matrix, full_range, False), origins.data_ptr(), n, h, w,
-                                               out.data_ptr(), _CODES[out.dtype], ops._stream()),
-             "ofasr_tile_gather_yuv420")
+    depth = ops.YUV_DEPTHS[y.dtype]
+    coeffs = ops.yuv_table(matrix, full_range, False, depth)
+    if depth == 8:
+        _C.check(_C.lib().ofasr_tile_gather_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W, coeffs,
+                                                   origins.data_ptr(), n, h, w, out.data_ptr(), _CODES[out.dtype],
+                                                   ops._stream()), "ofasr_tile_gather_yuv420")
+    else:
+        _C.check(_C.lib().ofasr_tile_gather_yuv420p16(y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W, depth, coeffs,
+                                                      origins.data_ptr(), n, h, w, out.data_ptr(), _CODES[out.dtype],
+                                                      ops._stream()), "ofasr_tile_gather_yuv420p16")
     return out
 
 
 def tile_scatter_yuv420(src, table, y, u, v, max_eh, max_ew, matrix="bt601", full_range=False):
     """src: network output [n, 3, sh, sw]; table: int64 [n, 6] (sy, sx, dy, dx, eh, ew) on the GPU, dy / dx / eh / ew even
     (the kernel clears their low bit); quantises as tile_scatter does and encodes every 2x2 block of the extents into the
-    planes y [OH, OW], u, v [OH/2, OW/2] (ofasr_tile_scatter_yuv420)"""
+    planes y [OH, OW], u, v [OH/2, OW/2] (ofasr_tile_scatter_yuv420).  uint16 planes are a 10-bit frame: quantised to
+    round_half_even(clamp(v, 0, 1) * 1023) and encoded at depth 10 (ofasr_tile_scatter_yuv420p16)."""
     ops._gpu(src)
     if not src.is_contiguous() or src.dim() != 4 or src.size(1) != 3:
         raise ValueError("tile_scatter_yuv420 needs a contiguous [n, 3, h, w] source")
     OH, OW = ops.yuv420_planes(y, u, v, "tile_scatter_yuv420")
     if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.size(0) > src.size(0):
         raise ValueError("tile_scatter_yuv420 needs a contiguous int64 table on the GPU, one row per source window at most")
-    _C.check(_C.lib().ofasr_tile_scatter_yuv420(src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype],
-                                                table.data_ptr(), ops.yuv_table(matrix, full_range, True), y.data_ptr(),
-                                                u.data_ptr(), v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()),
-             "ofasr_tile_scatter_yuv420")
+    depth = ops.YUV_DEPTHS[y.dtype]
+    coeffs = ops.yuv_table(matrix, full_range, True, depth)
+    if depth == 8:
+        _C.check(_C.lib().ofasr_tile_scatter_yuv420(src.data_ptr(), table.size(0), src.size(2), src.size(3),
+                                                    _CODES[src.dtype], table.data_ptr(), coeffs, y.data_ptr(), u.data_ptr(),
+                                                    v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()),
+                 "ofasr_tile_scatter_yuv420")
+    else:
+        _C.check(_C.lib().ofasr_tile_scatter_yuv420p16(src.data_ptr(), table.size(0), src.size(2), src.size(3),
+                                                       _CODES[src.dtype], table.data_ptr(), depth, coeffs, y.data_ptr(),
+                                                       u.data_ptr(), v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()),
+                 "ofasr_tile_scatter_yuv420p16")
     return y, u, v
 
 
@@ -290,10 +308,10 @@ def window_diff_yuv420(y, u, v, py, pu, pv, origins, h, w, flags=None):
     """two planar YUV 4:2:0 frames of one size (current y, u, v and previous py, pu, pv: uint8 GPU planes) and the
     int64 origin table [n, 2] of h x w windows on the GPU -> int32 flags [n, window_diff_slabs(h, w)]: a window's row is
     non-zero iff any byte of its support (video.window_support) differs between the frames (ofasr_window_diff_yuv420;
-    host definition: video.changed_windows_host)"""
+    host definition: video.changed_windows_host).  Two frames of uint16 planes alike (ofasr_window_diff_yuv420p16)."""
     H, W = ops.yuv420_planes(y, u, v, "window_diff_yuv420")
-    if ops.yuv420_planes(py, pu, pv, "window_diff_yuv420") != (H, W):
-        raise ValueError("window_diff_yuv420 needs two frames of one size")
+    if ops.yuv420_planes(py, pu, pv, "window_diff_yuv420") != (H, W) or py.dtype != y.dtype:
+        raise ValueError("window_diff_yuv420 needs two frames of one size and dtype")
     if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous() or origins.dim() != 2 \
             or origins.size(1) != 2:
         raise ValueError("window_diff_yuv420 needs a contiguous int64 origin table [n, 2] on the GPU")
@@ -303,9 +321,15 @@ def window_diff_yuv420(y, u, v, py, pu, pv, origins, h, w, flags=None):
         flags = torch.empty(n, max(S, 1), dtype=torch.int32, device=y.device)
     elif flags.dtype != torch.int32 or not flags.is_cuda or not flags.is_contiguous() or flags.numel() != n * S:
         raise ValueError("window_diff_yuv420 needs contiguous int32 flags [n, %d] on the GPU" % S)
-    _C.check(_C.lib().ofasr_window_diff_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), py.data_ptr(), pu.data_ptr(),
-                                               pv.data_ptr(), H, W, origins.data_ptr(), n, h, w, flags.data_ptr(),
-                                               ops._stream()), "ofasr_window_diff_yuv420")
+    depth = ops.YUV_DEPTHS[y.dtype]
+    if depth == 8:
+        _C.check(_C.lib().ofasr_window_diff_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), py.data_ptr(), pu.data_ptr(),
+                                                   pv.data_ptr(), H, W, origins.data_ptr(), n, h, w, flags.data_ptr(),
+                                                   ops._stream()), "ofasr_window_diff_yuv420")
+    else:
+        _C.check(_C.lib().ofasr_window_diff_yuv420p16(y.data_ptr(), u.data_ptr(), v.data_ptr(), py.data_ptr(), pu.data_ptr(),
+                                                      pv.data_ptr(), H, W, depth, origins.data_ptr(), n, h, w,
+                                                      flags.data_ptr(), ops._stream()), "ofasr_window_diff_yuv420p16")
     return flags
 
 
@@ -420,10 +444,22 @@ class TiledUpscaler(object):
         return TilePlan(H, W, H, W, [(0, 0, 0, 0, H, W)], self.scale, 1)
 
     def _forward(self, x):
-        if self.graphed is not None:
-            return self.graphed(x)
-        with torch.autocast("cuda", dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
-            return self.net(x)
+        # A window's output must not depend on the shape of the batch it was computed in: that is what makes tiling, and
+        # reuse between frames, exact.  The fused 16-bit MB kernel breaks it on small inputs: a launch of fewer tiles than
+        # CUs spreads each tile's mid-channel chunks over several workgroups (csrc/mbfused.hip, mf_plan) and then sums
+        # them in another order, and how many tiles a launch has depends on the batch.  So the upscaler's forwards (and
+        # the graphs captured from them) run with that split off; it never applied to launches of more than 128 tiles,
+        # which is every batch of real video windows.
+        split = _C.lib().ofasr_debug_mbfused_split(0) if self.autocast_dtype is not None else None
+        try:
+            if self.graphed is not None:
+                return self.graphed(x)
+            with torch.autocast("cuda", dtype=self.autocast_dtype or torch.bfloat16,
+                                enabled=self.autocast_dtype is not None):
+                return self.net(x)
+        finally:
+            if split is not None:
+                _C.lib().ofasr_debug_mbfused_split(split)
 
     def _image(self, img):
         if not torch.is_tensor(img):
@@ -505,8 +541,9 @@ class TiledUpscaler(object):
         for p in (y, u, v):
             if not torch.is_tensor(p):
                 p = torch.from_numpy(p)
-            if p.dtype != torch.uint8 or p.dim() != 2:
-                raise ValueError("upscale_yuv420 takes three 2-D uint8 planes, got %s %s" % (tuple(p.shape), p.dtype))
+            if p.dtype not in ops.YUV_DEPTHS or p.dim() != 2:
+                raise ValueError("upscale_yuv420 takes three 2-D uint8 (or, 10-bit, uint16) planes, got %s %s"
+                                 % (tuple(p.shape), p.dtype))
             planes.append(p.to(dev).contiguous())
         y, u, v = planes
         H, W = int(y.shape[0]), int(y.shape[1])
@@ -518,17 +555,26 @@ class TiledUpscaler(object):
         ops.yuv420_planes(y, u, v, "upscale_yuv420")
         return dev, (y, u, v), H, W
 
-    def upscale_yuv420(self, y, u, v, matrix="bt601", full_range=False, whole=False):
+    @staticmethod
+    def _yuv420_out(H, W, s, depth, dev):
+        """fresh output planes of a depth (8 or 10) for an H x W input at scale s"""
+        if isinstance(depth, bool) or depth not in ops.YUV_DTYPES:
+            raise ValueError("out_depth must be 8 or 10, got %r" % (depth,))
+        dt = ops.YUV_DTYPES[depth]
+        return (torch.empty(H * s, W * s, dtype=dt, device=dev), torch.empty(H * s // 2, W * s // 2, dtype=dt, device=dev),
+                torch.empty(H * s // 2, W * s // 2, dtype=dt, device=dev))
+
+    def upscale_yuv420(self, y, u, v, matrix="bt601", full_range=False, whole=False, out_depth=None):
         """one planar YUV 4:2:0 frame (uint8 planes y [H, W], u, v [H/2, W/2]; CPU or GPU tensors, or numpy arrays) ->
         the upscaled planes (Y [H*s, W*s], U, V [H*s/2, W*s/2]) on the GPU.  The same plan, graph replay and self-ensemble
         as upscale(); the colour conversion is fused into the two tile moves (tile_gather_yuv420 / tile_scatter_yuv420),
         so no RGB frame exists on either side: the result equals
-        ops.rgb_to_yuv420_u8(upscale(ops.yuv420_to_rgb_u8(y, u, v))) bit for bit."""
+        ops.rgb_to_yuv420_u8(upscale(ops.yuv420_to_rgb_u8(y, u, v))) bit for bit.  uint16 planes are a 10-bit frame.
+        `out_depth` (8 or 10; None: the input's) is the depth of the output planes, whatever the input's: 8 -> 10 writes
+        the network's output at 1024 levels instead of rounding it to 256."""
         dev, (y, u, v), H, W = self._yuv420_frame(y, u, v)
         s = self.scale
-        out = (torch.empty(H * s, W * s, dtype=torch.uint8, device=dev),
-               torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev),
-               torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev))
+        out = self._yuv420_out(H, W, s, ops.YUV_DEPTHS[y.dtype] if out_depth is None else out_depth, dev)
 
         def sink(t, real, table, wins, plan):
             tile_scatter_yuv420(t.contiguous(), table, out[0], out[1], out[2], max(w[4] for w in wins) * s,
@@ -538,10 +584,10 @@ class TiledUpscaler(object):
                           lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range))
         return out
 
-    def yuv420_stream(self, matrix="bt601", full_range=False):
+    def yuv420_stream(self, matrix="bt601", full_range=False, out_depth=None):
         """a YUV420Stream on this upscaler: upscale_yuv420 for the consecutive frames of one video, re-running only the
         windows whose input bytes changed since the previous frame; the same output bit for bit"""
-        return YUV420Stream(self, matrix, full_range)
+        return YUV420Stream(self, matrix, full_range, out_depth)
 
     def upscale_float(self, img, whole=False):
         """the network's fp32 output [3, H*scale, W*scale] before quantisation, assembled from the same window cores
@@ -598,13 +644,17 @@ class YUV420Stream(object):
     Skipping is therefore per batch of B windows of changed content; a smaller `batch` or `core` of the upscaler skips
     more finely and pays for it with more launches or a larger plan.overhead() (window pixels per core pixel).
 
-    The first frame, a frame of another size and the frame after reset() run every window.  The comparison is exact: it
-    pays off on content that repeats bit for bit and does nothing for camera noise."""
+    The first frame, a frame of another size or dtype (uint8 / uint16: 8-bit / 10-bit) and the frame after reset() run
+    every window.  The previous-frame planes have the input's dtype, the output planes that of `out_depth` (None: the
+    input's).  The comparison is exact: it pays off on content that repeats bit for bit and does nothing for camera
+    noise."""
 
-    def __init__(self, upscaler, matrix="bt601", full_range=False):
+    def __init__(self, upscaler, matrix="bt601", full_range=False, out_depth=None):
         ops.yuv_table(matrix, full_range, False)       # refuses an unknown matrix now rather than at the first frame
+        if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in ops.YUV_DTYPES):
+            raise ValueError("out_depth must be 8 or 10, got %r" % (out_depth,))
         self.up = upscaler
-        self.matrix, self.full_range = matrix, full_range
+        self.matrix, self.full_range, self.out_depth = matrix, full_range, out_depth
         self.stats = StreamStats()
         self._size = None
         self._fresh = self._all = True
@@ -614,7 +664,7 @@ class YUV420Stream(object):
         """forget the previous frame: the next one runs every window"""
         self._fresh = True
 
-    def _setup(self, H, W, dev):
+    def _setup(self, H, W, dev, dtype):
         up = self.up
         s = up.scale
         plan = up.plan(H, W)
@@ -626,18 +676,15 @@ class YUV420Stream(object):
         self._origins, self._table = up._tables(plan, dev)
         self._max_eh = max(w[4] for w in plan.windows) * s
         self._max_ew = max(w[5] for w in plan.windows) * s
-        self._prev = (torch.empty(H, W, dtype=torch.uint8, device=dev),
-                      torch.empty(H // 2, W // 2, dtype=torch.uint8, device=dev),
-                      torch.empty(H // 2, W // 2, dtype=torch.uint8, device=dev))
-        self._out = (torch.empty(H * s, W * s, dtype=torch.uint8, device=dev),
-                     torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev),
-                     torch.empty(H * s // 2, W * s // 2, dtype=torch.uint8, device=dev))
+        self._prev = (torch.empty(H, W, dtype=dtype, device=dev), torch.empty(H // 2, W // 2, dtype=dtype, device=dev),
+                      torch.empty(H // 2, W // 2, dtype=dtype, device=dev))
+        self._out = up._yuv420_out(H, W, s, ops.YUV_DEPTHS[dtype] if self.out_depth is None else self.out_depth, dev)
         n = len(plan)
         self._flags = torch.zeros(n, window_diff_slabs(plan.win_h, plan.win_w), dtype=torch.int32, device=dev)
         self._compact = (torch.zeros(self._origins.size(0), 2, dtype=torch.int64, device=dev),
                          torch.zeros(n, 6, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
                          torch.zeros(1, dtype=torch.int64, device=dev))
-        self._size = (H, W, dev)
+        self._size = (H, W, dev, dtype)
         self._fresh = True
 
     def changed_windows(self):
@@ -652,8 +699,8 @@ class YUV420Stream(object):
         """one frame -> the upscaled planes (Y, U, V): the stream's own buffers, valid until the next call"""
         up = self.up
         dev, (y, u, v), H, W = up._yuv420_frame(y, u, v)
-        if self._size != (H, W, dev):
-            self._setup(H, W, dev)
+        if self._size != (H, W, dev, y.dtype):
+            self._setup(H, W, dev, y.dtype)
         plan, B, n = self._plan, self._B, len(self._plan)
         out = self._out
 

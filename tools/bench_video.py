@@ -14,8 +14,12 @@ the windows static (about FRACTION of the plan; with small cores a centre can li
 fraction of windows that really ran is reported beside the one asked for).  Per fraction: wall-clock frames/s over --reps
 frames of per-frame upscale_yuv420 and of the stream on the same clip in the same process, and once per precision the
 cost of what the stream adds to a frame where nothing is skipped: diff + compaction + the count's read-back, timed alone.
+
+--depth 10 runs the same on a 10-bit frame (uint16 planes, the 16-bit tile moves and window diff), --out-depth 8|10 sets
+the output's depth independently (default: the input's; 8 -> 10 is the 8-bit gather with the 16-bit scatter).  There is no
+whole-frame 10-bit kernel, so (b) is left out whenever either depth is 10.
 usage: python tools/bench_video.py [--size 1080 1920] [--reps 3] [--precs f32 bf16] [--reuse 0 0.5 0.9 1.0] [--core N]
-       [--batch N]"""
+       [--batch N] [--depth 8|10] [--out-depth 8|10]"""
 import argparse
 import importlib
 import json
@@ -70,7 +74,7 @@ def wall_ms(fn, reps):
     return (time.perf_counter() - t0) * 1e3 / reps
 
 
-def bench_reuse(up, tu, planes, fractions, reps):
+def bench_reuse(up, tu, planes, fractions, reps, out_depth=None):
     """frames/s with and without reuse on two alternating frames, per fraction of static windows"""
     import torch
     y, u, v = planes
@@ -79,18 +83,19 @@ def bench_reuse(up, tu, planes, fractions, reps):
     n = len(plan)
     _, B = tu._batching(plan)
     rec = {"windows": n, "window": [plan.win_h, plan.win_w], "batch": B, "overhead": round(plan.overhead(), 3), "fractions": {}}
-    stream = tu.yuv420_stream()
+    stream = tu.yuv420_stream(out_depth=out_depth)
     for frac in fractions:
         moving = plan.windows[:n - int(round(frac * n))]
-        other = y.clone()
+        other = y.cpu().numpy().copy()                    # on the host: torch has no arithmetic on uint16
         for (_, _, cy, cx, ch, cw) in moving:
             other[cy + ch // 2, cx + cw // 2] ^= 0x40
+        other = torch.from_numpy(other).to(y.device)
         clip = [(y, u, v), (other, u, v)]
         state = {"i": 0, "run": 0, "frames": 0}
 
         def plain():
             state["i"] ^= 1
-            return tu.upscale_yuv420(*clip[state["i"]])
+            return tu.upscale_yuv420(*clip[state["i"]], out_depth=out_depth)
 
         def reuse():
             state["i"] ^= 1
@@ -131,6 +136,8 @@ def main():
                     help="measure window reuse with this fraction of static windows instead (several: one run each)")
     ap.add_argument("--core", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--depth", type=int, default=8, choices=[8, 10], help="bits per input sample")
+    ap.add_argument("--out-depth", type=int, default=None, choices=[8, 10], help="bits per output sample (default: --depth)")
     a = ap.parse_args()
     import torch
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
@@ -139,22 +146,28 @@ def main():
     ops = importlib.import_module(PKG + ".ops")
     H, W = a.size
     g = torch.Generator().manual_seed(0)
-    y = torch.randint(16, 236, (H, W), generator=g, dtype=torch.uint8).cuda()
-    u, v = (torch.randint(16, 241, (H // 2, W // 2), generator=g, dtype=torch.uint8).cuda() for _ in range(2))
+    out_depth = a.depth if a.out_depth is None else a.out_depth
+    if a.depth == 8:
+        y = torch.randint(16, 236, (H, W), generator=g, dtype=torch.uint8).cuda()
+        u, v = (torch.randint(16, 241, (H // 2, W // 2), generator=g, dtype=torch.uint8).cuda() for _ in range(2))
+    else:                                                  # legal 10-bit values, made as int16 (torch.randint has no uint16)
+        y = torch.randint(64, 941, (H, W), generator=g, dtype=torch.int16).view(torch.uint16).cuda()
+        u, v = (torch.randint(64, 961, (H // 2, W // 2), generator=g, dtype=torch.int16).view(torch.uint16).cuda()
+                for _ in range(2))
     sup = nets.OFAMobileNetS4(**KW)
     random.seed(0)
     sup.set_active_subnet(**MAX)
     net = st.build_static_net(sup.get_active_net_config())
     net.init_model("he_fout")
     net = net.cuda().eval()
-    out = {"size": [H, W], "reps": a.reps, "runs": {}}
+    out = {"size": [H, W], "reps": a.reps, "depth": a.depth, "out_depth": out_depth, "runs": {}}
     for prec in a.precs:
         tu = up.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=prec)
         plan = tu.plan(H, W)
         if a.reuse is not None:
             if any(not 0.0 <= f <= 1.0 for f in a.reuse):
                 raise SystemExit("--reuse takes fractions in 0 .. 1")
-            rec = bench_reuse(up, tu, (y, u, v), a.reuse, a.reps)
+            rec = bench_reuse(up, tu, (y, u, v), a.reuse, a.reps, out_depth)
             out["runs"]["max_" + prec] = rec
             print(prec, rec, file=sys.stderr, flush=True)
             del tu
@@ -162,7 +175,7 @@ def main():
             continue
 
         def fused():
-            return tu.upscale_yuv420(y, u, v)
+            return tu.upscale_yuv420(y, u, v, out_depth=out_depth)
 
         def unfused():
             return ops.rgb_to_yuv420_u8(tu.upscale(ops.yuv420_to_rgb_u8(y, u, v)))
@@ -181,12 +194,14 @@ def main():
                 for x in batches:
                     tu._forward(x)
 
-        ms = {"fused": event_ms(fused, a.reps), "unfused": event_ms(unfused, a.reps), "network": event_ms(network, a.reps)}
+        paths = {"fused": fused, "unfused": unfused} if a.depth == out_depth == 8 else {"fused": fused}
+        ms = {k: event_ms(fn, a.reps) for k, fn in paths.items()}
+        ms["network"] = event_ms(network, a.reps)
         del batches[:]
         rec = {"windows": len(plan), "window": [plan.win_h, plan.win_w], "ms": {k: round(t, 2) for k, t in ms.items()},
-               "frames_per_s": {k: round(1e3 / ms[k], 3) for k in ("fused", "unfused")},
+               "frames_per_s": {k: round(1e3 / ms[k], 3) for k in paths},
                "out_MP_per_s_fused": round(H * W * tu.scale ** 2 / 1e6 / (ms["fused"] / 1e3), 2),
-               "peak_extra_MiB": {"fused": peak_extra_mb(fused), "unfused": peak_extra_mb(unfused)}}
+               "peak_extra_MiB": {k: peak_extra_mb(fn) for k, fn in paths.items()}}
         out["runs"]["max_" + prec] = rec
         print(prec, rec, file=sys.stderr, flush=True)
         del tu

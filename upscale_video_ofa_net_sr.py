@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Upscale a raw 8-bit YUV 4:2:0 video (Y4M, or headerless yuv420p with --size) with an exported static SR network.
+"""Upscale a raw 8-bit or 10-bit YUV 4:2:0 video (Y4M, or headerless yuv420p with --size) with an exported static SR network.
 
 The network is a static SRNetS4 / SRNetX4 exported with `search_ofa_net_sr.py --export DIR` or
 `eval_ofa_net_sr.py --export DIR`.  Every frame goes planar YUV in, planar YUV out: the colour conversion (video.py: bt601
@@ -15,6 +15,11 @@ exact integer squared error, per frame and as the mean, printed and written to <
 output file is byte-identical, static content (screen recordings, animation, letterbox bars, repeated frames, a codec's
 skip blocks) costs a byte comparison instead of the network, and noisy camera material gains nothing.  A smaller --batch
 or --core skips more finely.  The summary then also says how many windows ran.
+10-bit video: a C420p10 Y4M is read as such; a headerless yuv420p10le file needs --depth 10 (little-endian 16-bit
+words).  --out-depth 8|10 is the depth of the output, by default the input's, and independent of it: 8-bit input with
+--out-depth 10 writes the network's output at 1024 levels instead of rounding it to 256, at no cost in network time.  The
+output Y4M carries the input's C tag when the depths are equal, C420p10 for 8 -> 10 and C420jpeg for 10 -> 8.  --reference
+is opened at the output's depth and scored against its peak (255 or 1023).  --dump-png needs an 8-bit output.
 Prints frames per second and output megapixels per second at the end."""
 import argparse
 import concurrent.futures
@@ -56,6 +61,9 @@ def parse_args(argv=None):
     ap.add_argument("--static", required=True, metavar="DIR", help="exported static network")
     ap.add_argument("--out", required=True, metavar="OUT", help="output file: *.y4m, or anything else for raw yuv420p")
     ap.add_argument("--size", type=parse_size, default=None, metavar="WxH", help="frame size of a headerless input")
+    ap.add_argument("--depth", type=int, default=None, choices=[8, 10],
+                    help="bits per sample of a headerless input (default 8); a Y4M input says it itself")
+    ap.add_argument("--out-depth", type=int, default=None, choices=[8, 10], help="bits per output sample (default: the input's)")
     ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
     ap.add_argument("--range", default="tv", choices=["tv", "pc"], help="tv: limited (16..235), pc: full range")
     ap.add_argument("--frames", type=parse_frames, default=(0, None), metavar="A:B", help="frames A .. B-1 only")
@@ -68,11 +76,14 @@ def parse_args(argv=None):
     ap.add_argument("--dump-png", default=None, metavar="DIR", help="also write every output frame as a PNG")
     ap.add_argument("--reference", default=None, metavar="REF", help="ground-truth video of the output's size: PSNR")
     ap.add_argument("input", metavar="INPUT", help="*.y4m, or a headerless yuv420p file (then --size is required)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.dump_png is not None and 10 in (a.out_depth, a.depth if a.out_depth is None else None):
+        ap.error("--dump-png needs an 8-bit output (there is no 16-bit PNG writer): leave it out or use --out-depth 8")
+    return a
 
 
-def psnr(sse, count):
-    return math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * count / sse)
+def psnr(sse, count, peak=255.0):
+    return math.inf if sse == 0 else 10.0 * math.log10(peak ** 2 * count / sse)
 
 
 def save_png(arr, path):
@@ -91,30 +102,39 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("upscaling runs on the GPU")
     try:
-        reader = video.open_reader(a.input, a.size)
+        reader = video.open_reader(a.input, a.size, a.depth)
     except ValueError as e:
         raise SystemExit(str(e))
     W, H = reader.width, reader.height
+    depth = reader.depth
+    out_depth = depth if a.out_depth is None else a.out_depth
+    if a.dump_png is not None and out_depth != 8:      # a C420p10 input without --out-depth 8: known only now
+        raise SystemExit("--dump-png needs an 8-bit output (there is no 16-bit PNG writer): use --out-depth 8")
     full = a.range == "pc"
     net = evals.load_static(a.static).cuda()
     up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble)
     s = up.scale
     OW, OH = W * s, H * s
-    stream = up.yuv420_stream(matrix=a.matrix, full_range=full) if a.reuse_static else None
-    print("%s x%d: %dx%d -> %dx%d, %s %s, receptive radius %d px, halo %d, core %d, %s%s" % (
+    stream = up.yuv420_stream(matrix=a.matrix, full_range=full, out_depth=out_depth) if a.reuse_static else None
+    print("%s x%d: %dx%d -> %dx%d, %s %s, receptive radius %d px, halo %d, core %d, %s%s%s" % (
         net.name(), s, W, H, OW, OH, a.matrix, a.range, up.radius, up.halo, up.core, a.mix_prec,
-        "" if a.self_ensemble == 1 else ", self-ensemble x%d" % a.self_ensemble))
+        "" if a.self_ensemble == 1 else ", self-ensemble x%d" % a.self_ensemble,
+        "" if depth == out_depth == 8 else ", %d -> %d bits" % (depth, out_depth)))
     if a.out.lower().endswith(".y4m"):
         y4m = isinstance(reader, video.Y4MReader)
+        if depth == out_depth:
+            chroma = reader.chroma if y4m else ("420jpeg" if depth == 8 else "420p10")
+        else:
+            chroma = "420p10" if out_depth == 10 else "420jpeg"
         writer = video.Y4MWriter(a.out, OW, OH, fps=reader.fps if y4m else None,
                                  interlace=reader.interlace if y4m else None, aspect=reader.aspect if y4m else None,
-                                 chroma=reader.chroma if y4m else "420jpeg", xtags=reader.xtags if y4m else ())
+                                 chroma=chroma, xtags=reader.xtags if y4m else (), depth=out_depth)
     else:
-        writer = video.RawYUV420Writer(a.out, OW, OH)
+        writer = video.RawYUV420Writer(a.out, OW, OH, out_depth)
     ref = None
     if a.reference is not None:
         try:
-            ref = video.open_reader(a.reference, (OW, OH))
+            ref = video.open_reader(a.reference, (OW, OH), out_depth)
         except ValueError as e:
             raise SystemExit(str(e))
         if (ref.width, ref.height) != (OW, OH):
@@ -129,7 +149,8 @@ def main(argv=None):
         if ref is not None and not ref.skip_frame():
             raise SystemExit("%s has fewer than %d frames" % (a.reference, first))
 
-    n_in, n_out = video.frame_bytes(W, H), video.frame_bytes(OW, OH)
+    n_in, n_out = video.frame_bytes(W, H, depth), video.frame_bytes(OW, OH, out_depth)
+    peak = 255.0 if out_depth == 8 else 1023.0
     pin_in = [torch.empty(n_in, dtype=torch.uint8).pin_memory() for _ in range(SLOTS)]
     pin_out = [torch.empty(n_out, dtype=torch.uint8).pin_memory() for _ in range(SLOTS)]
     dev_in = torch.empty(n_in, dtype=torch.uint8, device="cuda")
@@ -140,8 +161,12 @@ def main(argv=None):
         return None if fr is None else reader.frame_params if hasattr(reader, "frame_params") else ""
 
     def write(slot, params):
-        y, u, v = video.split_frame(pin_out[slot].numpy(), OW, OH)
+        y, u, v = video.split_frame(pin_out[slot].numpy(), OW, OH, out_depth)
         writer.write_frame(y, u, v, params)
+
+    def as_int64(t):
+        """a plane's samples as int64; uint16 words go through their int16 bits, which every conversion takes"""
+        return t.to(torch.int64) if t.dtype == torch.uint8 else t.view(torch.int16).to(torch.int64) & 0xFFFF
 
     scores = []
     done = 0
@@ -161,14 +186,14 @@ def main(argv=None):
             dev_in.copy_(pin_in[slot], non_blocking=True)
             torch.cuda.current_stream().synchronize()     # the pinned slot is free again once the upload has finished
             nxt = rd.submit(read, (done + 1) % SLOTS) if want is None or done + 1 < want else None
-            y, u, v = video.split_frame(dev_in, W, H)
+            y, u, v = video.split_frame(dev_in, W, H, depth)
             if stream is not None:
                 Y, U, V = stream.upscale(y, u, v)          # the stream's own planes: copied out before the next frame
             else:
-                Y, U, V = up.upscale_yuv420(y, u, v, matrix=a.matrix, full_range=full)
+                Y, U, V = up.upscale_yuv420(y, u, v, matrix=a.matrix, full_range=full, out_depth=out_depth)
             if writes[slot] is not None:
                 writes[slot].result()                      # the output slot's previous frame is on disk
-            dst = video.split_frame(pin_out[slot], OW, OH)
+            dst = video.split_frame(pin_out[slot], OW, OH, out_depth)
             for d, p in zip(dst, (Y, U, V)):
                 d.copy_(p, non_blocking=True)
             if ref is not None:
@@ -177,9 +202,9 @@ def main(argv=None):
                     raise SystemExit("%s ends before frame %d" % (a.reference, first + done))
                 rec = {"frame": first + done}
                 for name, got, exp in zip("yuv", (Y, U, V), fr):
-                    d = got.to(torch.int64) - torch.from_numpy(exp).to(got.device).to(torch.int64)
+                    d = as_int64(got) - as_int64(torch.from_numpy(exp).to(got.device))
                     sse = int((d * d).sum())
-                    rec["sse_" + name], rec["psnr_" + name] = sse, psnr(sse, got.numel())
+                    rec["sse_" + name], rec["psnr_" + name] = sse, psnr(sse, got.numel(), peak)
                 scores.append(rec)
                 print("frame %d: PSNR Y %.3f  U %.3f  V %.3f dB" % (rec["frame"], rec["psnr_y"], rec["psnr_u"], rec["psnr_v"]))
             if a.dump_png is not None:
