@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 309 /* + ofasr_tile_gather_yuv420p16, ofasr_tile_scatter_yuv420p16, ofasr_window_diff_yuv420p16 */
+#define OFASR_VERSION 310 /* + ofasr_tile_resize_scatter_u8, ofasr_tile_resize_scatter_yuv420, ofasr_tile_resize_scatter_yuv420p16 */
 
 typedef enum {
     OFASR_OK = 0,
@@ -488,6 +488,42 @@ int ofasr_tile_gather_yuv420p16(const void* y, const void* u, const void* v, int
 int ofasr_tile_scatter_yuv420p16(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
                                  int depth, const int32_t* coeffs, void* y, void* u, void* v, int64_t OH, int64_t OW,
                                  int64_t max_eh, int64_t max_ew, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Target-size output: the scatter with a Pillow-exact resize fused in (csrc/resize_scatter.hip; host statement:
+ * resize.py) -- for TiledUpscaler's `out_size`: the windows' output goes to an image or frame of TH x TW pixels, between
+ * the input's size and the network's own, and no full-size frame exists in memory.  The result is Pillow's
+ * Image.resize((TW, TH), filter) of the quantised full-size output (horizontal pass, clip, vertical pass, clip; 22
+ * coefficient bits at depth 8; at depth 10 the same arithmetic with 1023 for 255 and 20 bits), for the YUV sinks followed
+ * by the encode above.
+ *   src:   the network output [n, 3, sh, sw] of `dtype`, quantised on load as the scatters above do
+ *   table: device int64 [n][6] = (oy, ox, dy, dx, eh, ew): the origin of window n in the FULL-SIZE output and its target
+ *          rectangle; dy, dx, eh, ew are clamped to the target and to max_eh x max_ew (and, for the YUV sinks, have their
+ *          low bit cleared); an empty extent writes nothing
+ *   vtab:  device int32 [TH][2 + kh] rows (ymin, count, k[0 .. kh)) per target row; htab [TW][2 + kw] per target column:
+ *          Pillow's precompute_coeffs + normalize_coeffs_8bpc, computed on the HOST (resize.coeff_table); ymin / xmin are
+ *          full-size coordinates.  An axis that keeps its size takes the one-tap table (p, 1, 2^bits)
+ *   out[dy + r, dx + x] = clip((sum_j mid[ymin + j - oy, x] * kv[j] + 2^(bits-1)) >> bits),
+ *   mid[y, x] = clip((sum_i q(src[n, c, y, xmin + i - ox]) * kh[i] + 2^(bits-1)) >> bits)
+ * Sinks: _u8 a HWC uint8 image [TH, TW, 3]; _yuv420 / _yuv420p16 the planes y [TH, TW], u, v [TH/2, TW/2] of the
+ * frames defined above (TH, TW even; coeffs the encode table int32[10] of the depth).  Target rectangles of different
+ * windows must not overlap; bytes outside them are not written.  Plain loads and stores: two calls give identical bytes.
+ * Every access stays inside its tensor whatever the device tables hold: counts are clamped to kh / kw, source indices
+ * into the window, the tile's source rows to the 96 its LDS image holds -- a wrong table gives wrong values, never a
+ * fault.  64-bit addressing.  OFASR_ERR_INVALID_ARG: a null pointer, a non-positive size, kh or kw < 1, an extent bound
+ * larger than the target, a bad dtype, an odd side or a bad encode table (YUV), depth != 10 or a misaligned plane (p16).
+ * OFASR_ERR_UNSUPPORTED: kh or kw > 25 (lanczos at a 4 : 1 reduction), n > 65535, more than 2^40 pixels.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_tile_resize_scatter_u8(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
+                                 const int32_t* vtab, int kh, const int32_t* htab, int kw, void* img, int64_t TH, int64_t TW,
+                                 int64_t max_eh, int64_t max_ew, void* stream);
+int ofasr_tile_resize_scatter_yuv420(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
+                                     const int32_t* vtab, int kh, const int32_t* htab, int kw, const int32_t* coeffs, void* y,
+                                     void* u, void* v, int64_t TH, int64_t TW, int64_t max_eh, int64_t max_ew, void* stream);
+int ofasr_tile_resize_scatter_yuv420p16(const void* src, int64_t n, int64_t sh, int64_t sw, int dtype, const int64_t* table,
+                                        const int32_t* vtab, int kh, const int32_t* htab, int kw, int depth,
+                                        const int32_t* coeffs, void* y, void* u, void* v, int64_t TH, int64_t TW,
+                                        int64_t max_eh, int64_t max_ew, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Window reuse between video frames (csrc/reuse.hip; host statement: video.py window_support / changed_windows_host) --

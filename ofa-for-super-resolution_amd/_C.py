@@ -132,6 +132,13 @@ SIGNATURES = {
                                              _c_vp, _c_int, _c_vp]),
     "ofasr_tile_scatter_yuv420p16": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
                                               _c_i64, _c_i64, _c_i64, _c_i64, _c_vp]),
+    "ofasr_tile_resize_scatter_u8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp,
+                                              _c_i64, _c_i64, _c_i64, _c_i64, _c_vp]),
+    "ofasr_tile_resize_scatter_yuv420": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_int,
+                                                  _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp]),
+    "ofasr_tile_resize_scatter_yuv420p16": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_int,
+                                                     _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64,
+                                                     _c_vp]),
     "ofasr_window_diff_slabs": (_c_i64, [_c_i64, _c_i64]),
     "ofasr_window_diff_yuv420": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64,
                                           _c_vp, _c_vp]),

@@ -1,0 +1,130 @@
+// yuv_block.h -- what the kernels that read or write planar YUV 4:2:0 frames share: the sample types of a plane,
+// the 14-bit coefficient structs and their checks, the quantisation of network output, and the encode + store of one
+// 2 x 4 pixel block.  yuv.hip (the whole-frame conversions and the tile moves) and resize_scatter.hip (the resampling
+// scatter) include it, so there is one statement of the encode.
+#pragma once
+#include "ofasr_common.h"
+
+namespace ofasr {
+
+struct YuvDec { int yo, cy, rv, gu, gv, bu; };
+struct YuvEnc { int yo, yr, yg, yb, ur, ug, ub, vr, vg, vb; };
+
+// the sample type of a plane: its largest value, the chroma midpoint, how a stored sample is read, and the wide accesses
+// (four luma samples of a row, two chroma samples), which the callers take at addresses aligned for them only
+template <typename P> struct yuv_px;
+template <> struct yuv_px<uint8_t> {
+    static constexpr int maxv = 255, mid = 128;
+    static __device__ __forceinline__ int sample(uint8_t s) { return s; }
+    static __device__ __forceinline__ void load4(const uint8_t* p, int* o) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = (int)((w >> (8 * k)) & 0xffu);
+    }
+    static __device__ __forceinline__ void store4(uint8_t* p, const int* Y) {
+        *reinterpret_cast<uint32_t*>(p) = (uint32_t)Y[0] | (uint32_t)Y[1] << 8 | (uint32_t)Y[2] << 16 | (uint32_t)Y[3] << 24;
+    }
+    static __device__ __forceinline__ void store2(uint8_t* p, int a, int b) { *reinterpret_cast<uint16_t*>(p) = (uint16_t)(a | b << 8); }
+};
+template <> struct yuv_px<uint16_t> {
+    static constexpr int maxv = 1023, mid = 512;
+    static __device__ __forceinline__ int sample(unsigned s) { return (int)(s < 1023u ? s : 1023u); }   // the top six bits are not trusted
+    static __device__ __forceinline__ void load4(const uint16_t* p, int* o) {
+        const uint2 w = *reinterpret_cast<const uint2*>(p);
+        o[0] = sample(w.x & 0xffffu), o[1] = sample(w.x >> 16), o[2] = sample(w.y & 0xffffu), o[3] = sample(w.y >> 16);
+    }
+    static __device__ __forceinline__ void store4(uint16_t* p, const int* Y) {
+        *reinterpret_cast<uint2*>(p) = make_uint2((uint32_t)Y[0] | (uint32_t)Y[1] << 16, (uint32_t)Y[2] | (uint32_t)Y[3] << 16);
+    }
+    static __device__ __forceinline__ void store2(uint16_t* p, int a, int b) { *reinterpret_cast<uint32_t*>(p) = (uint32_t)a | (uint32_t)b << 16; }
+};
+
+template <typename P> __device__ __forceinline__ int yuv_clampv(int v) { return v < 0 ? 0 : (v > yuv_px<P>::maxv ? yuv_px<P>::maxv : v); }
+__device__ __forceinline__ long long yuv_clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// luma of the 2 x 4 block rgb (columns < valid, valid = 2 or 4) and its one or two chroma pairs
+template <typename P>
+__device__ __forceinline__ void yuv_encode_block(const int (&rgb)[2][4][3], const YuvEnc& E, int (&Y)[2][4], int (&U)[2],
+                                                 int (&V)[2]) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            Y[r][k] = yuv_clampv<P>(((E.yr * rgb[r][k][0] + E.yg * rgb[r][k][1] + E.yb * rgb[r][k][2] + (1 << 13)) >> 14) + E.yo);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        int su = 0, sv = 0;
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 2 * j; k < 2 * j + 2; ++k) {
+                su += E.ur * rgb[r][k][0] + E.ug * rgb[r][k][1] + E.ub * rgb[r][k][2];
+                sv += E.vr * rgb[r][k][0] + E.vg * rgb[r][k][1] + E.vb * rgb[r][k][2];
+            }
+        U[j] = yuv_clampv<P>(((su + (1 << 15)) >> 16) + yuv_px<P>::mid);
+        V[j] = yuv_clampv<P>(((sv + (1 << 15)) >> 16) + yuv_px<P>::mid);
+    }
+}
+
+// the planes' samples of one encoded block at the even position (by, bx) of an [OH, OW] frame; valid = 2 or 4 columns
+template <typename P>
+__device__ __forceinline__ void yuv_store_block(P* __restrict__ yp, P* __restrict__ up, P* __restrict__ vp, long long OW,
+                                                long long by, long long bx, int valid, const int (&Y)[2][4], const int (&U)[2],
+                                                const int (&V)[2]) {
+    typedef yuv_px<P> px;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        P* p = yp + (by + r) * OW + bx;
+        if ((reinterpret_cast<uintptr_t>(p) & (4 * sizeof(P) - 1)) == 0 && valid == 4) {
+            px::store4(p, Y[r]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < valid) p[k] = (P)Y[r][k];
+        }
+    }
+    const long long co = (by >> 1) * (OW >> 1) + (bx >> 1);
+    P* pu = up + co;
+    P* pv = vp + co;
+    if ((reinterpret_cast<uintptr_t>(pu) & (2 * sizeof(P) - 1)) == 0 && valid == 4) px::store2(pu, U[0], U[1]);
+    else {
+        pu[0] = (P)U[0];
+        if (valid == 4) pu[1] = (P)U[1];
+    }
+    if ((reinterpret_cast<uintptr_t>(pv) & (2 * sizeof(P) - 1)) == 0 && valid == 4) px::store2(pv, V[0], V[1]);
+    else {
+        pv[0] = (P)V[0];
+        if (valid == 4) pv[1] = (P)V[1];
+    }
+}
+
+template <typename P> __device__ __forceinline__ int yuv_quant(float v) {
+    const float f = fminf(fmaxf(v, 0.0f), 1.0f);
+    return (int)rintf(__fmul_rn(f, (float)yuv_px<P>::maxv));
+}
+
+static YuvDec yuv_dec(const int32_t* c) { return YuvDec{c[0], c[1], c[2], c[3], c[4], c[5]}; }
+static YuvEnc yuv_enc(const int32_t* c) { return YuvEnc{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]}; }
+
+// the 14-bit tables of every matrix / range stay below these bounds, which keep each sum below 2^24 (2^26 for the
+// four-pixel chroma sum): int32 cannot overflow whatever the caller passes
+static bool yuv_coeffs_ok(const int32_t* c, int n) {
+    if (c[0] < 0 || c[0] > 255) return false;
+    for (int i = 1; i < n; ++i)
+        if (c[i] < -(1 << 16) || c[i] > (1 << 16)) return false;
+    return true;
+}
+
+}  // namespace ofasr
+
+#define YUV_REQUIRE_FRAME(H, W)                                                                                          \
+    OFASR_REQUIRE((H) >= 2 && (W) >= 2, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);                          \
+    OFASR_REQUIRE((H) % 2 == 0 && (W) % 2 == 0, OFASR_ERR_INVALID_ARG, "%s: a 4:2:0 frame needs even sides, got %lldx%lld", \
+                  name, (long long)(H), (long long)(W));                                                                 \
+    OFASR_REQUIRE((H) <= (1LL << 40) / (W), OFASR_ERR_UNSUPPORTED, "%s: too large a frame", name)
+
+// 16-bit planes: the one depth this library defines, and plane pointers aligned for their samples
+#define YUV_REQUIRE_P16(depth, y, u, v)                                                                                  \
+    OFASR_REQUIRE((depth) == 10, OFASR_ERR_INVALID_ARG, "%s: depth %d is not supported (10 only)", name, (int)(depth));  \
+    OFASR_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(v)) & 1) == 0, \
+                  OFASR_ERR_INVALID_ARG, "%s: a 16-bit plane pointer is not 2-byte aligned", name)

@@ -38,13 +38,24 @@ ofasr_window_diff_yuv420, compacts their table rows with ofasr_window_compact (c
 in batches of the full plan's batch size, so that every forward has the shape of the non-reuse path and replays the
 same captured graph: the output equals upscale_yuv420's bit for bit.  The comparison is exact, so it does nothing for
 camera noise.
+
+Target-size output (`out_size=(TH, TW)`, `resample`): the result is DEFINED as Pillow's Image.resize of the quantised
+full-size output (resize.py), and the resize is fused into the scatter (ofasr_tile_resize_scatter_*,
+csrc/resize_scatter.hip), so the full-size frame never exists.  With S = scale * L full-size pixels and T target pixels on
+an axis, L <= T <= S.  A core covering the full-size pixels [a, b) owns the target pixels [t(a), t(b)), t(p) =
+ceil(p T / S) (rounded up to even for YUV planes, capped at T): the cores' rectangles tile the target exactly once.  Those
+target pixels read full-size pixels a little outside the core, by at most `extra` input pixels, which plan_resize
+computes from the coefficient tables themselves (the largest overhang of [xmin, xmin + count) over the owning core); the
+halo becomes radius + extra, so every pixel a window's rectangle reads lies at least `radius` input pixels inside the
+window's non-image edges, where the window's output equals the whole-image forward's.  plan_resize checks that for every
+window.  Hence tiled = whole, as before.  T = S on both axes is today's plan, halo and kernels, bit for bit.
 """
 import math
 from fractions import Fraction
 
 import torch
 
-from . import _C, ops
+from . import _C, ops, resize
 from .graphed import GraphedEval
 
 LIMIT = 2 ** 31          # no activation of one window reaches 2^31 bytes (fp32); no batched tensor 2^31 elements
@@ -146,6 +157,11 @@ def _up(v, m):
     return -(-v // m) * m
 
 
+def _px(px_elems, scale):
+    """activation elements per input pixel of a window: px_elems, or a bound for the networks of this project"""
+    return px_elems if px_elems is not None else max(384, 64 * scale * scale, 3 * scale * scale)
+
+
 class TilePlan(object):
     """windows of one image: all win_h x win_w; windows[i] = (wy, wx, cy, cx, ch, cw): window origin and core rectangle,
     in input pixels.  `batch` is the most windows one batch may hold (no batched tensor reaches 2^31 elements)."""
@@ -199,9 +215,127 @@ def plan_windows(H, W, core, halo, align=1, scale=4, px_elems=None, height8=Fals
     win_h, rows = _axis(H, core, halo, align, m8 if height8 else align)
     win_w, cols = _axis(W, core, halo, align, m8)
     windows = [(wy, wx, cy, cx, ch, cw) for (wy, cy, ch) in rows for (wx, cx, cw) in cols]
-    px = px_elems if px_elems is not None else max(384, 64 * scale * scale, 3 * scale * scale)
-    batch = max(1, min(MAX_WINDOWS, (LIMIT - 1) // (px * win_h * win_w)))
+    batch = max(1, min(MAX_WINDOWS, (LIMIT - 1) // (_px(px_elems, scale) * win_h * win_w)))
     return TilePlan(H, W, win_h, win_w, windows, scale, batch)
+
+
+class ResizePlan(TilePlan):
+    """a TilePlan for a target size: out_h x out_w, the filter, targets[i] = (dy, dx, eh, ew), the target rectangle that
+    window i owns (possibly empty), `extra` (input pixels added to the halo), `halo`, and `core`, the core side the
+    windows were planned with (plan_resize may have shrunk the one it was given)"""
+
+    def __init__(self, plan, out_h, out_w, resample, even, targets, extra, halo, radius, core=None):
+        TilePlan.__init__(self, plan.H, plan.W, plan.win_h, plan.win_w, plan.windows, plan.scale, plan.batch)
+        self.out_h, self.out_w, self.resample, self.even = out_h, out_w, resample, even
+        self.targets, self.extra, self.halo, self.radius, self.core = targets, extra, halo, radius, core
+        self._device_tables = {}
+
+    def tables(self, depth=8):
+        """(vertical, horizontal) coefficient tables of a sample depth (numpy int32, resize.axis_table)"""
+        return (resize.axis_table(self.H * self.scale, self.out_h, self.resample, depth),
+                resize.axis_table(self.W * self.scale, self.out_w, self.resample, depth))
+
+    def device_tables(self, depth, device):
+        """tables(depth) as int32 tensors on `device`, uploaded once per depth and device and kept with the plan"""
+        key = (depth, str(device))
+        if key not in self._device_tables:
+            self._device_tables[key] = tuple(torch.from_numpy(t).to(device) for t in self.tables(depth))
+        return self._device_tables[key]
+
+
+def check_out_size(H, W, scale, out_size, even=False):
+    """(TH, TW) of an `out_size` for an H x W input, or a ValueError that names the allowed range"""
+    try:
+        TH, TW = (int(v) for v in out_size)
+    except (TypeError, ValueError):
+        raise ValueError("out_size must be (height, width), got %r" % (out_size,))
+    if not (H <= TH <= H * scale and W <= TW <= W * scale):
+        raise ValueError("out_size %dx%d is outside what a %dx%d input allows: width %d .. %d, height %d .. %d (never "
+                         "smaller than the input, never larger than the network's x%d output)"
+                         % (TW, TH, W, H, W, W * scale, H, H * scale, scale))
+    if even and (TH % 2 or TW % 2):
+        raise ValueError("a YUV 4:2:0 output needs even sides, got out_size %dx%d" % (TW, TH))
+    if scale > 4 and (TH, TW) != (H * scale, W * scale):
+        raise ValueError("out_size needs an upscale factor of at most 4 (the resampling scatter holds the source rows of "
+                         "a 4 : 1 reduction), this network's is %d" % scale)
+    return TH, TW
+
+
+def _axis_targets(cores, s, T, L, even):
+    """[(t0, t1)] per core (core start, core length) of an axis of L input pixels"""
+    S = s * L
+    return [(resize.target_edge(c0 * s, S, T, even), resize.target_edge((c0 + cl) * s, S, T, even)) for (c0, cl) in cores]
+
+
+def _axis_extra(cores, s, T, L, even, table):
+    """the largest overhang, in input pixels rounded up, of the source range a core's target pixels read over the core"""
+    over = 0
+    for (c0, cl), (t0, t1) in zip(cores, _axis_targets(cores, s, T, L, even)):
+        need = resize.needed_range(table, t0, t1)
+        if need is not None:
+            over = max(over, c0 * s - need[0], need[1] - (c0 + cl) * s)
+    return -(-over // s)
+
+
+def attach_targets(plan, out_h, out_w, resample, even, radius, extra=0, halo=0, core=None):
+    """the ResizePlan of a TilePlan: each window's target rectangle, after checking that the full-size pixels it reads lie
+    inside the window's exact region (the window minus radius * scale on every side that is not an image edge)"""
+    s = plan.scale
+    vt = resize.axis_table(plan.H * s, out_h, resample)
+    ht = resize.axis_table(plan.W * s, out_w, resample)
+    targets = []
+    for (wy, wx, cy, cx, ch, cw) in plan.windows:
+        (ty0, ty1), = _axis_targets([(cy, ch)], s, out_h, plan.H, even)
+        (tx0, tx1), = _axis_targets([(cx, cw)], s, out_w, plan.W, even)
+        for tab, t0, t1, w0, wl, L, what in ((vt, ty0, ty1, wy, plan.win_h, plan.H, "rows"),
+                                             (ht, tx0, tx1, wx, plan.win_w, plan.W, "columns")):
+            need = resize.needed_range(tab, t0, t1)
+            if need is None:
+                continue
+            lo = (w0 + (radius if w0 > 0 else 0)) * s
+            hi = (w0 + wl - (radius if w0 + wl < L else 0)) * s
+            if need[0] < lo or need[1] > hi:
+                raise ValueError("the %s [%d, %d) that the target of window (%d, %d) reads leave its exact region [%d, %d)"
+                                 % (what, need[0], need[1], wy, wx, lo, hi))
+        targets.append((ty0, tx0, ty1 - ty0, tx1 - tx0))
+    return ResizePlan(plan, out_h, out_w, resample, even, targets, extra, halo, radius, core)
+
+
+def plan_resize(H, W, out_size, resample, core, radius, align=1, scale=4, px_elems=None, height8=False, even=False):
+    """the tile plan of an H x W input for the target size out_size = (TH, TW): plan_windows with the halo widened by
+    what the filter reads outside a core (see the module docstring).  TH x TW equal to the network's own output size:
+    plan_windows(H, W, core, radius rounded up to align, ...) itself, today's plan.  The wider halo must not push a window
+    over the 2^31-byte limit that `core` was sized for (default_core knows the plain halo only): where the plain plan's
+    window keeps an fp32 activation below LIMIT and the widened one does not, the core shrinks, by the side multiple at
+    a time, until it does again; a core that cannot shrink further is a ValueError."""
+    resize.check_filter(resample)
+    H, W, s, core, align = int(H), int(W), int(scale), int(core), int(align)
+    TH, TW = check_out_size(H, W, s, out_size, even)
+    halo0 = _up(max(int(radius), 0), align)
+    base = plan_windows(H, W, core, halo0, align, s, px_elems, height8)
+    if (TH, TW) == (H * s, W * s):
+        return base
+    px4 = 4 * _px(px_elems, s)
+    fits = px4 * base.win_h * base.win_w < LIMIT
+    step = align * 8 // math.gcd(align, 8)
+    tabs = (resize.axis_table(H * s, TH, resample), resize.axis_table(W * s, TW, resample))
+    while True:
+        extra = 0
+        for L, T, tab, cores in ((H, TH, tabs[0], sorted(set((w[2], w[4]) for w in base.windows))),
+                                 (W, TW, tabs[1], sorted(set((w[3], w[5]) for w in base.windows)))):
+            if len(cores) > 1:          # one core is the whole axis: nothing lies outside it
+                extra = max(extra, _axis_extra(cores, s, T, L, even, tab))
+        halo = _up(int(radius) + extra, align)
+        plan = plan_windows(H, W, core, halo, align, s, px_elems, height8)
+        if not fits or px4 * plan.win_h * plan.win_w < LIMIT:
+            return attach_targets(plan, TH, TW, resample, even, int(radius), extra, halo, core)
+        if core - step < max(align, 1):
+            raise ValueError("with the halo of %d that out_size %dx%d (%s) needs, a window of core %d is %dx%d and an fp32 "
+                             "activation of it would reach 2^31 bytes, and the core cannot shrink further: there is no "
+                             "core (--core) for this network at this target size"
+                             % (halo, TW, TH, resample, core, plan.win_w, plan.win_h))
+        core -= step
+        base = plan_windows(H, W, core, halo0, align, s, px_elems, height8)
 
 
 def default_core(halo, align, px_elems):
@@ -296,6 +430,54 @@ def tile_scatter_yuv420(src, table, y, u, v, max_eh, max_ew, matrix="bt601", ful
                                                        _CODES[src.dtype], table.data_ptr(), depth, coeffs, y.data_ptr(),
                                                        u.data_ptr(), v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()),
                  "ofasr_tile_scatter_yuv420p16")
+    return y, u, v
+
+
+def _resize_args(name, src, table, vtab, htab, TH, TW):
+    ops._gpu(src)
+    if not src.is_contiguous() or src.dim() != 4 or src.size(1) != 3:
+        raise ValueError("%s needs a contiguous [n, 3, h, w] source" % name)
+    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2 or \
+            table.size(1) != 6 or table.size(0) > src.size(0) or table.size(0) < 1:
+        raise ValueError("%s needs a contiguous int64 table [n, 6] on the GPU, one row per source window at most" % name)
+    for t, rows, what in ((vtab, TH, "vertical"), (htab, TW, "horizontal")):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.size(0) != rows or \
+                not 3 <= t.size(1) <= 2 + resize.MAX_TAPS:
+            raise ValueError("%s needs a contiguous int32 %s coefficient table [%d, 2 + taps] on the GPU, taps <= %d"
+                             % (name, what, rows, resize.MAX_TAPS))
+
+
+def tile_resize_scatter(src, table, vtab, htab, img, max_eh, max_ew):
+    """src: network output [n, 3, sh, sw]; table: int64 [n, 6] (oy, ox, dy, dx, eh, ew) on the GPU: each window's origin in
+    the full-size output and its target rectangle; vtab / htab: int32 coefficient tables [TH, 2 + kh] / [TW, 2 + kw] on the
+    GPU (resize.axis_table, depth 8); writes Pillow's resize of the quantised full-size output into the rectangles of the
+    HWC uint8 image img [TH, TW, 3] (ofasr_tile_resize_scatter_u8)"""
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.size(2) != 3 or not img.is_contiguous():
+        raise ValueError("tile_resize_scatter needs a contiguous HWC uint8 RGB destination")
+    _resize_args("tile_resize_scatter", src, table, vtab, htab, img.size(0), img.size(1))
+    _C.check(_C.lib().ofasr_tile_resize_scatter_u8(src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype],
+                                                   table.data_ptr(), vtab.data_ptr(), vtab.size(1) - 2, htab.data_ptr(),
+                                                   htab.size(1) - 2, img.data_ptr(), img.size(0), img.size(1), max_eh, max_ew,
+                                                   ops._stream()), "ofasr_tile_resize_scatter_u8")
+    return img
+
+
+def tile_resize_scatter_yuv420(src, table, vtab, htab, y, u, v, max_eh, max_ew, matrix="bt601", full_range=False):
+    """the same into the planes y [TH, TW], u, v [TH/2, TW/2] through the 2x2 encode of tile_scatter_yuv420: dy, dx, eh,
+    ew even (the kernel clears their low bit).  uint16 planes are a 10-bit frame: quantised to 1023 levels, resampled
+    with the tables of depth 10 (20 coefficient bits) and encoded at depth 10 (ofasr_tile_resize_scatter_yuv420 /
+    _yuv420p16)"""
+    TH, TW = ops.yuv420_planes(y, u, v, "tile_resize_scatter_yuv420")
+    _resize_args("tile_resize_scatter_yuv420", src, table, vtab, htab, TH, TW)
+    depth = ops.YUV_DEPTHS[y.dtype]
+    coeffs = ops.yuv_table(matrix, full_range, True, depth)
+    head = (src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype], table.data_ptr(), vtab.data_ptr(),
+            vtab.size(1) - 2, htab.data_ptr(), htab.size(1) - 2)
+    tail = (coeffs, y.data_ptr(), u.data_ptr(), v.data_ptr(), TH, TW, max_eh, max_ew, ops._stream())
+    if depth == 8:
+        _C.check(_C.lib().ofasr_tile_resize_scatter_yuv420(*(head + tail)), "ofasr_tile_resize_scatter_yuv420")
+    else:
+        _C.check(_C.lib().ofasr_tile_resize_scatter_yuv420p16(*(head + (depth,) + tail)), "ofasr_tile_resize_scatter_yuv420p16")
     return y, u, v
 
 
@@ -430,10 +612,31 @@ class TiledUpscaler(object):
         self.dtype = _DTYPES[mix_prec]
         self.autocast_dtype = None if mix_prec == "f32" else self.dtype
         self.graphed = GraphedEval(net, autocast_dtype=self.autocast_dtype, copy_output=False) if graphed else None
+        self._plans = {}
 
-    def plan(self, H, W):
-        return plan_windows(H, W, self.core, self.halo, self.align, self.scale, self.px_elems,
-                            height8=self.self_ensemble == 8)
+    def plan(self, H, W, out_size=None, resample="lanczos", even=False):
+        """the tile plan of an H x W input; with `out_size` = (TH, TW) the ResizePlan of that target (kept: its tables
+        take a pass over every target row and column), which for TH x TW = the network's own size is the plain plan.
+        Up to 8 plans are kept and all are dropped when a ninth comes, with their device tables: a directory of images
+        of more than 8 sizes recomputes and uploads its tables again each time round, a video never does."""
+        if out_size is None:
+            return plan_windows(H, W, self.core, self.halo, self.align, self.scale, self.px_elems,
+                                height8=self.self_ensemble == 8)
+        key = (int(H), int(W), tuple(int(v) for v in out_size), resample, bool(even))
+        if key not in self._plans:
+            if len(self._plans) >= 8:
+                self._plans.clear()
+            self._plans[key] = plan_resize(H, W, out_size, resample, self.core, self.radius, self.align, self.scale,
+                                           self.px_elems, self.self_ensemble == 8, even)
+        return self._plans[key]
+
+    def _whole_resize_plan(self, H, W, out_size, resample, even):
+        resize.check_filter(resample)
+        TH, TW = check_out_size(H, W, self.scale, out_size, even)
+        plan = self._whole_plan(H, W)
+        if (TH, TW) == (H * self.scale, W * self.scale):
+            return plan
+        return attach_targets(plan, TH, TW, resample, even, self.radius)
 
     def _whole_plan(self, H, W):
         if H % self.align or W % self.align:
@@ -471,11 +674,11 @@ class TiledUpscaler(object):
             raise _C.OfasrError("TiledUpscaler needs the network on the GPU")
         return img.to(dev).contiguous()
 
-    def _run(self, img, whole, sink):
+    def _run(self, img, whole, sink, plan=None):
         """run every batch of the plan; sink(y, real, tables, plan) consumes the network output of a batch"""
         img = self._image(img)
         return self._run_windows(img.size(0), img.size(1), img.device, whole, sink,
-                                 lambda origins, h, w: tile_gather(img, origins, h, w, self.dtype))
+                                 lambda origins, h, w: tile_gather(img, origins, h, w, self.dtype), plan)
 
     def _batching(self, plan):
         """(batches, windows per batch) of a plan: as many windows per batch as the plan and `batch` allow, spread evenly"""
@@ -486,14 +689,17 @@ class TiledUpscaler(object):
 
     def _tables(self, plan, device):
         """the plan's device tables: window origins [nb * B, 2], the last batch padded by repeating a window, and the
-        scatter rows [n, 6] = (sy, sx, dy, dx, eh, ew) in output pixels"""
+        scatter rows [n, 6] = (sy, sx, dy, dx, eh, ew) in output pixels; for a ResizePlan the rows of the resampling
+        scatter, (oy, ox, dy, dx, eh, ew): the window's origin in full-size pixels and its target rectangle"""
         s = self.scale
         nb, B = self._batching(plan)
         wins = plan.windows + [plan.windows[-1]] * (nb * B - len(plan))
         origins = torch.tensor([[wy, wx] for (wy, wx, _, _, _, _) in wins], dtype=torch.int64).to(device)
-        table = torch.tensor([[(cy - wy) * s, (cx - wx) * s, cy * s, cx * s, ch * s, cw * s]
-                              for (wy, wx, cy, cx, ch, cw) in plan.windows], dtype=torch.int64).to(device)
-        return origins, table
+        if isinstance(plan, ResizePlan):
+            rows = [[w[0] * s, w[1] * s] + list(t) for w, t in zip(plan.windows, plan.targets)]
+        else:
+            rows = [[(cy - wy) * s, (cx - wx) * s, cy * s, cx * s, ch * s, cw * s] for (wy, wx, cy, cx, ch, cw) in plan.windows]
+        return origins, torch.tensor(rows, dtype=torch.int64).to(device)
 
     def _run_batches(self, plan, origins, table, n, B, sink, gather, wins=None):
         """the batch loop: the first n rows of `origins` (padded to a multiple of B) / `table` in batches of B windows.
@@ -508,19 +714,42 @@ class TiledUpscaler(object):
                 real = min(B, n - b * B)
                 sink(y, real, table[b * B:b * B + real], wins[b * B:b * B + real] if wins is not None else None, plan)
 
-    def _run_windows(self, H, W, device, whole, sink, gather):
+    def _run_windows(self, H, W, device, whole, sink, gather, plan=None):
         """the same for any source of windows: gather(origins, h, w) -> the [n, 3, h, w] batch of self.dtype"""
-        plan = self._whole_plan(H, W) if whole else self.plan(H, W)
+        if plan is None:
+            plan = self._whole_plan(H, W) if whole else self.plan(H, W)
         _, B = self._batching(plan)
         origins, table = self._tables(plan, device)
         self._run_batches(plan, origins, table, len(plan), B, sink, gather, plan.windows)
         return plan
 
-    def upscale(self, img, whole=False):
+    def _target_plan(self, H, W, whole, out_size, resample, even):
+        """None without `out_size` or for the network's own size (today's path), else the ResizePlan"""
+        if out_size is None:
+            return None
+        plan = self._whole_resize_plan(H, W, out_size, resample, even) if whole else self.plan(H, W, out_size, resample, even)
+        return plan if isinstance(plan, ResizePlan) else None
+
+    def upscale(self, img, whole=False, out_size=None, resample="lanczos"):
         """HWC uint8 RGB -> HWC uint8 RGB (scale x) on the GPU.  whole=True: one forward of the whole image (parity;
-        refuses images whose activations would reach 2^31 bytes)"""
+        refuses images whose activations would reach 2^31 bytes).  out_size = (TH, TW), between the input's size and the
+        network's own on each axis: the output has that size and equals PIL's Image.fromarray(upscale(img)).resize((TW,
+        TH), resample) bit for bit ("lanczos" or "bicubic"), resampled inside the scatter (tile_resize_scatter)"""
         H, W = int(img.shape[0]), int(img.shape[1])
         out = None
+        rplan = self._target_plan(H, W, whole, out_size, resample, False)
+        if rplan is not None:
+            max_eh, max_ew = max(t[2] for t in rplan.targets), max(t[3] for t in rplan.targets)
+
+            def rsink(y, real, table, wins, plan):
+                nonlocal out
+                if out is None:
+                    out = torch.empty(plan.out_h, plan.out_w, 3, dtype=torch.uint8, device=y.device)
+                vtab, htab = plan.device_tables(8, y.device)
+                tile_resize_scatter(y.contiguous(), table, vtab, htab, out, max_eh, max_ew)
+
+            self._run(img, whole, rsink, rplan)
+            return out
 
         def sink(y, real, table, wins, plan):
             nonlocal out
@@ -564,17 +793,35 @@ class TiledUpscaler(object):
         return (torch.empty(H * s, W * s, dtype=dt, device=dev), torch.empty(H * s // 2, W * s // 2, dtype=dt, device=dev),
                 torch.empty(H * s // 2, W * s // 2, dtype=dt, device=dev))
 
-    def upscale_yuv420(self, y, u, v, matrix="bt601", full_range=False, whole=False, out_depth=None):
+    def upscale_yuv420(self, y, u, v, matrix="bt601", full_range=False, whole=False, out_depth=None, out_size=None,
+                       resample="lanczos"):
         """one planar YUV 4:2:0 frame (uint8 planes y [H, W], u, v [H/2, W/2]; CPU or GPU tensors, or numpy arrays) ->
         the upscaled planes (Y [H*s, W*s], U, V [H*s/2, W*s/2]) on the GPU.  The same plan, graph replay and self-ensemble
         as upscale(); the colour conversion is fused into the two tile moves (tile_gather_yuv420 / tile_scatter_yuv420),
         so no RGB frame exists on either side: the result equals
         ops.rgb_to_yuv420_u8(upscale(ops.yuv420_to_rgb_u8(y, u, v))) bit for bit.  uint16 planes are a 10-bit frame.
         `out_depth` (8 or 10; None: the input's) is the depth of the output planes, whatever the input's: 8 -> 10 writes
-        the network's output at 1024 levels instead of rounding it to 256."""
+        the network's output at 1024 levels instead of rounding it to 256.  out_size = (TH, TW), even, between the
+        input's size and the network's own: planes of that size, equal to the encode (ops.rgb_to_yuv420_u8, at the
+        output depth) of resize.resize_host of the quantised full-size RGB, resampled inside the scatter."""
         dev, (y, u, v), H, W = self._yuv420_frame(y, u, v)
         s = self.scale
-        out = self._yuv420_out(H, W, s, ops.YUV_DEPTHS[y.dtype] if out_depth is None else out_depth, dev)
+        depth = ops.YUV_DEPTHS[y.dtype] if out_depth is None else out_depth
+        rplan = self._target_plan(H, W, whole, out_size, resample, True)
+        if rplan is not None:
+            out = self._yuv420_out(rplan.out_h, rplan.out_w, 1, depth, dev)
+            vtab, htab = rplan.device_tables(depth, dev)
+            max_eh, max_ew = max(t[2] for t in rplan.targets), max(t[3] for t in rplan.targets)
+
+            def rsink(t, real, table, wins, plan):
+                tile_resize_scatter_yuv420(t.contiguous(), table, vtab, htab, out[0], out[1], out[2], max_eh, max_ew, matrix,
+                                           full_range)
+
+            self._run_windows(H, W, dev, whole, rsink,
+                              lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range),
+                              rplan)
+            return out
+        out = self._yuv420_out(H, W, s, depth, dev)
 
         def sink(t, real, table, wins, plan):
             tile_scatter_yuv420(t.contiguous(), table, out[0], out[1], out[2], max(w[4] for w in wins) * s,
@@ -584,10 +831,10 @@ class TiledUpscaler(object):
                           lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range))
         return out
 
-    def yuv420_stream(self, matrix="bt601", full_range=False, out_depth=None):
+    def yuv420_stream(self, matrix="bt601", full_range=False, out_depth=None, out_size=None, resample="lanczos"):
         """a YUV420Stream on this upscaler: upscale_yuv420 for the consecutive frames of one video, re-running only the
         windows whose input bytes changed since the previous frame; the same output bit for bit"""
-        return YUV420Stream(self, matrix, full_range, out_depth)
+        return YUV420Stream(self, matrix, full_range, out_depth, out_size, resample)
 
     def upscale_float(self, img, whole=False):
         """the network's fp32 output [3, H*scale, W*scale] before quantisation, assembled from the same window cores
@@ -649,12 +896,14 @@ class YUV420Stream(object):
     input's).  The comparison is exact: it pays off on content that repeats bit for bit and does nothing for camera
     noise."""
 
-    def __init__(self, upscaler, matrix="bt601", full_range=False, out_depth=None):
+    def __init__(self, upscaler, matrix="bt601", full_range=False, out_depth=None, out_size=None, resample="lanczos"):
         ops.yuv_table(matrix, full_range, False)       # refuses an unknown matrix now rather than at the first frame
         if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in ops.YUV_DTYPES):
             raise ValueError("out_depth must be 8 or 10, got %r" % (out_depth,))
+        resize.check_filter(resample)
         self.up = upscaler
         self.matrix, self.full_range, self.out_depth = matrix, full_range, out_depth
+        self.out_size, self.resample = out_size, resample
         self.stats = StreamStats()
         self._size = None
         self._fresh = self._all = True
@@ -667,18 +916,25 @@ class YUV420Stream(object):
     def _setup(self, H, W, dev, dtype):
         up = self.up
         s = up.scale
-        plan = up.plan(H, W)
+        plan = up.plan(H, W) if self.out_size is None else up.plan(H, W, self.out_size, self.resample, True)
         if len(plan) > MAX_WINDOWS:
             raise ValueError("a %dx%d frame makes %d windows with core %d; a stream takes at most %d: use a larger core"
                              % (W, H, len(plan), up.core, MAX_WINDOWS))
         self._plan = plan
         _, self._B = up._batching(plan)
         self._origins, self._table = up._tables(plan, dev)
-        self._max_eh = max(w[4] for w in plan.windows) * s
-        self._max_ew = max(w[5] for w in plan.windows) * s
+        depth = ops.YUV_DEPTHS[dtype] if self.out_depth is None else self.out_depth
+        self._coeffs = None
+        if isinstance(plan, ResizePlan):               # a window's target rectangle depends on that window's bytes alone
+            self._max_eh, self._max_ew = max(t[2] for t in plan.targets), max(t[3] for t in plan.targets)
+            self._coeffs = plan.device_tables(depth, dev)
+        else:
+            self._max_eh = max(w[4] for w in plan.windows) * s
+            self._max_ew = max(w[5] for w in plan.windows) * s
         self._prev = (torch.empty(H, W, dtype=dtype, device=dev), torch.empty(H // 2, W // 2, dtype=dtype, device=dev),
                       torch.empty(H // 2, W // 2, dtype=dtype, device=dev))
-        self._out = up._yuv420_out(H, W, s, ops.YUV_DEPTHS[dtype] if self.out_depth is None else self.out_depth, dev)
+        self._out = up._yuv420_out(plan.out_h, plan.out_w, 1, depth, dev) if self._coeffs is not None else \
+            up._yuv420_out(H, W, s, depth, dev)
         n = len(plan)
         self._flags = torch.zeros(n, window_diff_slabs(plan.win_h, plan.win_w), dtype=torch.int32, device=dev)
         self._compact = (torch.zeros(self._origins.size(0), 2, dtype=torch.int64, device=dev),
@@ -705,8 +961,12 @@ class YUV420Stream(object):
         out = self._out
 
         def sink(t, real, table, wins, plan):
-            tile_scatter_yuv420(t.contiguous(), table, out[0], out[1], out[2], self._max_eh, self._max_ew, self.matrix,
-                                self.full_range)
+            if self._coeffs is not None:
+                tile_resize_scatter_yuv420(t.contiguous(), table, self._coeffs[0], self._coeffs[1], out[0], out[1], out[2],
+                                           self._max_eh, self._max_ew, self.matrix, self.full_range)
+            else:
+                tile_scatter_yuv420(t.contiguous(), table, out[0], out[1], out[2], self._max_eh, self._max_ew, self.matrix,
+                                    self.full_range)
 
         def gather(origins, h, w):
             return tile_gather_yuv420(y, u, v, origins, h, w, up.dtype, self.matrix, self.full_range)

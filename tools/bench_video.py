@@ -18,8 +18,14 @@ cost of what the stream adds to a frame where nothing is skipped: diff + compact
 --depth 10 runs the same on a 10-bit frame (uint16 planes, the 16-bit tile moves and window diff), --out-depth 8|10 sets
 the output's depth independently (default: the input's; 8 -> 10 is the 8-bit gather with the 16-bit scatter).  There is no
 whole-frame 10-bit kernel, so (b) is left out whenever either depth is 10.
+
+--out-size WxH measures target-size output (upscale_yuv420(out_size=...), the resampling scatter) beside the full-size
+frame: "fused" and "target" are timed alternately, twice each, in the same process ("ms_rounds"); the record adds the
+plan overhead (window pixels per input pixel) with and without the target, the scatter's own time per frame from the
+library's launch events of one profiled frame ("scatter_ms": the full-size and the resampling scatter), and the bytes a
+frame copies to the host at either size.  --resample bicubic|lanczos picks the filter.
 usage: python tools/bench_video.py [--size 1080 1920] [--reps 3] [--precs f32 bf16] [--reuse 0 0.5 0.9 1.0] [--core N]
-       [--batch N] [--depth 8|10] [--out-depth 8|10]"""
+       [--batch N] [--depth 8|10] [--out-depth 8|10] [--out-size WxH] [--resample lanczos]"""
 import argparse
 import importlib
 import json
@@ -138,8 +144,18 @@ def main():
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--depth", type=int, default=8, choices=[8, 10], help="bits per input sample")
     ap.add_argument("--out-depth", type=int, default=None, choices=[8, 10], help="bits per output sample (default: --depth)")
+    ap.add_argument("--out-size", default=None, metavar="WxH", help="also measure this target size (even sides)")
+    ap.add_argument("--resample", default="lanczos", choices=["bicubic", "lanczos"])
     a = ap.parse_args()
     import torch
+    C = importlib.import_module(PKG + "._C")
+    target = None
+    if a.out_size is not None:
+        try:
+            tw, th = importlib.import_module(PKG + ".resize").parse_size(a.out_size)
+        except ValueError as e:
+            raise SystemExit("--out-size: %s" % e)
+        target = (th, tw)
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
     st = importlib.import_module(PKG + ".imagenet_codebase.networks.sr_static")
     up = importlib.import_module(PKG + ".upscale")
@@ -195,6 +211,33 @@ def main():
                     tu._forward(x)
 
         paths = {"fused": fused, "unfused": unfused} if a.depth == out_depth == 8 else {"fused": fused}
+        extra = {}
+        if target is not None:
+            def resized():
+                return tu.upscale_yuv420(y, u, v, out_depth=out_depth, out_size=target, resample=a.resample)
+
+            tplan = tu.plan(H, W, target, a.resample, True)
+            rounds = {"fused": [], "target": []}
+            for _ in range(2):                             # alternating, same process
+                rounds["fused"].append(round(event_ms(fused, a.reps), 2))
+                rounds["target"].append(round(event_ms(resized, a.reps), 2))
+            scatter = {}
+            for name, fn in (("fused", fused), ("target", resized)):
+                C.profile_read()
+                C.lib().ofasr_profile_enable(1)
+                fn()
+                torch.cuda.synchronize()
+                prof = C.profile_read()
+                C.lib().ofasr_profile_enable(0)
+                scatter[name] = round(sum(v["total_us"] for k, v in prof.items() if "scatter" in k) / 1e3, 3)
+            bps = 1 if out_depth == 8 else 2
+            extra = {"out_size": [target[1], target[0]], "resample": a.resample, "ms_rounds": rounds, "scatter_ms": scatter,
+                     "overhead": {"full": round(plan.overhead(), 3), "target": round(tplan.overhead(), 3)},
+                     "windows_target": len(tplan), "window_target": [tplan.win_h, tplan.win_w],
+                     "halo": {"full": tu.halo, "target": getattr(tplan, "halo", tu.halo)},
+                     "host_bytes_per_frame": {"full": H * W * tu.scale ** 2 * 3 // 2 * bps,
+                                              "target": target[0] * target[1] * 3 // 2 * bps},
+                     "peak_extra_MiB_target": peak_extra_mb(resized)}
         ms = {k: event_ms(fn, a.reps) for k, fn in paths.items()}
         ms["network"] = event_ms(network, a.reps)
         del batches[:]
@@ -202,6 +245,7 @@ def main():
                "frames_per_s": {k: round(1e3 / ms[k], 3) for k in paths},
                "out_MP_per_s_fused": round(H * W * tu.scale ** 2 / 1e6 / (ms["fused"] / 1e3), 2),
                "peak_extra_MiB": {k: peak_extra_mb(fn) for k, fn in paths.items()}}
+        rec.update(extra)
         out["runs"]["max_" + prec] = rec
         print(prec, rec, file=sys.stderr, flush=True)
         del tu

@@ -7,7 +7,11 @@ here: export its sub-network first.  Inputs are image files or directories of th
 and every output is written as OUTDIR/<name>.png.  The next image is decoded (and the previous one encoded) on a small
 host thread pool while the GPU upscales the current one.  Prints output megapixels per second at the end.
 --reference DIR scores every output against the equally named ground-truth image in DIR on the GPU (Y-PSNR and Y-SSIM by
-the HIP metric kernel, --shave border pixels left out), prints the numbers and writes them to OUTDIR/quality.json."""
+the HIP metric kernel, --shave border pixels left out), prints the numbers and writes them to OUTDIR/quality.json.
+--out-size WxH writes every output at that size instead of the network's own: any size from the input's up to the
+network's, each axis on its own.  The result equals Pillow's Image.resize (--resample lanczos, the default, or bicubic) of
+the full-size output bit for bit and is computed inside the scatter kernel; the full-size image never exists.  It applies to
+every input: an input that the size does not fit is refused by name.  --reference then compares at the target size."""
 import argparse
 import collections
 import concurrent.futures
@@ -24,6 +28,13 @@ EXTS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp", ".ppm", ".pgm
 WORKERS = 4   # host decode / encode threads
 
 
+def parse_out_size(text):
+    try:
+        return importlib.import_module(PKG + ".resize").parse_size(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0], epilog=__doc__.split("\n\n", 1)[1],
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -38,6 +49,9 @@ def parse_args(argv=None):
     ap.add_argument("--self-ensemble", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
                     help="geometric self-ensemble: average the outputs under the first K of the 8 flips / transposes "
                          "(K times the network time; 2: + horizontal flip, 4: + vertical flips, 8: + transposes)")
+    ap.add_argument("--out-size", type=parse_out_size, default=None, metavar="WxH",
+                    help="output size of every image (default: the network's own): from the input's size up to the network's")
+    ap.add_argument("--resample", default="lanczos", choices=["bicubic", "lanczos"], help="the filter of --out-size")
     ap.add_argument("--reference", default=None, metavar="PATH",
                     help="directory of ground-truth HR images named as the inputs: report Y-PSNR / Y-SSIM per image")
     ap.add_argument("--shave", type=int, default=0, help="with --reference: border pixels left out of the metric")
@@ -124,8 +138,14 @@ def main(argv=None):
             img = pending.popleft().result()
             if i + 2 < len(files):
                 pending.append(pool.submit(decode, files[i + 2]))
-            plan = None if a.whole else up.plan(img.shape[0], img.shape[1])
-            out_gpu = up.upscale(torch.from_numpy(img), whole=a.whole)
+            out_size = None if a.out_size is None else (a.out_size[1], a.out_size[0])
+            try:
+                plan = None if a.whole else up.plan(img.shape[0], img.shape[1], out_size, a.resample)
+                out_gpu = up.upscale(torch.from_numpy(img), whole=a.whole, out_size=out_size, resample=a.resample)
+            except ValueError as e:
+                if a.out_size is None:
+                    raise
+                raise SystemExit("%s: %s" % (f, e))
             if a.reference is not None:
                 ref = decode(refs[i])
                 if ref.shape != tuple(out_gpu.shape):

@@ -20,6 +20,12 @@ words).  --out-depth 8|10 is the depth of the output, by default the input's, an
 --out-depth 10 writes the network's output at 1024 levels instead of rounding it to 256, at no cost in network time.  The
 output Y4M carries the input's C tag when the depths are equal, C420p10 for 8 -> 10 and C420jpeg for 10 -> 8.  --reference
 is opened at the output's depth and scored against its peak (255 or 1023).  --dump-png needs an 8-bit output.
+--out-size WxH writes frames of that size instead of the network's own (1080p -> 3840x2160 with a x4 export, 720p -> 4K,
+576p -> 1080p): any even size from the input's up to the network's, each axis on its own.  The result is defined as
+Pillow's resize (--resample lanczos, the default, or bicubic) of the quantised full-size RGB output, encoded as before;
+it is computed inside the scatter kernel, so the full-size frame never exists and only the target frame is copied to the
+host.  The Y4M header, --reference, --dump-png, --reuse-static, --self-ensemble, --out-depth and --frames all work at
+the target size.
 Prints frames per second and output megapixels per second at the end."""
 import argparse
 import concurrent.futures
@@ -44,6 +50,39 @@ def parse_size(text):
         raise argparse.ArgumentTypeError("expected WxH, got %r" % text)
 
 
+def parse_out_size(text):
+    try:
+        return importlib.import_module(PKG + ".resize").parse_size(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def output_size(W, H, scale, out_size):
+    """(OW, OH) of a W x H input: --out-size (W, H) if upscale.check_out_size takes it for a YUV 4:2:0 frame"""
+    if out_size is None:
+        return W * scale, H * scale
+    try:
+        OH, OW = importlib.import_module(PKG + ".upscale").check_out_size(H, W, scale, (out_size[1], out_size[0]), even=True)
+    except ValueError as e:
+        raise SystemExit("--out-size: %s" % e)
+    return OW, OH
+
+
+def open_writer(video, reader, path, OW, OH, depth, out_depth):
+    """the output file of OW x OH frames: *.y4m keeps a Y4M input's frame rate, interlacing, aspect and X tags, with the C
+    tag of the output's depth; anything else is raw yuv420p"""
+    if not path.lower().endswith(".y4m"):
+        return video.RawYUV420Writer(path, OW, OH, out_depth)
+    y4m = isinstance(reader, video.Y4MReader)
+    if depth == out_depth:
+        chroma = reader.chroma if y4m else ("420jpeg" if depth == 8 else "420p10")
+    else:
+        chroma = "420p10" if out_depth == 10 else "420jpeg"
+    return video.Y4MWriter(path, OW, OH, fps=reader.fps if y4m else None, interlace=reader.interlace if y4m else None,
+                           aspect=reader.aspect if y4m else None, chroma=chroma, xtags=reader.xtags if y4m else (),
+                           depth=out_depth)
+
+
 def parse_frames(text):
     try:
         a, b = text.split(":")
@@ -64,6 +103,9 @@ def parse_args(argv=None):
     ap.add_argument("--depth", type=int, default=None, choices=[8, 10],
                     help="bits per sample of a headerless input (default 8); a Y4M input says it itself")
     ap.add_argument("--out-depth", type=int, default=None, choices=[8, 10], help="bits per output sample (default: the input's)")
+    ap.add_argument("--out-size", type=parse_out_size, default=None, metavar="WxH",
+                    help="output frame size (default: the network's own): even, from the input's size up to the network's")
+    ap.add_argument("--resample", default="lanczos", choices=["bicubic", "lanczos"], help="the filter of --out-size")
     ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
     ap.add_argument("--range", default="tv", choices=["tv", "pc"], help="tv: limited (16..235), pc: full range")
     ap.add_argument("--frames", type=parse_frames, default=(0, None), metavar="A:B", help="frames A .. B-1 only")
@@ -114,23 +156,21 @@ def main(argv=None):
     net = evals.load_static(a.static).cuda()
     up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble)
     s = up.scale
-    OW, OH = W * s, H * s
-    stream = up.yuv420_stream(matrix=a.matrix, full_range=full, out_depth=out_depth) if a.reuse_static else None
-    print("%s x%d: %dx%d -> %dx%d, %s %s, receptive radius %d px, halo %d, core %d, %s%s%s" % (
-        net.name(), s, W, H, OW, OH, a.matrix, a.range, up.radius, up.halo, up.core, a.mix_prec,
+    OW, OH = output_size(W, H, s, a.out_size)
+    out_size = None if a.out_size is None else (OH, OW)
+    try:
+        plan = up.plan(H, W, out_size, a.resample, True)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    stream = up.yuv420_stream(matrix=a.matrix, full_range=full, out_depth=out_depth, out_size=out_size,
+                              resample=a.resample) if a.reuse_static else None
+    print("%s x%d: %dx%d -> %dx%d, %s %s, receptive radius %d px, halo %d, core %d, %s%s%s%s" % (
+        net.name(), s, W, H, OW, OH, a.matrix, a.range, up.radius, getattr(plan, "halo", up.halo),
+        getattr(plan, "core", None) or up.core, a.mix_prec,
         "" if a.self_ensemble == 1 else ", self-ensemble x%d" % a.self_ensemble,
-        "" if depth == out_depth == 8 else ", %d -> %d bits" % (depth, out_depth)))
-    if a.out.lower().endswith(".y4m"):
-        y4m = isinstance(reader, video.Y4MReader)
-        if depth == out_depth:
-            chroma = reader.chroma if y4m else ("420jpeg" if depth == 8 else "420p10")
-        else:
-            chroma = "420p10" if out_depth == 10 else "420jpeg"
-        writer = video.Y4MWriter(a.out, OW, OH, fps=reader.fps if y4m else None,
-                                 interlace=reader.interlace if y4m else None, aspect=reader.aspect if y4m else None,
-                                 chroma=chroma, xtags=reader.xtags if y4m else (), depth=out_depth)
-    else:
-        writer = video.RawYUV420Writer(a.out, OW, OH, out_depth)
+        "" if depth == out_depth == 8 else ", %d -> %d bits" % (depth, out_depth),
+        "" if a.out_size is None else ", %s to %dx%d" % (a.resample, OW, OH)))
+    writer = open_writer(video, reader, a.out, OW, OH, depth, out_depth)
     ref = None
     if a.reference is not None:
         try:
@@ -190,7 +230,8 @@ def main(argv=None):
             if stream is not None:
                 Y, U, V = stream.upscale(y, u, v)          # the stream's own planes: copied out before the next frame
             else:
-                Y, U, V = up.upscale_yuv420(y, u, v, matrix=a.matrix, full_range=full, out_depth=out_depth)
+                Y, U, V = up.upscale_yuv420(y, u, v, matrix=a.matrix, full_range=full, out_depth=out_depth,
+                                            out_size=out_size, resample=a.resample)
             if writes[slot] is not None:
                 writes[slot].result()                      # the output slot's previous frame is on disk
             dst = video.split_frame(pin_out[slot], OW, OH, out_depth)
