@@ -570,6 +570,45 @@ int ofasr_window_compact(const int32_t* flags, int64_t slabs, const int64_t* ori
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Content-aware routing of tile windows between two networks (csrc/route.hip; host statement: routing.py) -- for
+ * upscale.py's TiledUpscaler(easy_net=..., easy_threshold=T): flat windows run a cheaper network.
+ *   luma sample L: a plane's sample as stored (uint8; uint16 at depth 10), or (77 R + 150 G + 29 B + 128) >> 8 of an
+ *   interleaved uint8 RGB pixel.  Activity of window n, (y0, x0) = origins[n] clamped to 0 <= y0 <= H - h,
+ *   0 <= x0 <= W - w as the gather kernels clamp it, over rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1:
+ *     A = sum_{r < h, c < w - 1} |L[r][c + 1] - L[r][c]| + sum_{r < h - 1, c < w} |L[r + 1][c] - L[r][c]|
+ *   (only differences with both samples inside the rectangle).  A window is easy iff A <= limit.
+ *   ofasr_window_activity_rgb8: img is an HWC uint8 image [H][W][3].  partial is a device int64 table [n][S],
+ *     S = ofasr_window_activity_slabs(h, w) (a host-only query, 1 <= S <= 64; 0 for non-positive sizes):
+ *     partial[n][s] = the terms of row slab s (the horizontal terms of its rows and the vertical terms whose upper row
+ *     it owns); A = the sum of a window's S partials.  Every partial is written by every call.
+ *   ofasr_window_activity_plane: the same on one 2-D plane [H][W]: depth 8: uint8 samples, depth 10: uint16 samples
+ *     (2-byte aligned pointer; the stored words are taken as they are); any other depth is OFASR_ERR_INVALID_ARG.
+ *   ofasr_window_route: ONE workgroup.  From partial [n][slabs], limit, optionally the changed flags [n][changed_slabs]
+ *     of ofasr_window_diff_* (null: every window counts as changed), the plan's origins [n][2] and scatter table [n][6]
+ *     (device int64) and the batch size `batch`: a window whose flags are all zero goes into neither list; the others
+ *     are class 1 (easy, A <= limit) or class 0 (hard).  With rows = ceil(n / batch) * batch, m_c the number of windows
+ *     of class c and i_0 < i_1 < ... their indices (stable, plan order):
+ *       out_index[c][j] = i_j, out_table[c][j][:] = table[i_j][:], out_origins[c][j][:] = origins[i_j][:]   for j < m_c
+ *       out_origins[c][j][:] = origins[i_{m_c - 1}][:]     for m_c <= j < ceil(m_c / batch) * batch
+ *       count[c] = m_c
+ *     out_origins is [2][rows][2], out_table [2][n][6], out_index [2][n], count [2] (device int64); rows past the ones
+ *     named are not written.  The call does not synchronise.
+ * Plain loads and stores, no atomics: two calls give identical bytes.  No load leaves the plane whatever the origin table
+ * holds, whatever the plane's base alignment (16-byte loads only where the address is aligned for them).  64-bit
+ * addressing; the sums are int64.  OFASR_ERR_INVALID_ARG: a null pointer, a non-positive size, a window larger than the
+ * frame, an odd 16-bit plane pointer, an unknown depth, slabs > 64.  OFASR_ERR_UNSUPPORTED: n or batch > 65535, more than
+ * 2^40 pixels.
+ * ------------------------------------------------------------------------------------------- */
+int64_t ofasr_window_activity_slabs(int64_t h, int64_t w);
+int ofasr_window_activity_rgb8(const void* img, int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h, int64_t w,
+                               int64_t* partial, void* stream);
+int ofasr_window_activity_plane(const void* plane, int64_t H, int64_t W, int depth, const int64_t* origins, int64_t n,
+                                int64_t h, int64_t w, int64_t* partial, void* stream);
+int ofasr_window_route(const int64_t* partial, int64_t slabs, int64_t limit, const int32_t* changed, int64_t changed_slabs,
+                       const int64_t* origins, const int64_t* table, int64_t n, int64_t batch, int64_t* out_origins,
+                       int64_t* out_table, int64_t* out_index, int64_t* count, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Geometric self-ensemble: the 8 flips / transposes (the dihedral group D4) of an NCHW batch and the fp32 merge of the
  * 8 network outputs, for upscale.py's TiledUpscaler(self_ensemble=k) and ops.self_ensemble (csrc/d4.hip; host statement:
  * upscale.d4_transform / d4_inverse).  With b_i = bit i of t (0 <= t < 8), on the last two axes:

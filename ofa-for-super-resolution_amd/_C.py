@@ -145,6 +145,11 @@ SIGNATURES = {
     "ofasr_window_diff_yuv420p16": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_i64,
                                              _c_i64, _c_i64, _c_vp, _c_vp]),
     "ofasr_window_compact": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "ofasr_window_activity_slabs": (_c_i64, [_c_i64, _c_i64]),
+    "ofasr_window_activity_rgb8": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "ofasr_window_activity_plane": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "ofasr_window_route": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp,
+                                    _c_vp, _c_vp]),
     "ofasr_d4_apply": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp]),
     "ofasr_d4_accumulate": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, ctypes.c_float,
                                      _c_vp]),

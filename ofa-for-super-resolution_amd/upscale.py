@@ -49,13 +49,23 @@ computes from the coefficient tables themselves (the largest overhang of [xmin, 
 halo becomes radius + extra, so every pixel a window's rectangle reads lies at least `radius` input pixels inside the
 window's non-image edges, where the window's output equals the whole-image forward's.  plan_resize checks that for every
 window.  Hence tiled = whole, as before.  T = S on both axes is today's plan, halo and kernels, bit for bit.
+
+Content-aware routing (`easy_net`, `easy_threshold`): two networks exported from one supernet share one tile plan (the
+larger receptive radius, the lcm of the alignments, the larger activation: routing.shared_plan_params); a window whose
+luma activity (routing.py: the sum of absolute differences of neighbouring luma samples inside the window, an exact
+integer) is at most the threshold's integer limit runs `easy_net`, every other window `net`.  ofasr_window_activity_* and
+ofasr_window_route (csrc/route.hip) classify on the GPU and compact the plan's tables into one list per class; the host
+reads the two counts (the one synchronisation routing adds) and runs the batch loop once per class, in batches of the
+plan's size, so each network replays the graph of its full-batch shape.  The class is a function of the window's own
+bytes, so it composes with window reuse: an unchanged window keeps its class and its output.  There is no blending:
+neighbouring cores from different networks can differ at the seam.
 """
 import math
 from fractions import Fraction
 
 import torch
 
-from . import _C, ops, resize
+from . import _C, ops, resize, routing
 from .graphed import GraphedEval
 
 LIMIT = 2 ** 31          # no activation of one window reaches 2^31 bytes (fp32); no batched tensor 2^31 elements
@@ -150,6 +160,13 @@ def activation_elems_per_pixel(config):
 def alignment(config):
     """the side multiple an input needs: 2 ** (PixelUnshuffle blocks) for X4, 1 for S4"""
     return 2 ** config.get("n_unshuffle", 0) if config["name"] == "SRNetX4" else 1
+
+
+def shared_geometry(config_a, config_b):
+    """(radius, align, halo, px_elems) of the one tile plan that two static networks can both run
+    (routing.shared_plan_params of their receptive radii, alignments and activation sizes); symmetric in its arguments"""
+    return routing.shared_plan_params(*((receptive_radius(c), alignment(c), activation_elems_per_pixel(c))
+                                        for c in (config_a, config_b)))
 
 
 # ---------------------------------------------------------------------------------------------- tile plan
@@ -547,6 +564,83 @@ def window_compact(flags, origins, table, batch, out=None):
     return out
 
 
+def window_activity_slabs(h, w):
+    """row slabs per window of window_activity's partial table (ofasr_window_activity_slabs; host only)"""
+    return int(_C.lib().ofasr_window_activity_slabs(h, w))
+
+
+def _origin_table(origins, name):
+    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous() or origins.dim() != 2 \
+            or origins.size(1) != 2:
+        raise ValueError("%s needs a contiguous int64 origin table [n, 2] on the GPU" % name)
+    return origins.size(0)
+
+
+def window_activity(src, origins, h, w, partial=None):
+    """src: an HWC uint8 RGB image [H, W, 3] or one 2-D luma plane (uint8, or uint16: depth 10) on the GPU; origins: int64
+    [n, 2] of h x w windows on the GPU -> int64 partial [n, window_activity_slabs(h, w)]: a window's row sums to its
+    luma activity A (routing.window_activity_host; ofasr_window_activity_rgb8 / ofasr_window_activity_plane)"""
+    ops._gpu(src)
+    if not src.is_contiguous() or not ((src.dim() == 3 and src.size(2) == 3 and src.dtype == torch.uint8) or
+                                       (src.dim() == 2 and src.dtype in ops.YUV_DEPTHS)):
+        raise ValueError("window_activity needs a contiguous HWC uint8 RGB image or a 2-D uint8 / uint16 plane, got %s %s"
+                         % (tuple(src.shape), src.dtype))
+    n = _origin_table(origins, "window_activity")
+    S = window_activity_slabs(h, w)
+    if partial is None:
+        partial = torch.empty(n, max(S, 1), dtype=torch.int64, device=src.device)
+    elif partial.dtype != torch.int64 or not partial.is_cuda or not partial.is_contiguous() or partial.numel() != n * S:
+        raise ValueError("window_activity needs contiguous int64 partials [n, %d] on the GPU" % S)
+    if src.dim() == 3:
+        _C.check(_C.lib().ofasr_window_activity_rgb8(src.data_ptr(), src.size(0), src.size(1), origins.data_ptr(), n, h, w,
+                                                     partial.data_ptr(), ops._stream()), "ofasr_window_activity_rgb8")
+    else:
+        _C.check(_C.lib().ofasr_window_activity_plane(src.data_ptr(), src.size(0), src.size(1), ops.YUV_DEPTHS[src.dtype],
+                                                      origins.data_ptr(), n, h, w, partial.data_ptr(), ops._stream()),
+                 "ofasr_window_activity_plane")
+    return partial
+
+
+def window_route(partial, limit, origins, table, batch, changed=None, out=None):
+    """partial: int64 [n, S] from window_activity; limit: the integer of routing.activity_limit; origins [n, 2] and table
+    [n, 6]: the plan's int64 tables on the GPU; changed: None, or the int32 flags [n, S'] of window_diff_yuv420 (a window
+    whose flags are all zero goes into neither list) -> (origins [2, ceil(n / batch) * batch, 2], table rows [2, n, 6],
+    plan indices [2, n], counts [2]), index 0 the hard windows (A > limit), index 1 the easy ones, each in plan order and
+    its origins filled up to a multiple of `batch` by repeating the class's last window; rows past those are not
+    written.  One workgroup, no synchronisation (ofasr_window_route)."""
+    ops._gpu(partial)
+    n = _origin_table(origins, "window_route")
+    batch, limit = int(batch), int(limit)
+    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or tuple(table.shape) != (n, 6):
+        raise ValueError("window_route needs a contiguous int64 table [n, 6] on the GPU")
+    if partial.dtype != torch.int64 or not partial.is_contiguous() or partial.dim() != 2 or partial.size(0) != n:
+        raise ValueError("window_route needs contiguous int64 partials [n, S]")
+    if changed is not None and (changed.dtype != torch.int32 or not changed.is_cuda or not changed.is_contiguous() or
+                                changed.dim() != 2 or changed.size(0) != n):
+        raise ValueError("window_route needs contiguous int32 changed flags [n, S] on the GPU")
+    if batch < 1:
+        raise ValueError("window_route needs a positive batch size")
+    if not -1 <= limit <= routing.INT64_MAX:
+        raise ValueError("window_route needs a limit in -1 .. 2^63 - 1")
+    rows = -(-n // batch) * batch
+    if out is None:
+        out = (torch.zeros(2, rows, 2, dtype=torch.int64, device=partial.device),
+               torch.zeros(2, n, 6, dtype=torch.int64, device=partial.device),
+               torch.zeros(2, n, dtype=torch.int64, device=partial.device),
+               torch.zeros(2, dtype=torch.int64, device=partial.device))
+    o, t, idx, count = out
+    if (tuple(o.shape), tuple(t.shape), tuple(idx.shape), tuple(count.shape)) != ((2, rows, 2), (2, n, 6), (2, n), (2,)) or \
+            any(b.dtype != torch.int64 or not b.is_cuda or not b.is_contiguous() for b in out):
+        raise ValueError("window_route needs contiguous int64 outputs [2, %d, 2], [2, %d, 6], [2, %d], [2] on the GPU"
+                         % (rows, n, n))
+    _C.check(_C.lib().ofasr_window_route(partial.data_ptr(), partial.size(1), limit,
+                                         None if changed is None else changed.data_ptr(),
+                                         0 if changed is None else changed.size(1), origins.data_ptr(), table.data_ptr(), n,
+                                         batch, o.data_ptr(), t.data_ptr(), idx.data_ptr(), count.data_ptr(), ops._stream()),
+             "ofasr_window_route")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- self-ensemble
 def _d4_index(t):
     if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 8:
@@ -590,9 +684,16 @@ class TiledUpscaler(object):
     keep every batched tensor below 2^31 elements, spread evenly over the batches.  `self_ensemble` = k in {1, 2, 4, 8}:
     every batch runs under the first k flips / transposes and the fp32 mean of the mapped-back outputs is what is
     scattered (ops.self_ensemble); k = 8 plans window heights as multiples of 8 as well and replays two graphs, one per
-    window orientation."""
+    window orientation.
 
-    def __init__(self, net, core=None, batch=None, mix_prec="f32", graphed=True, self_ensemble=1):
+    `easy_net` and `easy_threshold` (both or neither) switch content-aware routing on: a window whose mean absolute luma
+    difference (routing.py, in 8-bit levels) is at most `easy_threshold` runs `easy_net`, a cheaper export with the same
+    upscale factor, every other window `net`.  The threshold is a number or the decimal string the user wrote (the limit
+    is computed from the decimal exactly); window_activity() shows the measure per window and route_stats the counts of
+    the last call.  Both networks share one plan (the larger radius, the lcm of the alignments)."""
+
+    def __init__(self, net, core=None, batch=None, mix_prec="f32", graphed=True, self_ensemble=1, easy_net=None,
+                 easy_threshold=None):
         if mix_prec not in _DTYPES:
             raise ValueError("mix_prec must be one of %s" % sorted(_DTYPES))
         if isinstance(self_ensemble, bool) or self_ensemble not in ops.ENSEMBLE_SIZES:
@@ -607,11 +708,29 @@ class TiledUpscaler(object):
         self.radius = receptive_radius(self.config)
         self.halo = _up(self.radius, self.align)
         self.px_elems = activation_elems_per_pixel(self.config)
+        if (easy_net is None) != (easy_threshold is None):
+            raise ValueError("routing needs both easy_net and easy_threshold (or neither)")
+        self.easy_net = self.easy_threshold = None
+        self.route_stats = None
+        self._limits = {}
+        if easy_net is not None:
+            routing.activity_limit(easy_threshold, 1, 2)        # refuses NaN and what is not a number now
+            if easy_net.config["upscale"] != self.config["upscale"]:
+                raise ValueError("the two networks of a routed upscaler need the same upscale factor, got x%s and x%s"
+                                 % (self.config["upscale"], easy_net.config["upscale"]))
+            devs = [next(m.parameters()).device for m in (net, easy_net)]
+            if devs[0] != devs[1]:
+                raise ValueError("the two networks of a routed upscaler must be on the same device, got %s and %s"
+                                 % (devs[0], devs[1]))
+            self.easy_net, self.easy_threshold = easy_net.eval(), easy_threshold
+            self.radius, self.align, self.halo, self.px_elems = shared_geometry(self.config, easy_net.config)
         self.core = int(core) if core else default_core(self.halo, self.align, self.px_elems)
         self.batch = batch
         self.dtype = _DTYPES[mix_prec]
         self.autocast_dtype = None if mix_prec == "f32" else self.dtype
         self.graphed = GraphedEval(net, autocast_dtype=self.autocast_dtype, copy_output=False) if graphed else None
+        self.graphed_easy = GraphedEval(easy_net, autocast_dtype=self.autocast_dtype, copy_output=False) \
+            if graphed and easy_net is not None else None
         self._plans = {}
 
     def plan(self, H, W, out_size=None, resample="lanczos", even=False):
@@ -646,7 +765,7 @@ class TiledUpscaler(object):
                              "use the tiled path" % (H, W))
         return TilePlan(H, W, H, W, [(0, 0, 0, 0, H, W)], self.scale, 1)
 
-    def _forward(self, x):
+    def _forward(self, x, easy=False):
         # A window's output must not depend on the shape of the batch it was computed in: that is what makes tiling, and
         # reuse between frames, exact.  The fused 16-bit MB kernel breaks it on small inputs: a launch of fewer tiles than
         # CUs spreads each tile's mid-channel chunks over several workgroups (csrc/mbfused.hip, mf_plan) and then sums
@@ -656,10 +775,10 @@ class TiledUpscaler(object):
         split = _C.lib().ofasr_debug_mbfused_split(0) if self.autocast_dtype is not None else None
         try:
             if self.graphed is not None:
-                return self.graphed(x)
+                return (self.graphed_easy if easy else self.graphed)(x)
             with torch.autocast("cuda", dtype=self.autocast_dtype or torch.bfloat16,
                                 enabled=self.autocast_dtype is not None):
-                return self.net(x)
+                return (self.easy_net if easy else self.net)(x)
         finally:
             if split is not None:
                 _C.lib().ofasr_debug_mbfused_split(split)
@@ -678,7 +797,7 @@ class TiledUpscaler(object):
         """run every batch of the plan; sink(y, real, tables, plan) consumes the network output of a batch"""
         img = self._image(img)
         return self._run_windows(img.size(0), img.size(1), img.device, whole, sink,
-                                 lambda origins, h, w: tile_gather(img, origins, h, w, self.dtype), plan)
+                                 lambda origins, h, w: tile_gather(img, origins, h, w, self.dtype), plan, luma=img)
 
     def _batching(self, plan):
         """(batches, windows per batch) of a plan: as many windows per batch as the plan and `batch` allow, spread evenly"""
@@ -701,27 +820,88 @@ class TiledUpscaler(object):
             rows = [[(cy - wy) * s, (cx - wx) * s, cy * s, cx * s, ch * s, cw * s] for (wy, wx, cy, cx, ch, cw) in plan.windows]
         return origins, torch.tensor(rows, dtype=torch.int64).to(device)
 
-    def _run_batches(self, plan, origins, table, n, B, sink, gather, wins=None):
+    def _run_batches(self, plan, origins, table, n, B, sink, gather, wins=None, easy=False):
         """the batch loop: the first n rows of `origins` (padded to a multiple of B) / `table` in batches of B windows.
-        `wins`: the plan windows behind the rows, where the host knows them (sink gets the batch's slice, or None)"""
+        `wins`: the plan windows behind the rows, where the host knows them (sink gets the batch's slice, or None).
+        `easy`: the batches run the easy network of a routed upscaler"""
+        forward = (lambda x: self._forward(x, True)) if easy else self._forward
         with torch.no_grad():
             for b in range(-(-n // B)):
                 x = gather(origins[b * B:(b + 1) * B], plan.win_h, plan.win_w)
                 if self.self_ensemble == 1:
-                    y = self._forward(x)
+                    y = forward(x)
                 else:
-                    y = ops.self_ensemble(self._forward, x, self.self_ensemble)
+                    y = ops.self_ensemble(forward, x, self.self_ensemble)
                 real = min(B, n - b * B)
                 sink(y, real, table[b * B:b * B + real], wins[b * B:b * B + real] if wins is not None else None, plan)
 
-    def _run_windows(self, H, W, device, whole, sink, gather, plan=None):
-        """the same for any source of windows: gather(origins, h, w) -> the [n, 3, h, w] batch of self.dtype"""
+    def _refuse_whole(self, whole):
+        if whole and self.easy_net is not None:
+            raise ValueError("whole=True runs one window: there is nothing to route (use an upscaler without easy_net)")
+
+    def set_easy_threshold(self, threshold):
+        """another `easy_threshold` for the calls that follow (a routed upscaler only); plans and graphs are kept.  A
+        YUV420Stream on this upscaler must be reset(): its kept windows were classified with the old threshold"""
+        if self.easy_net is None:
+            raise ValueError("this upscaler has no easy_net: there is no threshold to set")
+        routing.activity_limit(threshold, 1, 2)
+        self.easy_threshold = threshold
+        self._limits = {}
+
+    def _limit(self, plan, depth):
+        """the integer activity limit of the threshold for the plan's windows at a sample depth"""
+        key = (plan.win_h, plan.win_w, depth)
+        if key not in self._limits:
+            self._limits[key] = routing.activity_limit(self.easy_threshold, plan.win_h, plan.win_w, depth)
+        return self._limits[key]
+
+    def _route(self, luma, plan, origins, table, B, changed=None, partial=None, out=None):
+        """classify the plan's windows on the GPU by the luma activity of `luma` (an HWC RGB image or a Y plane) and run
+        nothing yet: (routed origins [2, rows, 2], routed table [2, n, 6], indices [2, n], hard count, easy count).
+        Reading the two counts back is the one synchronisation that routing adds."""
+        n = len(plan)
+        depth = 8 if luma.dim() == 3 else ops.YUV_DEPTHS[luma.dtype]
+        partial = window_activity(luma, origins[:n], plan.win_h, plan.win_w, partial)
+        o, t, idx, count = window_route(partial, self._limit(plan, depth), origins[:n], table, B, changed, out)
+        hard, easy = count.tolist()
+        self.route_stats = {"windows": n, "easy": easy, "hard": hard}
+        return o, t, idx, hard, easy
+
+    def _run_windows(self, H, W, device, whole, sink, gather, plan=None, luma=None):
+        """the same for any source of windows: gather(origins, h, w) -> the [n, 3, h, w] batch of self.dtype.  `luma`:
+        what a routed upscaler classifies the windows by (the RGB image or the Y plane)"""
+        self._refuse_whole(whole)
         if plan is None:
             plan = self._whole_plan(H, W) if whole else self.plan(H, W)
         _, B = self._batching(plan)
         origins, table = self._tables(plan, device)
-        self._run_batches(plan, origins, table, len(plan), B, sink, gather, plan.windows)
+        if self.easy_net is None:
+            self._run_batches(plan, origins, table, len(plan), B, sink, gather, plan.windows)
+            return plan
+        if len(plan) > MAX_WINDOWS:
+            raise ValueError("a %dx%d image makes %d windows with core %d; routing takes at most %d: use a larger core"
+                             % (W, H, len(plan), self.core, MAX_WINDOWS))
+        o, t, _, hard, easy = self._route(luma, plan, origins, table, B)
+        self._run_batches(plan, o[0], t[0], hard, B, sink, gather)
+        self._run_batches(plan, o[1], t[1], easy, B, sink, gather, easy=True)
         return plan
+
+    def window_activity(self, img, out_size=None, resample="lanczos"):
+        """the mean absolute luma difference, in 8-bit levels, of every window of the plan of an image (HWC uint8 RGB) or
+        of a YUV 4:2:0 frame (a tuple (y, u, v); only y is read): A / (D * depth factor) of routing.py as a CPU float64
+        tensor [windows], in plan order -- what `easy_threshold` is compared with.  A read-back, for choosing the
+        threshold; not on the hot path."""
+        if isinstance(img, (tuple, list)):
+            _, (luma, _, _), H, W = self._yuv420_frame(*img)
+            depth, even = ops.YUV_DEPTHS[luma.dtype], True
+        else:
+            luma = self._image(img)
+            H, W, depth, even = luma.size(0), luma.size(1), 8, False
+        plan = self.plan(H, W) if out_size is None else self.plan(H, W, out_size, resample, even)
+        origins, _ = self._tables(plan, luma.device)
+        A = window_activity(luma, origins[:len(plan)], plan.win_h, plan.win_w).sum(dim=1).cpu()
+        d = routing.activity_terms(plan.win_h, plan.win_w) * routing.depth_factor(depth)
+        return A.to(torch.float64) / d if d else torch.zeros(len(plan), dtype=torch.float64)
 
     def _target_plan(self, H, W, whole, out_size, resample, even):
         """None without `out_size` or for the network's own size (today's path), else the ResizePlan"""
@@ -735,6 +915,7 @@ class TiledUpscaler(object):
         refuses images whose activations would reach 2^31 bytes).  out_size = (TH, TW), between the input's size and the
         network's own on each axis: the output has that size and equals PIL's Image.fromarray(upscale(img)).resize((TW,
         TH), resample) bit for bit ("lanczos" or "bicubic"), resampled inside the scatter (tile_resize_scatter)"""
+        self._refuse_whole(whole)
         H, W = int(img.shape[0]), int(img.shape[1])
         out = None
         rplan = self._target_plan(H, W, whole, out_size, resample, False)
@@ -755,6 +936,7 @@ class TiledUpscaler(object):
             nonlocal out
             if out is None:
                 out = torch.empty(H * self.scale, W * self.scale, 3, dtype=torch.uint8, device=y.device)
+            wins = plan.windows if wins is None else wins         # routed batches: the plan's largest core bounds them
             tile_scatter(y.contiguous(), table, out, max(w[4] for w in wins) * self.scale,
                          max(w[5] for w in wins) * self.scale)
 
@@ -804,6 +986,7 @@ class TiledUpscaler(object):
         the network's output at 1024 levels instead of rounding it to 256.  out_size = (TH, TW), even, between the
         input's size and the network's own: planes of that size, equal to the encode (ops.rgb_to_yuv420_u8, at the
         output depth) of resize.resize_host of the quantised full-size RGB, resampled inside the scatter."""
+        self._refuse_whole(whole)
         dev, (y, u, v), H, W = self._yuv420_frame(y, u, v)
         s = self.scale
         depth = ops.YUV_DEPTHS[y.dtype] if out_depth is None else out_depth
@@ -819,16 +1002,18 @@ class TiledUpscaler(object):
 
             self._run_windows(H, W, dev, whole, rsink,
                               lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range),
-                              rplan)
+                              rplan, luma=y)
             return out
         out = self._yuv420_out(H, W, s, depth, dev)
 
         def sink(t, real, table, wins, plan):
+            wins = plan.windows if wins is None else wins         # routed batches: the plan's largest core bounds them
             tile_scatter_yuv420(t.contiguous(), table, out[0], out[1], out[2], max(w[4] for w in wins) * s,
                                 max(w[5] for w in wins) * s, matrix, full_range)
 
         self._run_windows(H, W, dev, whole, sink,
-                          lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range))
+                          lambda origins, h, w: tile_gather_yuv420(y, u, v, origins, h, w, self.dtype, matrix, full_range),
+                          luma=y)
         return out
 
     def yuv420_stream(self, matrix="bt601", full_range=False, out_depth=None, out_size=None, resample="lanczos"):
@@ -839,6 +1024,8 @@ class TiledUpscaler(object):
     def upscale_float(self, img, whole=False):
         """the network's fp32 output [3, H*scale, W*scale] before quantisation, assembled from the same window cores
         as upscale() (torch copies; for parity checks)"""
+        if self.easy_net is not None:
+            raise ValueError("upscale_float is the parity path of one network: use an upscaler without easy_net")
         H, W = int(img.shape[0]), int(img.shape[1])
         s = self.scale
         out = None
@@ -859,19 +1046,24 @@ class TiledUpscaler(object):
 class StreamStats(object):
     """windows / run / batches: the plan's windows, the windows that went through the network and the forward batches of
     the last frame; frames, frames_unchanged (no window run), total_windows, total_run, total_batches: since the stream
-    was made"""
+    was made.  run_easy / run_hard (total_run_easy / total_run_hard): the windows of `run` that a routed upscaler gave to
+    its easy / hard network; without routing every window is hard."""
 
     def __init__(self):
-        self.windows = self.run = self.batches = 0
+        self.windows = self.run = self.batches = self.run_easy = self.run_hard = 0
         self.frames = self.frames_unchanged = self.total_windows = self.total_run = self.total_batches = 0
+        self.total_run_easy = self.total_run_hard = 0
 
-    def _frame(self, windows, run, batches):
+    def _frame(self, windows, run, batches, run_easy=0):
         self.windows, self.run, self.batches = windows, run, batches
+        self.run_easy, self.run_hard = run_easy, run - run_easy
         self.frames += 1
         self.frames_unchanged += run == 0
         self.total_windows += windows
         self.total_run += run
         self.total_batches += batches
+        self.total_run_easy += run_easy
+        self.total_run_hard += run - run_easy
 
 
 class YUV420Stream(object):
@@ -894,7 +1086,12 @@ class YUV420Stream(object):
     The first frame, a frame of another size or dtype (uint8 / uint16: 8-bit / 10-bit) and the frame after reset() run
     every window.  The previous-frame planes have the input's dtype, the output planes that of `out_depth` (None: the
     input's).  The comparison is exact: it pays off on content that repeats bit for bit and does nothing for camera
-    noise."""
+    noise.
+
+    On a routed upscaler (easy_net) a frame runs diff, then ofasr_window_activity_plane on the Y plane, then
+    ofasr_window_route with the diff's flags: a changed window goes to the list of its class, an unchanged one to neither,
+    and the two counts replace the one read-back.  A window's class depends on its own bytes alone, so an unchanged
+    window would have been given the same network again: the output still equals the routed upscale_yuv420's."""
 
     def __init__(self, upscaler, matrix="bt601", full_range=False, out_depth=None, out_size=None, resample="lanczos"):
         ops.yuv_table(matrix, full_range, False)       # refuses an unknown matrix now rather than at the first frame
@@ -940,6 +1137,12 @@ class YUV420Stream(object):
         self._compact = (torch.zeros(self._origins.size(0), 2, dtype=torch.int64, device=dev),
                          torch.zeros(n, 6, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
                          torch.zeros(1, dtype=torch.int64, device=dev))
+        self._routed = None
+        if up.easy_net is not None:
+            self._partial = torch.zeros(n, window_activity_slabs(plan.win_h, plan.win_w), dtype=torch.int64, device=dev)
+            self._routed = (torch.zeros(2, -(-n // self._B) * self._B, 2, dtype=torch.int64, device=dev),
+                            torch.zeros(2, n, 6, dtype=torch.int64, device=dev),
+                            torch.zeros(2, n, dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
         self._size = (H, W, dev, dtype)
         self._fresh = True
 
@@ -949,6 +1152,9 @@ class YUV420Stream(object):
             return []
         if self._all:
             return list(range(len(self._plan)))
+        if self._routed is not None:
+            idx = self._routed[2]
+            return sorted(idx[0, :self.stats.run_hard].tolist() + idx[1, :self.stats.run_easy].tolist())
         return self._compact[2][:self.stats.run].tolist()
 
     def upscale(self, y, u, v):
@@ -973,6 +1179,19 @@ class YUV420Stream(object):
 
         self._all = self._fresh
         self._fresh = True                             # until this frame is complete: a failed frame leaves nothing to reuse
+        if self._routed is not None:
+            flags = None
+            if not self._all:
+                flags = window_diff_yuv420(y, u, v, self._prev[0], self._prev[1], self._prev[2], self._origins[:n],
+                                           plan.win_h, plan.win_w, self._flags)
+            o, t, _, hard, easy = up._route(y, plan, self._origins, self._table, B, flags, self._partial, self._routed)
+            up._run_batches(plan, o[0], t[0], hard, B, sink, gather)
+            up._run_batches(plan, o[1], t[1], easy, B, sink, gather, easy=True)
+            for dst, src in zip(self._prev, (y, u, v)):
+                dst.copy_(src)
+            self._fresh = False
+            self.stats._frame(n, hard + easy, -(-hard // B) + -(-easy // B), easy)
+            return out
         if self._all:
             m = n
             up._run_batches(plan, self._origins, self._table, n, B, sink, gather)

@@ -11,7 +11,13 @@ the HIP metric kernel, --shave border pixels left out), prints the numbers and w
 --out-size WxH writes every output at that size instead of the network's own: any size from the input's up to the
 network's, each axis on its own.  The result equals Pillow's Image.resize (--resample lanczos, the default, or bicubic) of
 the full-size output bit for bit and is computed inside the scatter kernel; the full-size image never exists.  It applies to
-every input: an input that the size does not fit is refused by name.  --reference then compares at the target size."""
+every input: an input that the size does not fit is refused by name.  --reference then compares at the target size.
+--easy-static DIR --easy-threshold T route every window by its content: a window whose mean absolute difference of
+neighbouring luma samples (L = (77 R + 150 G + 29 B + 128) >> 8, in 8-bit levels) is at most T runs the cheaper export in
+DIR, every other window the --static network; both need the same upscale factor and share one tile plan.  There is no
+blending: neighbouring cores from different networks can differ at the seam.  --route-report prints per image the easy and
+hard window counts and the min / median / max of the per-window measure (what to look at when choosing T) and, with
+--reference, writes the counts into quality.json.  Routing needs the tiled path: it is refused with --whole."""
 import argparse
 import collections
 import concurrent.futures
@@ -52,11 +58,28 @@ def parse_args(argv=None):
     ap.add_argument("--out-size", type=parse_out_size, default=None, metavar="WxH",
                     help="output size of every image (default: the network's own): from the input's size up to the network's")
     ap.add_argument("--resample", default="lanczos", choices=["bicubic", "lanczos"], help="the filter of --out-size")
+    ap.add_argument("--easy-static", default=None, metavar="DIR",
+                    help="a cheaper exported network of the same upscale factor for flat windows (needs --easy-threshold)")
+    ap.add_argument("--easy-threshold", default=None, metavar="T",
+                    help="a window is easy when its mean absolute luma difference, in 8-bit levels, is at most T")
+    ap.add_argument("--route-report", action="store_true", help="per image: easy / hard windows and the activity")
     ap.add_argument("--reference", default=None, metavar="PATH",
                     help="directory of ground-truth HR images named as the inputs: report Y-PSNR / Y-SSIM per image")
     ap.add_argument("--shave", type=int, default=0, help="with --reference: border pixels left out of the metric")
     ap.add_argument("inputs", nargs="+", metavar="INPUT", help="image files or directories")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if (a.easy_static is None) != (a.easy_threshold is None):
+        ap.error("--easy-static and --easy-threshold need each other")
+    if a.route_report and a.easy_static is None:
+        ap.error("--route-report needs --easy-static and --easy-threshold")
+    if a.easy_static is not None and a.whole:
+        ap.error("--whole runs one window per image: there is nothing to route")
+    if a.easy_threshold is not None:
+        try:
+            importlib.import_module(PKG + ".routing").activity_limit(a.easy_threshold, 1, 2)
+        except ValueError as e:
+            ap.error("--easy-threshold: %s" % e)
+    return a
 
 
 def list_inputs(inputs):
@@ -117,11 +140,22 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("upscaling runs on the GPU")
     net = evals.load_static(a.static).cuda()
-    up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble)
+    easy = None if a.easy_static is None else evals.load_static(a.easy_static).cuda()
+    try:
+        up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble,
+                                   easy_net=easy, easy_threshold=a.easy_threshold)
+    except ValueError as e:
+        if easy is None:
+            raise
+        raise SystemExit("--easy-static: %s" % e)
     os.makedirs(a.out, exist_ok=True)
     print("%s x%d: receptive radius %d px, halo %d, core %d, %s%s" % (
         net.name(), up.scale, up.radius, up.halo, up.core, a.mix_prec,
         "" if a.self_ensemble == 1 else ", self-ensemble x%d" % a.self_ensemble))
+    if easy is not None:
+        print("routing: windows of mean luma activity <= %s run %s (receptive radius %d px)"
+              % (a.easy_threshold, easy.name(), upscale.receptive_radius(easy.config)))
+    routes = []
     taken = set()
     mpix = 0.0
     saves = []
@@ -146,6 +180,13 @@ def main(argv=None):
                 if a.out_size is None:
                     raise
                 raise SystemExit("%s: %s" % (f, e))
+            if easy is not None:
+                routes.append({k: up.route_stats[k] for k in ("windows", "easy", "hard")})
+                if a.route_report:
+                    act = up.window_activity(torch.from_numpy(img), out_size, a.resample)
+                    print("%s: easy %d hard %d of %d windows; activity min %.3f median %.3f max %.3f" % (
+                        f, routes[-1]["easy"], routes[-1]["hard"], routes[-1]["windows"], float(act.min()),
+                        float(act.median()), float(act.max())))
             if a.reference is not None:
                 ref = decode(refs[i])
                 if ref.shape != tuple(out_gpu.shape):
@@ -171,9 +212,11 @@ def main(argv=None):
     if a.reference is not None:
         import json
         recs = []
-        for f, r, q in scores:
+        for i, (f, r, q) in enumerate(scores):
             recs.append({"input": f, "reference": r, "psnr": q.psnr()[0], "ssim": q.ssim_list()[0], "sse": q.sse_list()[0],
                          "count": q.count})
+            if a.route_report:
+                recs[-1]["route"] = routes[i]
             print("%s: Y-PSNR %.3f dB  Y-SSIM %.4f" % (f, recs[-1]["psnr"], recs[-1]["ssim"]))
         mean = {"psnr": sum(x["psnr"] for x in recs) / len(recs), "ssim": sum(x["ssim"] for x in recs) / len(recs)}
         print("mean of %d images: Y-PSNR %.3f dB  Y-SSIM %.4f  (shave %d)" % (len(recs), mean["psnr"], mean["ssim"], a.shave))

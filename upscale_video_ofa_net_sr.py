@@ -26,6 +26,14 @@ Pillow's resize (--resample lanczos, the default, or bicubic) of the quantised f
 it is computed inside the scatter kernel, so the full-size frame never exists and only the target frame is copied to the
 host.  The Y4M header, --reference, --dump-png, --reuse-static, --self-ensemble, --out-depth and --frames all work at
 the target size.
+--easy-static DIR --easy-threshold T route every window by its content (upscale.TiledUpscaler(easy_net=...)): a window
+whose mean absolute difference of neighbouring luma samples, in 8-bit levels, is at most T (flat: letterbox bars, sky, slide
+backgrounds) runs the cheaper export in DIR, every other window the --static network.  The two exports need the same
+upscale factor and share one tile plan.  The measure is an exact integer function of the window's bytes: the result is
+reproducible, and with --reuse-static an unchanged window keeps its class and its output.  There is no blending between
+the two networks: neighbouring cores can differ at the seam.  --route-report prints per frame how many windows were easy,
+hard and reused and the min / median / max of the per-window measure, which is what to look at when choosing T.  Both
+flags work with --reuse-static, --self-ensemble, --out-size, --out-depth, --frames and --reference.
 Prints frames per second and output megapixels per second at the end."""
 import argparse
 import concurrent.futures
@@ -115,13 +123,32 @@ def parse_args(argv=None):
     ap.add_argument("--self-ensemble", type=int, default=1, choices=[1, 2, 4, 8], metavar="K")
     ap.add_argument("--reuse-static", action="store_true",
                     help="keep the output of windows whose input did not change since the previous frame (same output)")
+    ap.add_argument("--easy-static", default=None, metavar="DIR",
+                    help="a cheaper exported network of the same upscale factor for flat windows (needs --easy-threshold)")
+    ap.add_argument("--easy-threshold", default=None, metavar="T",
+                    help="a window is easy when its mean absolute luma difference, in 8-bit levels, is at most T")
+    ap.add_argument("--route-report", action="store_true", help="per frame: easy / hard / reused windows and the activity")
     ap.add_argument("--dump-png", default=None, metavar="DIR", help="also write every output frame as a PNG")
     ap.add_argument("--reference", default=None, metavar="REF", help="ground-truth video of the output's size: PSNR")
     ap.add_argument("input", metavar="INPUT", help="*.y4m, or a headerless yuv420p file (then --size is required)")
     a = ap.parse_args(argv)
+    check_route_args(ap, a)
     if a.dump_png is not None and 10 in (a.out_depth, a.depth if a.out_depth is None else None):
         ap.error("--dump-png needs an 8-bit output (there is no 16-bit PNG writer): leave it out or use --out-depth 8")
     return a
+
+
+def check_route_args(ap, a):
+    """--easy-static and --easy-threshold come together, T is a number, and --route-report needs both"""
+    if (a.easy_static is None) != (a.easy_threshold is None):
+        ap.error("--easy-static and --easy-threshold need each other")
+    if a.route_report and a.easy_static is None:
+        ap.error("--route-report needs --easy-static and --easy-threshold")
+    if a.easy_threshold is not None:
+        try:
+            importlib.import_module(PKG + ".routing").activity_limit(a.easy_threshold, 1, 2)
+        except ValueError as e:
+            ap.error("--easy-threshold: %s" % e)
 
 
 def psnr(sse, count, peak=255.0):
@@ -154,7 +181,14 @@ def main(argv=None):
         raise SystemExit("--dump-png needs an 8-bit output (there is no 16-bit PNG writer): use --out-depth 8")
     full = a.range == "pc"
     net = evals.load_static(a.static).cuda()
-    up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble)
+    easy = None if a.easy_static is None else evals.load_static(a.easy_static).cuda()
+    try:
+        up = upscale.TiledUpscaler(net, core=a.core, batch=a.batch, mix_prec=a.mix_prec, self_ensemble=a.self_ensemble,
+                                   easy_net=easy, easy_threshold=a.easy_threshold)
+    except ValueError as e:
+        if easy is None:
+            raise
+        raise SystemExit("--easy-static: %s" % e)
     s = up.scale
     OW, OH = output_size(W, H, s, a.out_size)
     out_size = None if a.out_size is None else (OH, OW)
@@ -170,6 +204,10 @@ def main(argv=None):
         "" if a.self_ensemble == 1 else ", self-ensemble x%d" % a.self_ensemble,
         "" if depth == out_depth == 8 else ", %d -> %d bits" % (depth, out_depth),
         "" if a.out_size is None else ", %s to %dx%d" % (a.resample, OW, OH)))
+    if easy is not None:
+        print("routing: windows of mean luma activity <= %s run %s (receptive radius %d px)"
+              % (a.easy_threshold, easy.name(), upscale.receptive_radius(easy.config)))
+    routed = [0, 0, 0]                                     # easy, hard, reused windows of all frames
     writer = open_writer(video, reader, a.out, OW, OH, depth, out_depth)
     ref = None
     if a.reference is not None:
@@ -232,6 +270,15 @@ def main(argv=None):
             else:
                 Y, U, V = up.upscale_yuv420(y, u, v, matrix=a.matrix, full_range=full, out_depth=out_depth,
                                             out_size=out_size, resample=a.resample)
+            if easy is not None:
+                rs = up.route_stats
+                counts = (rs["easy"], rs["hard"], rs["windows"] - rs["easy"] - rs["hard"])
+                routed = [t + c for t, c in zip(routed, counts)]
+                if a.route_report:
+                    act = up.window_activity((y, u, v), out_size, a.resample)
+                    print("frame %d: easy %d hard %d reused %d of %d windows; activity min %.3f median %.3f max %.3f"
+                          % ((first + done,) + counts + (rs["windows"], float(act.min()), float(act.median()),
+                                                         float(act.max()))))
             if writes[slot] is not None:
                 writes[slot].result()                      # the output slot's previous frame is on disk
             dst = video.split_frame(pin_out[slot], OW, OH, out_depth)
@@ -271,10 +318,17 @@ def main(argv=None):
         mean = {"psnr_" + k: sum(r["psnr_" + k] for r in scores) / len(scores) for k in "yuv"}
         print("mean of %d frames: PSNR Y %.3f  U %.3f  V %.3f dB" % (len(scores), mean["psnr_y"], mean["psnr_u"], mean["psnr_v"]))
         with open(a.out + ".quality.json", "w") as fh:
-            json.dump({"reference": a.reference, "matrix": a.matrix, "range": a.range, "self_ensemble": a.self_ensemble,
-                       "frames": scores, "mean": mean}, fh, indent=1)
+            rec = {"reference": a.reference, "matrix": a.matrix, "range": a.range, "self_ensemble": a.self_ensemble,
+                   "frames": scores, "mean": mean}
+            if easy is not None:
+                rec["route"] = {"easy_static": a.easy_static, "easy_threshold": a.easy_threshold, "easy": routed[0],
+                                "hard": routed[1], "reused": routed[2]}
+            json.dump(rec, fh, indent=1)
     mp = done * OW * OH / 1e6
     print("%d frames, %.2f output MP in %.3f s: %.2f frames/s, %.2f MP/s" % (done, mp, dt, done / dt, mp / dt))
+    if easy is not None:
+        print("routed %d windows: %d easy (%.1f %%), %d hard, %d reused" % (
+            sum(routed), routed[0], 100.0 * routed[0] / max(sum(routed), 1), routed[1], routed[2]))
     if stream is not None:
         st = stream.stats
         print("windows run %d of %d (%.1f %%), %d frames unchanged" % (
