@@ -28,6 +28,16 @@
  *     parameter, so `weight[:out, :in]` (dynamic_op.py:108) costs no `.contiguous()` copy.
  *   - workspace: caller-allocated device scratch, size from the matching *_workspace() query;
  *     contents need not be initialised.
+ *   - alignment: activations, weights, gradients and outputs need only the alignment of their element type unless
+ *     an entry point says otherwise; the kernels pick vector or element-wise access from the addresses they are given.
+ *     16-byte aligned tensors are REQUIRED by the 16-bit static conv (ofasr_conv2d_fwd / _fwd_stat / _dgrad / _wgrad /
+ *     _infer_run: x, y, dy, dx), by ofasr_pixel_shuffle2_bn (x, y), by ofasr_bn_bwd_ps2 (dout, x, dx), by the workspace
+ *     of ofasr_conv2d_f32_* and by act_buf / tmp_buf of the composite block; without it these return
+ *     OFASR_ERR_UNSUPPORTED (the two buffers of the composite: OFASR_ERR_INVALID_ARG / UNSUPPORTED, the fp32 conv's
+ *     workspace: OFASR_ERR_WORKSPACE) and write nothing.  The host mirror (ops.py) copies such a tensor once.
+ *   - bounds: an entry point reads and writes nothing outside its operands, writes only the elements its description
+ *     names, and uses at most the *_workspace() bytes of scratch (tests/test_hip_placement_abi.py holds every operand
+ *     between guard bands at 0, one element and 8 bytes past a 16-byte boundary).
  */
 #ifndef OFASR_H
 #define OFASR_H

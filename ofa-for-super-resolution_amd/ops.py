@@ -98,6 +98,13 @@ class _timed(object):
         return False
 
 
+def _al16(t):
+    """`t` itself when its address is 16-byte aligned (no copy, no launch), else one clone into fresh storage.  Only for
+    the entry points that refuse misaligned tensors (include/ofasr.h, Conventions): a contiguous view that starts at an
+    odd storage offset is a legal input to this module, and .contiguous() leaves it where it is."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _f32_param(w):
     if w.dtype != torch.float32:
         raise _C.OfasrError("weights / filters are fp32 master copies (got %s)" % w.dtype)
@@ -713,7 +720,7 @@ class BNActCPFn(Function):
             # both BatchNorm-backward passes read the gradient through the inverse shuffle (no un-shuffle pass)
             N, C, H, W = x.shape
             L = _C.lib()
-            dy = dy.contiguous()
+            dy = _al16(dy.contiguous())
             dx = torch.empty_like(x)
             wshape = ctx.meta[3]
             full = int(wshape[0]) == C
@@ -1486,7 +1493,7 @@ class Conv2dFn(Function):
 
     @staticmethod
     def forward(ctx, x, weight, dgrad_hip=True):
-        x = x.contiguous()
+        x = _al16(x.contiguous())
         N, Cin, H, W = x.shape
         Cout, _, K, _ = weight.shape
         ctx.dgrad_hip = dgrad_hip
@@ -1513,7 +1520,7 @@ class Conv2dStatFn(Function):
 
     @staticmethod
     def forward(ctx, x, weight):
-        x = x.contiguous()
+        x = _al16(x.contiguous())
         N, Cin, H, W = x.shape
         Cout, _, K, _ = weight.shape
         ctx.dgrad_hip = True
@@ -1541,7 +1548,7 @@ def _conv2d_backward(ctx, dy):
     x, weight = ctx.saved_tensors
     N, Cin, H, W = x.shape
     Cout, _, K, _ = weight.shape
-    dy = dy.contiguous()
+    dy = _al16(dy.contiguous())
     L = _C.lib()
     dx = dw = None
     if not ctx.dgrad_hip:
@@ -1663,7 +1670,7 @@ def conv_bn_act_infer(x, conv, bn, act):
     if act == ACT_PIXEL_SHUFFLE2 and Cout % 4:
         return None
     L = _C.lib()
-    xa = x.contiguous()
+    xa = _al16(x.contiguous())
     padw = (-W) % 8          # ragged widths: zero columns on the right ARE the convolution's padding (see conv2d)
     if padw:
         xa = torch.nn.functional.pad(xa, (0, padw))
