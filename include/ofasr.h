@@ -715,6 +715,13 @@ int ofasr_debug_mbfused_split(int enable);
  *   what it writes instead of running the reduction pass (default 0: measured 1 % slower in the training step;
  *   OFASR_MBCONV_BN_BWD_STAT=1 at load time); returns the previous setting. */
 int ofasr_debug_mbconv_bn_bwd_stat(int enable);
+/*   ofasr_debug_pwconv_wgrad_xf: ofasr_pwconv_wgrad with x read through v -> min(max((v - mean[c]) * scale[c] +
+ *   shift[c] + mean[c] * scale[c], 0), 6) per input channel c (fp32 [Cin] each) -- the fused-input weight gradient the MB
+ *   block's backward runs, reachable on its own so that a test can drive both operand roles.  16-bit, 16-byte aligned
+ *   tensors with HW % 8 == 0 only; workspace as ofasr_pwconv_wgrad_workspace. */
+int ofasr_debug_pwconv_wgrad_xf(const void* dy, const void* x, float* dw, int64_t ldw, int64_t N, int64_t Cin,
+                                int64_t Cout, int64_t HW, int dtype, const float* scale, const float* shift,
+                                const float* mean, void* workspace, size_t workspace_bytes, void* stream);
 long long ofasr_debug_launch_count(const char* substr);
 void ofasr_debug_reset_launch_counts(void);
 const char* ofasr_debug_launch_table(void);

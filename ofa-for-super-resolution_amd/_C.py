@@ -163,6 +163,8 @@ SIGNATURES = {
     "ofasr_debug_mbfused_tile": (_c_int, [_c_int]),
     "ofasr_debug_mbfused_split": (_c_int, [_c_int]),
     "ofasr_debug_mbconv_bn_bwd_stat": (_c_int, [_c_int]),
+    "ofasr_debug_pwconv_wgrad_xf": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp,
+                                             _c_vp, _c_vp, _c_sz, _c_vp]),
     "ofasr_debug_launch_count": (ctypes.c_longlong, [ctypes.c_char_p]),
     "ofasr_debug_reset_launch_counts": (None, []),
     "ofasr_debug_launch_table": (ctypes.c_char_p, []),

@@ -29,6 +29,7 @@
 //                             with the accumulators resident.
 #include <stdlib.h>
 #include "ofasr_common.h"
+#include "pw_wgrad_stream.h"
 
 namespace ofasr {
 
@@ -1466,15 +1467,24 @@ __global__ void __launch_bounds__(PW_THREADS) pw_wgrad_kernel(const T* __restric
 // dw[r*sr + s*ss] = sum_z part[z][r][s]: 64 outputs x 16 z-lanes per block (each z-lane sums every 16th slab with 4
 // independent loads in flight), z-lane partial sums combined through LDS in a fixed order (deterministic)
 constexpr int WR_ZL = 16;
+static_assert(WS_PAIR_STRIDE == WR_ZL && WS_PAIR_GROUP == 4 * WR_ZL, "the pair slabs of the streaming weight gradient follow this kernel's order");
 __global__ void __launch_bounds__(64 * WR_ZL) pw_wgrad_reduce_kernel(const float* __restrict__ part,
                                                                      float* __restrict__ dw, int MR, int NS, int nsplit,
-                                                                     long long sr, long long ss) {
+                                                                     long long sr, long long ss, int pairs) {
     __shared__ float red[WR_ZL][64];
     const long long tot = (long long)MR * NS;
     const long long idx = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
     const int zl = threadIdx.x >> 6;
     float a = 0.f;
-    if (idx < tot) {
+    if (idx < tot && pairs) {
+        // slab 2 * WR_ZL * g + WR_ZL * half + zl already holds v(z) + v(z + WR_ZL) of z = 4 * WR_ZL * g + 2 * WR_ZL * half + zl
+        // (pw_wgrad_stream.h, nsplit % (4 * WR_ZL) == 0): the sum below continues exactly as the loop of the other branch
+        for (int g = 0; g < nsplit / (4 * WR_ZL); ++g) {
+            const float v01 = part[(long long)(2 * WR_ZL * g + zl) * tot + idx];
+            const float v23 = part[(long long)(2 * WR_ZL * g + WR_ZL + zl) * tot + idx];
+            a += v01 + v23;
+        }
+    } else if (idx < tot) {
         int z = zl;
         for (; z + 3 * WR_ZL < nsplit; z += 4 * WR_ZL) {
             const float v0 = part[(long long)z * tot + idx], v1 = part[(long long)(z + WR_ZL) * tot + idx];
@@ -1506,7 +1516,155 @@ constexpr int WD_ROWS = 4 * WD_RB * 32, WD_COLS = 64;
 
 struct WdPlan {
     int quads_per_img, total_quads, nsplit, MR, NS;
+    int stream;   // 1: the LDS-DMA streaming body (wd_stream_body), 192-row tiles; 0: the per-lane loads below, 384-row tiles
+    int pairs;    // 1 (streaming only): a workgroup walks splits z and z + 16 and writes their sum as one slab (nsplit / 2 slabs)
 };
+
+// ---- streaming operand path (pw_wgrad_stream.h has the geometry and the address model).  Both operands reach LDS as
+// whole 128-byte lines by LDS-DMA -- 4 wave instructions per wave and stage, no VGPR destination, no ds_write -- into a
+// ring of 3 stages; a fragment is one ds_read_b128.  Per stage: counted vmcnt (the next stage stays in flight) -> one raw
+// barrier -> issue the stage after next into the slot the previous iteration read -> fragment reads and MFMAs.
+// The sums are those of the per-lane-load body BIT FOR BIT: the same split ranges (WdPlan::nsplit), per output element the
+// same chain of MFMAs over the quads of a split with the same k-slot <-> pixel map (k-step j of a quad = pixels
+// [8j, 8j + 8) and [32 + 8j, 32 + 8j + 8): chunk j + 4h), no split of k over waves.  Waves 0..5 own one 32-row block x
+// both column blocks (2 accumulators), waves 6 and 7 only copy.  With WdPlan::pairs a workgroup walks the two splits
+// z and z + 16 that pw_wgrad_reduce_kernel adds first, one after the other, and writes p_z + p_(z+16) as ONE slab: half the
+// slabs, and the reduce launch (pairs = 1) continues the very same association.
+__device__ __forceinline__ void ws_dma16(const void* src, char* lds_piece) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)lds_piece, 16, 0, 0);
+}
+
+template <typename T, int XF>
+__device__ __forceinline__ void wd_stream_body(const T* __restrict__ R, const T* __restrict__ S, float* __restrict__ part,
+                                               int MR, int NS, int HW, const WdPlan& wp, const InputXf& xf, char* ring) {
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const bool worker = wave < WS_ROWS / 32;          // waves 6, 7: copy only
+    const int c = lane & 31, h = lane >> 5;
+    const int row0 = blockIdx.y * WS_ROWS;
+    const int wline = worker ? 32 * wave : 0;         // first line / row of this wave inside the tile
+    const int wrow0 = row0 + wline;
+    const bool rs = wrow0 + c < MR;
+    bool cs[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) cs[cb] = 32 * cb + c < NS;
+    // the lane's channel constants: loaded and consumed BEFORE the first DMA is issued (an ordinary load result used
+    // while a DMA is outstanding drains the whole queue)
+    float xsc = 1.f, xmu = 0.f, xb = 0.f;
+    float csc[2] = {1.f, 1.f}, cmu[2] = {0.f, 0.f}, cbb[2] = {0.f, 0.f};
+    if constexpr (XF == 1) {
+        const int rc = rs ? wrow0 + c : MR - 1;
+        xsc = xf.scale[rc];
+        xmu = xf.mean[rc];
+        xb = fmaf(xmu, xsc, xf.shift[rc]);
+        asm volatile("" : "+v"(xsc), "+v"(xmu), "+v"(xb));
+    }
+    if constexpr (XF == 2) {
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            const int colc = cs[cb] ? 32 * cb + c : NS - 1;
+            csc[cb] = xf.scale[colc];
+            cmu[cb] = xf.mean[colc];
+            cbb[cb] = fmaf(cmu[cb], csc[cb], xf.shift[colc]);
+            asm volatile("" : "+v"(csc[cb]), "+v"(cmu[cb]), "+v"(cbb[cb]));
+        }
+    }
+    // the stages of this workgroup: split za, then (pairs) split za + 16
+    const int za = wp.pairs ? ws_pair_first((int)blockIdx.x) : (int)blockIdx.x;
+    const int qa0 = ws_split_begin(za, wp.nsplit, wp.total_quads);
+    const int n_a = ws_split_begin(za + 1, wp.nsplit, wp.total_quads) - qa0;
+    const int qb0 = wp.pairs ? ws_split_begin(za + WS_PAIR_STRIDE, wp.nsplit, wp.total_quads) : 0;
+    const int n_b = wp.pairs ? ws_split_begin(za + WS_PAIR_STRIDE + 1, wp.nsplit, wp.total_quads) - qb0 : 0;
+    const int n_st = n_a + n_b;
+    // this lane's source of the wave's 4 pieces (3 of R, 1 of S): tensor base + clamped row + swizzled chunk, fixed for
+    // the launch; a stage adds the uniform (image, pixel) offset
+    const T* src[WS_PPW];
+    int dst[WS_PPW];
+#pragma unroll
+    for (int k = 0; k < WS_PPW; ++k) {
+        const int piece = ws_piece_of(wave, k);
+        const WsSrc s = ws_piece_src(piece, lane, row0, MR, NS);
+        src[k] = (s.is_s ? S : R) + (long long)s.row * HW + s.chunk * 8;
+        dst[k] = piece * WS_PIECE_BYTES;
+    }
+    auto issue = [&](int i, int slot) {
+        const int q = i < n_a ? qa0 + i : qb0 + (i - n_a);
+        const int n = q / wp.quads_per_img;
+        const int p0 = (q - n * wp.quads_per_img) * WS_PX;
+        const long long ro = (long long)n * MR * HW + p0, so = (long long)n * NS * HW + p0;
+        char* sl = ring + slot * WS_STAGE_BYTES;
+#pragma unroll
+        for (int k = 0; k < WS_PPW; ++k) ws_dma16(src[k] + (k < WS_PPW - 1 ? ro : so), sl + dst[k]);
+    };
+    // fragment offsets inside a slot: k-step j reads chunk ws_kstep_chunk(j, h) of the lane's lines
+    int aoff[4], boff[2][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int chunk = ws_kstep_chunk(j, h);
+        aoff[j] = ws_frag_off(wline + c, chunk);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) boff[cb][j] = ws_frag_off(WS_ROWS + 32 * cb + c, chunk);
+    }
+    f32x16 acc[2], first[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) acc[cb] = first[cb] = zero16();
+    if (n_st > 0) issue(0, 0);
+    if (n_st > 1) issue(1, 1);
+    int slot = 0, slot2 = 2;   // the slot read now, the slot filled now
+    for (int i = 0; i < n_st; ++i) {
+        // this wave's pieces of stage i have landed (those of stage i + 1 stay in flight) and its fragment reads of the
+        // previous stage are done; past the barrier that holds for every wave: slot is readable, slot2 is free
+        if (i + 1 < n_st) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (i + 2 < n_st) issue(i + 2, slot2);
+        if (i == n_a) {   // (pairs) the first split is complete: its sum is set aside, the second starts from zero
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                first[cb] = acc[cb];
+                acc[cb] = zero16();
+            }
+        }
+        if (worker) {
+            const char* sl = ring + slot * WS_STAGE_BYTES;
+            uint4 a[4], b[2][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                a[j] = *reinterpret_cast<const uint4*>(sl + aoff[j]);
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) b[cb][j] = *reinterpret_cast<const uint4*>(sl + boff[cb][j]);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (XF == 1) a[j] = xf_apply8_core<T>(a[j], xsc, xmu, xb);
+                if (!rs) a[j] = make_uint4(0, 0, 0, 0);
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                    if constexpr (XF == 2) b[cb][j] = xf_apply8_core<T>(b[cb][j], csc[cb], cmu[cb], cbb[cb]);
+                    if (!cs[cb]) b[cb][j] = make_uint4(0, 0, 0, 0);
+                    acc[cb] = Mma16<T>::run(__builtin_bit_cast(s16x8, a[j]), __builtin_bit_cast(s16x8, b[cb][j]), acc[cb]);
+                }
+            }
+        }
+        slot = slot == WS_RING - 1 ? 0 : slot + 1;
+        slot2 = slot2 == WS_RING - 1 ? 0 : slot2 + 1;
+    }
+    if (worker) {
+        float* dstp = part + (long long)blockIdx.x * MR * NS;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            if (!cs[cb]) continue;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int r = wrow0 + acc_row(reg, h);
+                // pairs: p_za + p_(za + 16), the first addition of the reduce launch
+                if (r < MR) dstp[(long long)r * NS + 32 * cb + c] = wp.pairs ? first[cb][reg] + acc[cb][reg] : acc[cb][reg];
+            }
+        }
+    }
+}
 
 // XF: 0 none, 1 the R operand, 2 the S operand is read through the fused BN + ReLU6 (InputXf); 3: the R operand is the
 // gradient of a BN(+ReLU6) OUTPUT and the product wants the gradient of its INPUT: dy is formed from (R = da, bx.y) with
@@ -1516,6 +1674,14 @@ template <typename T, int XF = 0>
 __global__ void __launch_bounds__(512) pw_wgrad_direct_kernel(const T* __restrict__ R, const T* __restrict__ S,
                                                               float* __restrict__ part, int MR, int NS, int HW,
                                                               WdPlan wp, InputXf xf = InputXf{}, BwdXf bx = BwdXf{}) {
+    if constexpr (XF != 3) {
+        // the kernel's only LDS object (a second one beside the DMA ring makes the compiler drain the queue per read)
+        __shared__ __attribute__((aligned(1024))) char ws_ring[WS_RING * WS_STAGE_BYTES];
+        if (wp.stream) {   // block-uniform
+            wd_stream_body<T, XF>(R, S, part, MR, NS, HW, wp, xf, ws_ring);
+            return;
+        }
+    }
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int wr = wave & 3, wc = wave >> 2;
@@ -1649,6 +1815,17 @@ static WdPlan wd_plan(int64_t N, int64_t Cin, int64_t Cout, int64_t HW) {
     p.total_quads = (int)(N * p.quads_per_img);
     const int64_t tiles = cdiv(p.MR, WD_ROWS) * cdiv(p.NS, WD_COLS);
     static const int blocks = [] { const char* e = getenv("OFASR_PW_WGRAD_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+    // OFASR_PW_WGRAD_STREAM=0: the per-lane-load body for every shape (A/B runs)
+    static const bool stream_on = [] { const char* e = getenv("OFASR_PW_WGRAD_STREAM"); return !(e && e[0] == '0'); }();
+    p.stream = stream_on && ws_shape_ok(p.NS, HW) ? 1 : 0;
+    p.pairs = 0;
+    if (p.stream) {
+        // the split count of the per-lane-load body (same partial sums); in whole groups of 64 splits a workgroup walks the
+        // two splits the reduce launch adds first and writes one slab for both: 2 row tiles x nsplit / 2 workgroups
+        p.nsplit = ws_nsplit(p.total_quads, p.MR, p.NS, blocks);
+        p.pairs = ws_pairs_ok(p.nsplit) ? 1 : 0;
+        return p;
+    }
     int64_t want = blocks / (tiles > 0 ? tiles : 1);   // one 8-wave block per CU ...
     if (want > p.total_quads / 4) want = p.total_quads / 4;   // ... but at least 4 quads per slab written
     if (want < 1) want = 1;
@@ -1750,6 +1927,11 @@ __global__ void __launch_bounds__(512) pw_wgrad_direct_f32_kernel(const float* _
                 p += (reg & 3) == 3 ? 5 * (long long)NS : (long long)NS;
             }
     }
+}
+
+static bool wgrad_f32_direct_on() {
+    static const bool on = [] { const char* e = getenv("OFASR_PW_WGRAD_F32_DIRECT"); return e && e[0] == '1'; }();
+    return on;
 }
 
 static WdPlan32 wd_plan32(int64_t N, int64_t Cin, int64_t Cout, int64_t HW) {
@@ -1912,8 +2094,13 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
               2.0 * (double)N * (double)HW * (double)Cin * (double)Cout);
     if constexpr (Elem<T>::is16) {
         if (al) {
-            const WdPlan wp = wd_plan(N, Cin, Cout, HW);
-            dim3 grid((unsigned)wp.nsplit, (unsigned)cdiv(wp.MR, WD_ROWS), (unsigned)cdiv(wp.NS, WD_COLS));
+            WdPlan wp = wd_plan(N, Cin, Cout, HW);
+            if (BXM) {   // no streaming body: the per-lane-load body under the number of slabs the workspace was sized for
+                if (wp.pairs) wp.nsplit /= 2;
+                wp.stream = wp.pairs = 0;
+            }
+            dim3 grid((unsigned)(wp.pairs ? wp.nsplit / 2 : wp.nsplit), (unsigned)cdiv(wp.MR, wp.stream ? WS_ROWS : WD_ROWS),
+                      (unsigned)cdiv(wp.NS, WD_COLS));
             if constexpr (XF) {
                 if (big_is_dy)   // x is the S operand
                     OFASR_LAUNCH((pw_wgrad_direct_kernel<T, 2>), grid, dim3(512), 0, st, R, S, ws, wp.MR, wp.NS,
@@ -1936,7 +2123,7 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
             if (rc) return rc;
             const long long tot = (long long)wp.MR * wp.NS;
             OFASR_LAUNCH(pw_wgrad_reduce_kernel, dim3((unsigned)cdiv(tot, 64)), dim3(64 * WR_ZL), 0, st, ws, dw, wp.MR,
-                               wp.NS, wp.nsplit, sr, ss);
+                               wp.NS, wp.nsplit, sr, ss, wp.pairs);
             return check_launch(name);
         }
     }
@@ -1948,8 +2135,7 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
         // OFF by default (OFASR_PW_WGRAD_F32_DIRECT=1): 68 against 71.6 us per call in isolation, but the fp32 training step is
         // 22.96 against 22.78 ms with it (two A/B pairs) -- a wave-load of 64 lanes in 32 different rows runs at about one
         // lane per clock in the address path, which is what bounds this kernel, and it competes with the chain for that path
-        static const bool f32_direct = [] { const char* e = getenv("OFASR_PW_WGRAD_F32_DIRECT"); return e && e[0] == '1'; }();
-        if (al && f32_direct) {
+        if (al && wgrad_f32_direct_on()) {
             const WdPlan32 wp = wd_plan32(N, Cin, Cout, HW);
             dim3 grid((unsigned)wp.nsplit, (unsigned)cdiv(wp.MR, WD_ROWS), (unsigned)cdiv(wp.NS, WD_COLS));
             OFASR_LAUNCH(pw_wgrad_direct_f32_kernel, grid, dim3(512), 0, st, (const float*)R, (const float*)S, ws, wp.MR, wp.NS,
@@ -1958,7 +2144,7 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
             if (rc) return rc;
             const long long tot = (long long)wp.MR * wp.NS;
             OFASR_LAUNCH(pw_wgrad_reduce_kernel, dim3((unsigned)cdiv(tot, 64)), dim3(64 * WR_ZL), 0, st, ws, dw, wp.MR, wp.NS,
-                         wp.nsplit, sr, ss);
+                         wp.nsplit, sr, ss, 0);
             return check_launch(name);
         }
     }
@@ -1973,7 +2159,7 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
     if (rc) return rc;
     const long long tot = (long long)p.MR * p.NS;
     OFASR_LAUNCH(pw_wgrad_reduce_kernel, dim3((unsigned)cdiv(tot, 64)), dim3(64 * WR_ZL), 0, st, ws, dw, p.MR, p.NS,
-                       p.nsplit, sr, ss);
+                       p.nsplit, sr, ss, 0);
     return check_launch(name);
 }
 
@@ -2197,11 +2383,21 @@ OFASR_EXPORT size_t ofasr_pwconv_wgrad_workspace(int64_t N, int64_t Cin, int64_t
     // the 16-bit and fp32 kernels stage different pixel counts per barrier: size for the larger plan
     const WgradPlan p4 = wgrad_plan(N, Cin, Cout, HW, 4), p2 = wgrad_plan(N, Cin, Cout, HW, 2);
     int ns = p4.nsplit > p2.nsplit ? p4.nsplit : p2.nsplit;
-    const int nd = wd_plan(N, Cin, Cout, HW).nsplit;
+    const WdPlan wd = wd_plan(N, Cin, Cout, HW);
+    const int nd = wd.pairs ? wd.nsplit / 2 : wd.nsplit;   // slabs written
     ns = nd > ns ? nd : ns;
-    const int nd32 = wd_plan32(N, Cin, Cout, HW).nsplit;
-    ns = nd32 > ns ? nd32 : ns;
+    if (wgrad_f32_direct_on()) {   // the opt-in fp32 direct kernel plans its own (larger) split count
+        const int nd32 = wd_plan32(N, Cin, Cout, HW).nsplit;
+        ns = nd32 > ns ? nd32 : ns;
+    }
     return (size_t)ns * (size_t)p4.MR * (size_t)p4.NS * sizeof(float);
+}
+
+OFASR_EXPORT int ofasr_debug_pwconv_wgrad_xf(const void* dy, const void* x, float* dw, int64_t ldw, int64_t N, int64_t Cin,
+                                             int64_t Cout, int64_t HW, int dtype, const float* scale, const float* shift,
+                                             const float* mean, void* workspace, size_t workspace_bytes, void* stream) {
+    return pwconv_wgrad_xf(dy, x, dw, ldw, N, Cin, Cout, HW, dtype, InputXf{scale, shift, mean}, workspace, workspace_bytes,
+                           stream);
 }
 
 OFASR_EXPORT int ofasr_pwconv_wgrad(const void* dy, const void* x, float* dw, int64_t ldw, int64_t N, int64_t Cin,

@@ -60,6 +60,11 @@ def main():
                   lambda: L.ofasr_pwconv_wgrad(P(xm), P(x64), P(dw1), 64, N, 64, mid, HW, code, P(ws), wsn, st)))
     cases.append(("pwconv_wgrad project", act_big,
                   lambda: L.ofasr_pwconv_wgrad(P(x64), P(xm), P(dw2), mid, N, mid, 64, HW, code, P(ws), wsn, st)))
+    if a.dtype != "f32":   # the project weight gradient as the MB block runs it: x read through the fused BN + ReLU6
+        xfc = torch.ones(3, mid, device=dev)
+        cases.append(("pwconv_wgrad project, fused input", act_big,
+                      lambda: L.ofasr_debug_pwconv_wgrad_xf(P(x64), P(xm), P(dw2), mid, N, mid, 64, HW, code, P(xfc[0]), P(xfc[1]),
+                                                            P(xfc[2]), P(ws), wsn, st)))
     for K in (3, 5, 7):
         f = torch.randn(mid, 1, K, K, device=dev) * 0.1
         df = torch.zeros_like(f)
