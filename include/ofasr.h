@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 310 /* + ofasr_tile_resize_scatter_u8, ofasr_tile_resize_scatter_yuv420, ofasr_tile_resize_scatter_yuv420p16 */
+#define OFASR_VERSION 311 /* + ofasr_mode_unpack_u8, ofasr_mode_pack_u8 */
 
 typedef enum {
     OFASR_OK = 0,
@@ -534,6 +534,34 @@ int ofasr_tile_resize_scatter_yuv420p16(const void* src, int64_t n, int64_t sh, 
                                         const int32_t* vtab, int kh, const int32_t* htab, int kw, int depth,
                                         const int32_t* coeffs, void* y, void* u, void* v, int64_t TH, int64_t TW,
                                         int64_t max_eh, int64_t max_ew, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Alpha and greyscale around the RGB image path (csrc/mode_io.hip; host statement: modes.py) -- for
+ * TiledUpscaler.upscale_image: an L, LA or RGBA image goes in and comes out in its own mode, and everything between the two
+ * calls is the RGB path as it is.  C is the channel count of the HWC uint8 image: 1 (L), 2 (LA) or 4 (RGBA); 3 has nothing
+ * to do here and is refused.
+ *   ofasr_mode_unpack_u8: img [H, W, C] -> rgb [H, W, 3] and alpha [H, W].  L / LA: R = G = B = L (Pillow's
+ *     convert("RGB") of L); RGBA: the first three channels untouched (straight alpha: the colour under transparent pixels
+ *     is kept).  alpha is the last channel of LA / RGBA; for C = 1 it must be null, otherwise it must not be.  One pass;
+ *     any byte-aligned pointers (4-byte accesses only where all three are aligned for them, bytes elsewhere).
+ *   ofasr_mode_pack_u8: rgb [TH, TW, 3] (the RGB output) and alpha_src [H, W] (the SOURCE alpha) -> out [TH, TW, C].
+ *     alpha_out = Pillow's Image.resize((TW, TH), filter) of alpha_src: horizontal pass, clip, vertical pass, clip, 22
+ *     coefficient bits, from the host tables vtab [TH][2 + kh] / htab [TW][2 + kw] of int32 rows (min, count, k[0 ..))
+ *     in alpha_src coordinates (resize.axis_table; modes.alpha_tables); an axis that keeps its size takes the one-tap
+ *     table.  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 of rgb (Pillow's convert("L")).  out = L | L, alpha_out |
+ *     R, G, B, alpha_out.  For C = 1 alpha_src, the tables, kh, kw, H and W are not read (null is fine; H, W must still
+ *     be positive).  One workgroup per 16 x 64 target tile, Pillow's intermediate in LDS.  4-byte stores where an aligned
+ *     dword lies inside a row's bytes of a tile, byte stores at the ragged ends, for any alignment of `out`: no store
+ *     covers a byte outside out.  Every access stays inside its tensor whatever the device tables hold (counts clamped
+ *     to kh / kw, source indices into alpha_src, a tile's source rows to the 24 its LDS image holds): a wrong table gives
+ *     wrong values, never a fault.
+ * Plain loads and stores: two calls give identical bytes.  64-bit addressing.  OFASR_ERR_INVALID_ARG: C not 1, 2 or 4, a
+ * null pointer (or an alpha plane with C = 1), a non-positive size.  OFASR_ERR_UNSUPPORTED: kh or kw outside 1 .. 7 or a
+ * target smaller than the alpha plane (pack enlarges only: lanczos enlarging has 7 taps), more than 2^40 pixels.
+ * ------------------------------------------------------------------------------------------- */
+int ofasr_mode_unpack_u8(const void* img, int C, void* rgb, void* alpha, int64_t H, int64_t W, void* stream);
+int ofasr_mode_pack_u8(const void* rgb, const void* alpha_src, const int32_t* vtab, int kh, const int32_t* htab, int kw,
+                       void* out, int C, int64_t H, int64_t W, int64_t TH, int64_t TW, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Window reuse between video frames (csrc/reuse.hip; host statement: video.py window_support / changed_windows_host) --

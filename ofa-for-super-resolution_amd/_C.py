@@ -139,6 +139,9 @@ SIGNATURES = {
     "ofasr_tile_resize_scatter_yuv420p16": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_int,
                                                      _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64,
                                                      _c_vp]),
+    "ofasr_mode_unpack_u8": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
+    "ofasr_mode_pack_u8": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64,
+                                    _c_vp]),
     "ofasr_window_diff_slabs": (_c_i64, [_c_i64, _c_i64]),
     "ofasr_window_diff_yuv420": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64,
                                           _c_vp, _c_vp]),

@@ -363,6 +363,83 @@ def rgb_to_yuv420_u8(rgb, matrix="bt601", full_range=False, out=None):
     return y, u, v
 
 
+# ------------------------------------------------------------------------------ image modes (alpha, greyscale)
+MODE_MAX_TAPS = 7     # taps per axis of ofasr_mode_pack_u8: lanczos enlarging (modes.MAX_TAPS)
+
+
+def _u8(t, what, shape_ok, need):
+    _gpu(t)
+    if t.dtype != torch.uint8 or not t.is_contiguous() or not shape_ok(t) or t.numel() == 0:
+        raise ValueError("%s needs %s, got %s %s" % (what, need, tuple(t.shape), t.dtype))
+
+
+def mode_unpack_u8(img, rgb=None, alpha=None):
+    """HWC uint8 [H, W, C] on the GPU, C in {1: L, 2: LA, 4: RGBA} -> (rgb [H, W, 3], alpha [H, W] or None for L):
+    modes.split_host (ofasr_mode_unpack_u8, csrc/mode_io.hip).  `rgb`, `alpha`: tensors to write into."""
+    _u8(img, "mode_unpack_u8", lambda t: t.dim() == 3 and t.size(2) in (1, 2, 4),
+        "a contiguous HWC uint8 image of 1, 2 or 4 channels")
+    H, W, C = img.shape
+    if rgb is None:
+        rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=img.device)
+    if alpha is None and C != 1:
+        alpha = torch.empty(H, W, dtype=torch.uint8, device=img.device)
+    _u8(rgb, "mode_unpack_u8", lambda t: tuple(t.shape) == (H, W, 3), "a contiguous uint8 RGB output [%d, %d, 3]" % (H, W))
+    if C == 1:
+        if alpha is not None:
+            raise ValueError("mode_unpack_u8: an L image has no alpha plane")
+    else:
+        _u8(alpha, "mode_unpack_u8", lambda t: tuple(t.shape) == (H, W), "a contiguous uint8 alpha output [%d, %d]" % (H, W))
+    if rgb.device != img.device or (alpha is not None and alpha.device != img.device):
+        raise ValueError("mode_unpack_u8 needs all tensors on one GPU")
+    _C.check(_C.lib().ofasr_mode_unpack_u8(_p(img), C, _p(rgb), None if alpha is None else _p(alpha), H, W, _stream()),
+             "ofasr_mode_unpack_u8")
+    return rgb, alpha
+
+
+def mode_pack_u8(rgb, channels, alpha=None, vtab=None, htab=None, out=None):
+    """the RGB output [TH, TW, 3] (HWC uint8, GPU) -> HWC uint8 [TH, TW, channels], channels in {1, 2, 4}: the luma of rgb
+    (Pillow's convert("L")) for L / LA, rgb itself for RGBA, and as last channel of LA / RGBA the SOURCE alpha plane
+    `alpha` [H, W] resized to TH x TW with the int32 coefficient tables vtab [TH, 2 + kh] / htab [TW, 2 + kw] on the GPU
+    (modes.alpha_tables: Pillow's resize, at most 7 taps per axis, enlarging only) -- modes.join_host(rgb, channels,
+    modes.alpha_host(alpha, TH, TW, filter)) (ofasr_mode_pack_u8, csrc/mode_io.hip).  channels = 1 takes no alpha and no
+    tables.  `out`: the tensor to write into."""
+    if isinstance(channels, bool) or channels not in (1, 2, 4):
+        raise ValueError("mode_pack_u8: channels must be 1 (L), 2 (LA) or 4 (RGBA), got %r" % (channels,))
+    _u8(rgb, "mode_pack_u8", lambda t: t.dim() == 3 and t.size(2) == 3, "a contiguous HWC uint8 RGB image")
+    TH, TW = rgb.size(0), rgb.size(1)
+    H, W = TH, TW
+    if channels == 1:
+        if alpha is not None or vtab is not None or htab is not None:
+            raise ValueError("mode_pack_u8: an L image takes no alpha plane and no tables")
+    else:
+        if alpha is None or vtab is None or htab is None:
+            raise ValueError("mode_pack_u8: %d channels need the source alpha plane and both coefficient tables" % channels)
+        _u8(alpha, "mode_pack_u8", lambda t: t.dim() == 2, "a contiguous uint8 alpha plane [H, W]")
+        H, W = alpha.shape
+        if H > TH or W > TW:
+            raise ValueError("mode_pack_u8 enlarges only: a %dx%d alpha plane for a %dx%d image" % (W, H, TW, TH))
+        for t, rows, what in ((vtab, TH, "vertical"), (htab, TW, "horizontal")):
+            _gpu(t)
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 2 or t.size(0) != rows or \
+                    not 3 <= t.size(1) <= 2 + MODE_MAX_TAPS:
+                raise ValueError("mode_pack_u8 needs a contiguous int32 %s coefficient table [%d, 2 + taps] on the GPU, "
+                                 "taps <= %d" % (what, rows, MODE_MAX_TAPS))
+        if any(t.device != rgb.device for t in (alpha, vtab, htab)):
+            raise ValueError("mode_pack_u8 needs all tensors on one GPU")
+    if out is None:
+        out = torch.empty(TH, TW, channels, dtype=torch.uint8, device=rgb.device)
+    _u8(out, "mode_pack_u8", lambda t: tuple(t.shape) == (TH, TW, channels),
+        "a contiguous uint8 output [%d, %d, %d]" % (TH, TW, channels))
+    if out.device != rgb.device:
+        raise ValueError("mode_pack_u8 needs all tensors on one GPU")
+    if channels == 1:
+        args = (None, None, 1, None, 1)
+    else:
+        args = (_p(alpha), _p(vtab), vtab.size(1) - 2, _p(htab), htab.size(1) - 2)
+    _C.check(_C.lib().ofasr_mode_pack_u8(_p(rgb), *args, _p(out), channels, H, W, TH, TW, _stream()), "ofasr_mode_pack_u8")
+    return out
+
+
 # ------------------------------------------------------------------------------ geometric self-ensemble
 ENSEMBLE_SIZES = (1, 2, 4, 8)
 

@@ -59,13 +59,19 @@ reads the two counts (the one synchronisation routing adds) and runs the batch l
 plan's size, so each network replays the graph of its full-batch shape.  The class is a function of the window's own
 bytes, so it composes with window reuse: an unchanged window keeps its class and its output.  There is no blending:
 neighbouring cores from different networks can differ at the seam.
+
+Image modes (`upscale_image`, `split_image`, `join_image`): an L, LA or RGBA image keeps its mode (modes.py is the
+definition).  ofasr_mode_unpack_u8 makes the RGB image (R = G = B = L; RGBA's colour untouched) that everything above reads,
+upscale() runs on it unchanged, and ofasr_mode_pack_u8 (csrc/mode_io.hip) joins its output -- as it is, or as Pillow's
+convert("L") of it -- with the SOURCE alpha plane resized straight to the output's size, Pillow's Image.resize bit for
+bit.  The alpha does not go through the network.  Three channels take no new kernel: upscale_image is upscale.
 """
 import math
 from fractions import Fraction
 
 import torch
 
-from . import _C, ops, resize, routing
+from . import _C, modes, ops, resize, routing
 from .graphed import GraphedEval
 
 LIMIT = 2 ** 31          # no activation of one window reaches 2^31 bytes (fp32); no batched tensor 2^31 elements
@@ -732,6 +738,7 @@ class TiledUpscaler(object):
         self.graphed_easy = GraphedEval(easy_net, autocast_dtype=self.autocast_dtype, copy_output=False) \
             if graphed and easy_net is not None else None
         self._plans = {}
+        self._alpha_tables = {}
 
     def plan(self, H, W, out_size=None, resample="lanczos", even=False):
         """the tile plan of an H x W input; with `out_size` = (TH, TW) the ResizePlan of that target (kept: its tables
@@ -942,6 +949,66 @@ class TiledUpscaler(object):
 
         self._run(img, whole, sink)
         return out
+
+    # ------------------------------------------------------------------------------------------ image modes
+    def split_image(self, img):
+        """an HWC uint8 image of 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA) channels (CPU or GPU tensor, or numpy array) ->
+        (rgb [H, W, 3], channels, alpha [H, W] or None), on the GPU: modes.split_host (ops.mode_unpack_u8).  The RGB
+        image is what upscale(), window_activity() and the metric take; three channels pass through untouched."""
+        if not torch.is_tensor(img):
+            img = torch.from_numpy(img)
+        if img.dtype != torch.uint8 or img.dim() != 3 or img.size(2) not in modes.MODES:
+            raise ValueError("upscale_image takes an HWC uint8 image of 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA) channels, got %s %s"
+                             % (tuple(img.shape), img.dtype))
+        C = int(img.size(2))
+        if C == 3:
+            return self._image(img), 3, None
+        dev = next(self.net.parameters()).device
+        if dev.type != "cuda":
+            raise _C.OfasrError("TiledUpscaler needs the network on the GPU")
+        rgb, alpha = ops.mode_unpack_u8(img.to(dev).contiguous())
+        return rgb, C, alpha
+
+    def _alpha_device_tables(self, H, W, TH, TW, filter, device):
+        """modes.alpha_tables as int32 tensors on `device`; up to 8 are kept and all are dropped when a ninth comes, as
+        plan() does"""
+        key = (int(H), int(W), int(TH), int(TW), filter, str(device))
+        if key not in self._alpha_tables:
+            if len(self._alpha_tables) >= 8:
+                self._alpha_tables.clear()
+            self._alpha_tables[key] = tuple(torch.from_numpy(t).to(device) for t in modes.alpha_tables(H, W, TH, TW, filter))
+        return self._alpha_tables[key]
+
+    def join_image(self, rgb_out, channels, alpha=None, in_hw=None, alpha_resample=modes.ALPHA_FILTER):
+        """the RGB output [TH, TW, 3] on the GPU, the channel count and the SOURCE alpha plane of split_image -> the HWC
+        uint8 output of that channel count: modes.join_host(rgb_out, channels, modes.alpha_host(alpha, TH, TW,
+        alpha_resample)) (ops.mode_pack_u8).  `in_hw`: the input's (H, W), checked against the alpha plane.  Three
+        channels: rgb_out itself."""
+        resize.check_filter(alpha_resample)
+        if isinstance(channels, bool) or channels not in modes.MODES:
+            raise ValueError("channels must be one of %s, got %r" % (sorted(modes.MODES), channels))
+        if (alpha is not None) != (channels in (2, 4)):
+            raise ValueError("%s %s an alpha plane" % (modes.MODES[channels], "needs" if alpha is None else "takes no"))
+        if channels == 3:
+            return rgb_out
+        if channels == 1:
+            return ops.mode_pack_u8(rgb_out, 1)
+        if alpha.dim() != 2 or (in_hw is not None and tuple(int(v) for v in in_hw) != tuple(alpha.shape)):
+            raise ValueError("the alpha plane must be the input's [H, W], got %s" % (tuple(alpha.shape),))
+        vtab, htab = self._alpha_device_tables(alpha.size(0), alpha.size(1), rgb_out.size(0), rgb_out.size(1), alpha_resample,
+                                               rgb_out.device)
+        return ops.mode_pack_u8(rgb_out, channels, alpha, vtab, htab)
+
+    def upscale_image(self, img, whole=False, out_size=None, resample="lanczos", alpha_resample=modes.ALPHA_FILTER):
+        """upscale() for an HWC uint8 image of 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA) channels: the output, on the GPU, has
+        the input's channel count (modes.py is the definition).  The network sees L as R = G = B and RGBA's colour
+        untouched; the colour of the result is upscale() of that, bit for bit (for L / LA its Pillow luma); the alpha is
+        the SOURCE alpha resized straight to the output's size with `alpha_resample` ("bicubic" or "lanczos"), Pillow's
+        Image.resize bit for bit; it does not go through the network.  Three channels: upscale() itself."""
+        resize.check_filter(alpha_resample)
+        rgb, C, alpha = self.split_image(img)
+        out = self.upscale(rgb, whole=whole, out_size=out_size, resample=resample)
+        return self.join_image(out, C, alpha, rgb.shape[:2], alpha_resample)
 
     def _yuv420_frame(self, y, u, v):
         """(device, the three planes on it, H, W) of one frame for the YUV paths; refuses what they cannot take"""

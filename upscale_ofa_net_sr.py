@@ -3,9 +3,10 @@
 
 The network is a static SRNetS4 / SRNetX4 exported with `search_ofa_net_sr.py --export DIR` or
 `eval_ofa_net_sr.py --export DIR` (DIR/net_config.json + DIR/static_state_dict.pth); a supernet checkpoint is not loaded
-here: export its sub-network first.  Inputs are image files or directories of them; grayscale and RGBA images become RGB,
-and every output is written as OUTDIR/<name>.png.  The next image is decoded (and the previous one encoded) on a small
-host thread pool while the GPU upscales the current one.  Prints output megapixels per second at the end.
+here: export its sub-network first.  Inputs are image files or directories of them; grayscale and RGBA images become RGB
+(unless --keep-mode, below), and every output is written as OUTDIR/<name>.png.  The next image is decoded (and the
+previous one encoded) on a small host thread pool while the GPU upscales the current one.  Prints output megapixels per
+second at the end.
 --reference DIR scores every output against the equally named ground-truth image in DIR on the GPU (Y-PSNR and Y-SSIM by
 the HIP metric kernel, --shave border pixels left out), prints the numbers and writes them to OUTDIR/quality.json.
 --out-size WxH writes every output at that size instead of the network's own: any size from the input's up to the
@@ -17,7 +18,14 @@ neighbouring luma samples (L = (77 R + 150 G + 29 B + 128) >> 8, in 8-bit levels
 DIR, every other window the --static network; both need the same upscale factor and share one tile plan.  There is no
 blending: neighbouring cores from different networks can differ at the seam.  --route-report prints per image the easy and
 hard window counts and the min / median / max of the per-window measure (what to look at when choosing T) and, with
---reference, writes the counts into quality.json.  Routing needs the tiled path: it is refused with --whole."""
+--reference, writes the counts into quality.json.  Routing needs the tiled path: it is refused with --whole.
+--keep-mode writes every output in its input's mode instead of RGB: RGB, RGBA, L (greyscale) and LA files keep theirs, 1-bit
+files become L, paletted files with transparency and every file with a tRNS chunk become RGBA, paletted files without
+become RGB, and everything else (CMYK, 16-bit, float, YCbCr ...) becomes RGB as without the flag.  The network still sees
+RGB (R = G = B for greyscale; the colour under transparent pixels as it is, neither premultiplied nor bled), the RGB it
+returns is what the other options and --reference see, and a greyscale output is Pillow's convert("L") of it.  The alpha
+channel does not go through the network: it is the file's alpha resized straight to the output's size as Pillow's
+Image.resize does it, bit for bit (--alpha-resample bicubic, the default, or lanczos).  8 bits per channel."""
 import argparse
 import collections
 import concurrent.futures
@@ -63,6 +71,10 @@ def parse_args(argv=None):
     ap.add_argument("--easy-threshold", default=None, metavar="T",
                     help="a window is easy when its mean absolute luma difference, in 8-bit levels, is at most T")
     ap.add_argument("--route-report", action="store_true", help="per image: easy / hard windows and the activity")
+    ap.add_argument("--keep-mode", action="store_true",
+                    help="write RGBA, L and LA inputs (and paletted ones with transparency, as RGBA) in their own mode")
+    ap.add_argument("--alpha-resample", default=None, choices=["bicubic", "lanczos"],
+                    help="with --keep-mode: the filter that brings the alpha channel to the output's size (default: bicubic)")
     ap.add_argument("--reference", default=None, metavar="PATH",
                     help="directory of ground-truth HR images named as the inputs: report Y-PSNR / Y-SSIM per image")
     ap.add_argument("--shave", type=int, default=0, help="with --reference: border pixels left out of the metric")
@@ -74,6 +86,8 @@ def parse_args(argv=None):
         ap.error("--route-report needs --easy-static and --easy-threshold")
     if a.easy_static is not None and a.whole:
         ap.error("--whole runs one window per image: there is nothing to route")
+    if a.alpha_resample is not None and not a.keep_mode:
+        ap.error("--alpha-resample needs --keep-mode")
     if a.easy_threshold is not None:
         try:
             importlib.import_module(PKG + ".routing").activity_limit(a.easy_threshold, 1, 2)
@@ -102,9 +116,33 @@ def decode(path):
         return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
 
 
+def decode_keep(path):
+    """HWC uint8 numpy array in the mode --keep-mode keeps for the file: [H, W, 1] L, [H, W, 2] LA, [H, W, 3] RGB or
+    [H, W, 4] RGBA"""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as im:
+        if "transparency" in im.info or im.mode == "PA":
+            im = im.convert("RGBA")
+        elif im.mode == "1":
+            im = im.convert("L")
+        elif im.mode not in ("RGB", "RGBA", "L", "LA"):
+            im = im.convert("RGB")
+        arr = np.array(im, dtype=np.uint8)
+    return np.ascontiguousarray(arr if arr.ndim == 3 else arr[:, :, None])
+
+
 def encode(arr, path):
     from PIL import Image
     Image.fromarray(arr, "RGB").save(path, format="PNG")
+    return path
+
+
+def encode_keep(arr, path):
+    """[H, W, C] uint8 -> a PNG of mode L, LA, RGB or RGBA by C"""
+    from PIL import Image
+    mode = {1: "L", 2: "LA", 3: "RGB", 4: "RGBA"}[arr.shape[2]]
+    Image.fromarray(arr[:, :, 0] if mode == "L" else arr, mode).save(path, format="PNG")
     return path
 
 
@@ -166,16 +204,20 @@ def main(argv=None):
             raise SystemExit("--reference %s is not a directory" % a.reference)
         refs = [reference_path(a.reference, f) for f in files]
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(WORKERS, len(files) + 1)) as pool:
-        pending = collections.deque(pool.submit(decode, f) for f in files[:2])
+        dec = decode_keep if a.keep_mode else decode
+        pending = collections.deque(pool.submit(dec, f) for f in files[:2])
         t0 = time.perf_counter()
         for i, f in enumerate(files):
             img = pending.popleft().result()
             if i + 2 < len(files):
-                pending.append(pool.submit(decode, files[i + 2]))
+                pending.append(pool.submit(dec, files[i + 2]))
             out_size = None if a.out_size is None else (a.out_size[1], a.out_size[0])
+            src = torch.from_numpy(img)
+            if a.keep_mode:                 # everything up to the join below sees the RGB image, as without the flag
+                src, channels, alpha = up.split_image(src)
             try:
                 plan = None if a.whole else up.plan(img.shape[0], img.shape[1], out_size, a.resample)
-                out_gpu = up.upscale(torch.from_numpy(img), whole=a.whole, out_size=out_size, resample=a.resample)
+                out_gpu = up.upscale(src, whole=a.whole, out_size=out_size, resample=a.resample)
             except ValueError as e:
                 if a.out_size is None:
                     raise
@@ -183,7 +225,7 @@ def main(argv=None):
             if easy is not None:
                 routes.append({k: up.route_stats[k] for k in ("windows", "easy", "hard")})
                 if a.route_report:
-                    act = up.window_activity(torch.from_numpy(img), out_size, a.resample)
+                    act = up.window_activity(src, out_size, a.resample)
                     print("%s: easy %d hard %d of %d windows; activity min %.3f median %.3f max %.3f" % (
                         f, routes[-1]["easy"], routes[-1]["hard"], routes[-1]["windows"], float(act.min()),
                         float(act.median()), float(act.max())))
@@ -197,9 +239,11 @@ def main(argv=None):
                                      % (refs[i], ref.shape[1], ref.shape[0], a.shave))
                 scores.append((f, refs[i], utils.quality_y_device(out_gpu, torch.from_numpy(ref).to(out_gpu.device),
                                                                   a.shave)))
+            if a.keep_mode:
+                out_gpu = up.join_image(out_gpu, channels, alpha, img.shape[:2], a.alpha_resample or "bicubic")
             out = out_gpu.cpu().numpy()
             dst = out_path(a.out, f, taken)
-            saves.append(pool.submit(encode, out, dst))
+            saves.append(pool.submit(encode_keep if a.keep_mode else encode, out, dst))
             mpix += out.shape[0] * out.shape[1] / 1e6
             print("%s: %dx%d -> %dx%d%s" % (f, img.shape[1], img.shape[0], out.shape[1], out.shape[0],
                                            "" if plan is None else "  (%d windows of %dx%d, %.2fx halo overhead)"
