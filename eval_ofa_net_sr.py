@@ -68,7 +68,10 @@ def main(argv=None):
     ap.add_argument("--self-ensemble", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
                     help="with --static: also score the geometric self-ensemble, the fp32 mean of the outputs under the "
                          "first K of the 8 flips / transposes (2: + horizontal flip, 4: + vertical flips, 8: + transposes)")
+    vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
+    vf.add_video_args(ap)
     a = ap.parse_args(argv)
+    video_kw = vf.take_video_args(a)        # --video: evaluate on the evaluation frames of raw YUV 4:2:0 video
     if a.self_ensemble != 1 and not a.static:
         ap.error("--self-ensemble needs an exported static network (--static DIR)")
     import torch
@@ -86,10 +89,13 @@ def main(argv=None):
              (512, 512), (512, 512), (512, 768), (512, 512), (656, 528), (388, 584)]
     if a.test_sizes:
         sizes = [tuple(int(v) for v in s.split("x")) for s in a.test_sizes.split(",")]
-    cfg = rm.Div2K_SetXXRunConfig(n_epochs=1, init_lr=1e-3, opt_type="adam", no_decay_keys="bn#bias",
-                                  label_smoothing=0.0, train_batch_size=1, test_batch_size=1, image_size=256,
-                                  test_sizes=sizes,
-                                  n_train_batches=1, allow_synthetic=True if a.synthetic else None)
+    kw = dict(n_epochs=1, init_lr=1e-3, opt_type="adam", no_decay_keys="bn#bias", label_smoothing=0.0,
+              train_batch_size=1, test_batch_size=1)
+    if video_kw:
+        cfg = rm.VideoFramesRunConfig(image_size=32, **dict(kw, **video_kw))
+    else:
+        cfg = rm.Div2K_SetXXRunConfig(image_size=256, test_sizes=sizes, n_train_batches=1,
+                                      allow_synthetic=True if a.synthetic else None, **kw)
     mgr = rm.SRRunManager(a.path, net, cfg, init=a.checkpoint is None and not a.static, mix_prec=a.mix_prec, num_gpus=1)
     if a.static:
         key = input_key(net.upscale)
@@ -101,7 +107,7 @@ def main(argv=None):
         if a.export:
             export_static(net, a.export)
     import time
-    n_img = sum(b["image"].shape[0] for b in cfg.test_loader)
+    n_img = len(cfg.test_loader) if video_kw else sum(b["image"].shape[0] for b in cfg.test_loader)
 
     def run():
         if a.batch1:

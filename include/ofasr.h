@@ -694,6 +694,28 @@ int ofasr_add(const void* a, const void* b, void* y, int64_t n, int dtype, void*
 int ofasr_aug_gather_u8(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, void* out_u8,
                         void* out_f32, void* stream);
 
+/* The same augmentation on GPU-resident planar YUV 4:2:0 video frames (8 bits a sample) with the colour decode fused in:
+ * the batch equals ofasr_aug_gather_u8 over ofasr_yuv420_to_rgb_u8 of every frame, byte for byte, and no RGB frame exists
+ * (host statement: augment.gather_yuv420_np / apply_params_yuv420_np).  One launch per batch.
+ *   pool:    device uint8 buffer of pool_bytes bytes holding frames as they sit in a yuv420p / Y4M file: Y [H, W], then
+ *            U [H/2, W/2], then V [H/2, W/2], contiguous.
+ *   table:   the 12 columns above; offset = byte offset of a frame's Y plane, H, W = the frame's (even) sides.
+ *   coeffs:  host int32[6] decode table (yo, cy, rv, gu, gv, bu), as for ofasr_yuv420_to_rgb_u8 (same bounds).
+ *   per output (n, c, y, x):  xin, yin as above; outside [0, S): 0.  Otherwise py = i + yin, px = j + (flip ? S-1-xin :
+ *            xin) and the value is channel c of the decode of the WHOLE frame at (py, px): chroma taps cy0 = py >> 1 and
+ *            the neighbour row cy0 - 1 (even py) / cy0 + 1 (odd py), columns alike from px, both clamped into the plane
+ *            (edge replication at the frame's edge, not the crop's; parity from frame coordinates),
+ *            (9a + 3b + 3c + d + 8) >> 4, then the 14-bit matrix with + 2^13 >> 14 and the clamp to 0 .. 255.
+ * Table entries are clamped in the kernel, with Se = S rounded up to even: H = clamp(H, Se, 2^24) & ~1, W alike,
+ * 0 <= i <= H-S, 0 <= j <= W-S, 0 <= offset <= pool_bytes, and the byte address of each of a pixel's 9 samples (Y:
+ * offset + py*W + px; U: offset + H*W + cr*(W/2) + cc; V: offset + H*W + (H/2)*(W/2) + cr*(W/2) + cc) to
+ * [0, pool_bytes-1], so no table content makes an access leave pool.
+ * OFASR_ERR_UNSUPPORTED: S > 4096, n > 65535, pool_bytes < Se*Se*3/2 (no frame with even H, W >= S fits).
+ * OFASR_ERR_INVALID_ARG: a coefficient outside the 14-bit tables' range.  Even H, W >= S per row is the caller's
+ * contract (augment.make_table(..., yuv420=True) refuses the rest on the host).  Plain loads and stores, no atomics. */
+int ofasr_aug_gather_yuv420(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S,
+                            const int32_t* coeffs, void* out_u8, void* out_f32, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Y-channel quality metrics: exact SSE (for Y-PSNR) and mean SSIM of two image batches, per image  -- replaces the host
  * round trip of the reference's logged metric (sr_run_manager.py:567-597: tensor2img -> rgb2y -> psnr on numpy arrays)

@@ -158,6 +158,7 @@ SIGNATURES = {
                                      _c_vp]),
     "ofasr_add": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp]),
     "ofasr_aug_gather_u8": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "ofasr_aug_gather_yuv420": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ofasr_quality_y_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "ofasr_quality_y": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_sz,
                                  _c_vp]),

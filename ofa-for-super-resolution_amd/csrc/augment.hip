@@ -1,4 +1,5 @@
-// augment.hip -- the training augmentation on GPU-resident images (ofasr_aug_gather_u8).
+// augment.hip -- the training augmentation on GPU-resident images (ofasr_aug_gather_u8) and on GPU-resident planar
+// YUV 4:2:0 video frames with the colour decode fused in (ofasr_aug_gather_yuv420, stated before its kernel below).
 //
 // The DIV2K training sample is RandomCrop(S) -> RandomHorizontalFlip -> RandomRotation((-90, 90)) of a decoded RGB image
 // (data_providers/div2k_setxx.py).  With the decoded images resident in one uint8 pool, the three transforms are one
@@ -27,6 +28,7 @@
 // plane for the fp32 batch when S % 4 == 0 and the outputs are aligned for them; element stores otherwise (S = 30: rows
 // are not dword-aligned).
 #include "ofasr_common.h"
+#include "yuv_block.h"
 
 namespace ofasr {
 
@@ -111,9 +113,162 @@ static void aug_launch(const void* pool, int64_t pool_bytes, const int64_t* tabl
                  (const long long*)table, (int)S, (uint8_t*)out_u8, (float*)out_f32);
 }
 
+// ---- the same gather from a pool of planar YUV 4:2:0 frames (ofasr_aug_gather_yuv420) --------------------------------
+// A frame sits in the pool as it sits in a yuv420p / Y4M file: Y [H, W], U [H/2, W/2], V [H/2, W/2], contiguous, 8 bits
+// a sample; `offset` is the byte offset of its Y plane.  With xin, yin, ok from the walk above,
+//   py = i + yin,  px = j + (flip ? S - 1 - xin : xin),  out[n, c, y, x] = ok ? RGB(frame)[py, px, c] : 0
+// where RGB(frame) is the decode of the WHOLE frame (video.yuv420_to_rgb_host, stated in yuv.hip's header): the chroma
+// taps are cy0 = py >> 1 and its neighbour row cy0 - 1 (even py) / cy0 + 1 (odd py), columns alike from px, clamped into
+// the PLANE -- chroma replicates at the frame's edge, never at the crop's, and the parity is the frame coordinate's, so a
+// crop at an odd corner decodes as the frame does there.  The batch equals aug_gather_u8 of the decoded frames byte for
+// byte, and no RGB frame exists.
+//
+// Nothing leaves the pool whatever the table holds.  With Se = S rounded up to even:  H = clamp(H, Se, 2^24) & ~1 and W
+// alike (even, still inside [Se, 2^24]);  (i, j) to [0, H - S] x [0, W - S];  offset to [0, pool_bytes];  then the byte
+// address of every one of the 9 samples of a pixel --
+//   Y: offset + py * W + px,   U: offset + H * W + cr * (W/2) + cc,   V: offset + H * W + (H/2) * (W/2) + cr * (W/2) + cc
+// -- to [0, pool_bytes - 1].  H * W <= 2^48 and offset <= pool_bytes: the sums stay far inside int64.
+//
+// Access.  As above: a lane owns 4 adjacent output columns of one row; its 36 source bytes (per pixel 1 Y, 4 U, 4 V) are
+// 36 byte loads, all issued unconditionally from clamped addresses, and the zero fill is selected after the decode.  The
+// only early exit is that of lanes past the end of the plane.  Stores as above.  There is no unrotated fast path: one
+// code for every angle.
+__device__ __forceinline__ int aug_tap(int p, int last) {      // the neighbour chroma index of frame coordinate p
+    const int c0 = p >> 1;
+    const int nb = (p & 1) ? c0 + 1 : c0 - 1;
+    return nb < 0 ? 0 : (nb > last ? last : nb);
+}
+
+template <bool VEC, bool F32>
+__global__ void __launch_bounds__(256) aug_gather_yuv420_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                                const long long* __restrict__ table, int S, YuvDec D,
+                                                                uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
+    const long long n = blockIdx.y;
+    const long long* t = table + 12 * n;
+    long long off = t[0], H = t[1], W = t[2], ci = t[3], cj = t[4];
+    const bool flip = t[5] != 0;
+    const uint32_t a0 = (uint32_t)t[6], a1 = (uint32_t)t[7], a2 = (uint32_t)t[8];
+    const uint32_t a3 = (uint32_t)t[9], a4 = (uint32_t)t[10], a5 = (uint32_t)t[11];
+    const long long lim = 1LL << 24, Se = (S + 1) & ~1;
+    H = (H < Se ? Se : (H > lim ? lim : H)) & ~1LL;
+    W = (W < Se ? Se : (W > lim ? lim : W)) & ~1LL;
+    ci = ci < 0 ? 0 : (ci > H - S ? H - S : ci);
+    cj = cj < 0 ? 0 : (cj > W - S ? W - S : cj);
+    off = off < 0 ? 0 : (off > pool_bytes ? pool_bytes : off);
+    const long long last = pool_bytes - 1;
+    const long long CW = W >> 1;
+    const int chl = (int)(H >> 1) - 1, cwl = (int)CW - 1;      // H, W <= 2^24: frame coordinates fit int32
+    const long long ub = off + H * W, vb = ub + (H >> 1) * CW;
+    const int gw = (S + 3) >> 2;
+    const int total = S * gw;
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= total) return;   // whole lanes past the end of the plane; nothing below branches around a load
+    const int y = e / gw;
+    const int x0 = (e - y * gw) * 4;
+    uint32_t fx = a2 + (uint32_t)y * a1 + (uint32_t)x0 * a0;
+    uint32_t fy = a5 + (uint32_t)y * a4 + (uint32_t)x0 * a3;
+    int Y[4], U[4][4], V[4][4];
+    bool ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xin = (int)fx >> 16, yin = (int)fy >> 16;
+        ok[k] = xin >= 0 && xin < S && yin >= 0 && yin < S;
+        const int xc = xin < 0 ? 0 : (xin > S - 1 ? S - 1 : xin);
+        const int yc = yin < 0 ? 0 : (yin > S - 1 ? S - 1 : yin);
+        const int py = (int)ci + yc, px = (int)cj + (flip ? S - 1 - xc : xc);
+        const long long r0 = (long long)(py >> 1) * CW, r1 = (long long)aug_tap(py, chl) * CW;
+        const long long c0 = px >> 1, c1 = aug_tap(px, cwl);
+        const long long by = off + (long long)py * W + px;
+        const long long q[4] = {r0 + c0, r0 + c1, r1 + c0, r1 + c1};
+        Y[k] = pool[by > last ? last : by];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const long long bu = ub + q[m], bv = vb + q[m];
+            U[k][m] = pool[bu > last ? last : bu];
+            V[k][m] = pool[bv > last ? last : bv];
+        }
+        fx += a0;
+        fy += a3;
+    }
+    uint32_t v[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int u = ((9 * U[k][0] + 3 * U[k][1] + 3 * U[k][2] + U[k][3] + 8) >> 4) - 128;
+        const int w = ((9 * V[k][0] + 3 * V[k][1] + 3 * V[k][2] + V[k][3] + 8) >> 4) - 128;
+        const int l = D.cy * (Y[k] - D.yo) + (1 << 13);
+        v[k][0] = ok[k] ? (uint32_t)yuv_clampv<uint8_t>((l + D.rv * w) >> 14) : 0u;
+        v[k][1] = ok[k] ? (uint32_t)yuv_clampv<uint8_t>((l + D.gu * u + D.gv * w) >> 14) : 0u;
+        v[k][2] = ok[k] ? (uint32_t)yuv_clampv<uint8_t>((l + D.bu * u) >> 14) : 0u;
+    }
+    const long long plane = (long long)S * S;
+    const long long o = n * 3 * plane + (long long)y * S + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        uint8_t* d8 = out_u8 + o + c * plane;
+        if (VEC) {
+            *reinterpret_cast<uint32_t*>(d8) = v[0][c] | v[1][c] << 8 | v[2][c] << 16 | v[3][c] << 24;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < S) d8[k] = (uint8_t)v[k][c];
+        }
+        if (F32) {
+            float f[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) f[k] = __fdiv_rn((float)v[k][c], 255.0f);
+            float* df = out_f32 + o + c * plane;
+            if (VEC) {
+                *reinterpret_cast<float4*>(df) = make_float4(f[0], f[1], f[2], f[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x0 + k < S) df[k] = f[k];
+            }
+        }
+    }
+}
+
+template <bool VEC, bool F32>
+static void aug_yuv_launch(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, const YuvDec& D,
+                           void* out_u8, void* out_f32, hipStream_t st) {
+    const dim3 grid((unsigned)cdiv(S * cdiv(S, 4), 256), (unsigned)n);
+    prof_note((double)n * (double)(S * S) * (F32 ? 18.0 : 6.0), 0.0);
+    OFASR_LAUNCH((aug_gather_yuv420_kernel<VEC, F32>), grid, dim3(256), 0, st, (const uint8_t*)pool, (long long)pool_bytes,
+                 (const long long*)table, (int)S, D, (uint8_t*)out_u8, (float*)out_f32);
+}
+
 }  // namespace ofasr
 
 using namespace ofasr;
+
+OFASR_EXPORT int ofasr_aug_gather_yuv420(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S,
+                                         const int32_t* coeffs, void* out_u8, void* out_f32, void* stream) {
+    const char* name = "ofasr_aug_gather_yuv420";
+    OFASR_REQUIRE(pool && table && coeffs && out_u8, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE(n > 0 && S > 0 && pool_bytes > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
+    OFASR_REQUIRE(S <= 4096, OFASR_ERR_UNSUPPORTED, "%s: crop side %lld above 4096 (the fixed-point walk is int32)", name,
+                  (long long)S);
+    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: %lld samples in one launch (at most 65535)", name, (long long)n);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    // the table lives on the device: the smallest pool that can hold one even-sided frame with H, W >= S is what the
+    // host can check
+    const int64_t Se = (S + 1) & ~(int64_t)1;
+    OFASR_REQUIRE(pool_bytes >= Se * Se * 3 / 2, OFASR_ERR_UNSUPPORTED,
+                  "%s: a pool of %lld bytes holds no 4:2:0 frame of at least %lldx%lld (even H, W >= S)", name,
+                  (long long)pool_bytes, (long long)Se, (long long)Se);
+    hipStream_t st = as_stream(stream);
+    const YuvDec D = yuv_dec(coeffs);
+    const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(out_u8) % 4 == 0 &&
+                     reinterpret_cast<uintptr_t>(out_f32) % 16 == 0;
+    if (out_f32) {
+        if (vec) aug_yuv_launch<true, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+        else aug_yuv_launch<false, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+    } else {
+        if (vec) aug_yuv_launch<true, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+        else aug_yuv_launch<false, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+    }
+    return check_launch(name);
+}
 
 OFASR_EXPORT int ofasr_aug_gather_u8(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S,
                                      void* out_u8, void* out_f32, void* stream) {

@@ -10,8 +10,14 @@ The rotation.  Image.rotate(angle, NEAREST, expand=False) reduces the angle modu
 with a_k = floor(m_k * 65536 + 0.5) and half a pixel folded into a2 / a5.  The transposes fit the same form with integer
 coefficients, so one gather serves every angle: the host computes six ints per sample (rotate_coeffs) and the kernel is
 the same code for all of them.
+
+Video.  The same gather runs on a pool of raw 8-bit YUV 4:2:0 frames with video.py's colour decode fused in
+(ofasr_aug_gather_yuv420, ops.aug_gather_yuv420, ResidentVideoSet): gather_yuv420_np is its definition on the pool's
+bytes and apply_params_yuv420_np the same thing said as "the transforms of the decoded whole frame"
+(tests/test_video_train.py on the host, tests/test_hip_video_train.py on the GPU).
 """
 import math
+import os
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -115,24 +121,86 @@ def apply_params_np(img, size, params):
     return rotate_nearest_np(a, angle)
 
 
-def table_row(offset, H, W, size, params):
-    """one row of ofasr_aug_gather_u8's table; refuses what the kernel would have to clamp"""
+def table_row(offset, H, W, size, params, yuv420=False):
+    """one row of the gathers' table (ofasr_aug_gather_u8; with `yuv420`, ofasr_aug_gather_yuv420, whose frames have
+    even sides); refuses what the kernel would have to clamp"""
     i, j, flip, angle = params
     if H < size or W < size:
         raise ValueError("aug_gather_u8: image %dx%d is smaller than the %dx%d crop" % (H, W, size, size))
     if not (0 <= i <= H - size and 0 <= j <= W - size):
         raise ValueError("aug_gather_u8: crop corner (%d, %d) outside the %dx%d image" % (i, j, H, W))
+    if yuv420 and (H % 2 or W % 2):
+        raise ValueError("aug_gather_yuv420: a 4:2:0 frame needs even sides, got %dx%d" % (W, H))
     return (int(offset), int(H), int(W), int(i), int(j), int(bool(flip))) + tuple(rotate_coeffs(angle, size))
 
 
-def make_table(rows, size, out=None):
-    """int64 [n, 12] host table from (offset, H, W, (i, j, flip, angle)) entries"""
-    vals = [table_row(o, H, W, size, p) for (o, H, W, p) in rows]
+def make_table(rows, size, out=None, yuv420=False):
+    """int64 [n, 12] host table from (offset, H, W, (i, j, flip, angle)) entries; `yuv420`: the entries are frames of a
+    planar YUV 4:2:0 pool (offset = the Y plane's), odd sides are refused"""
+    vals = [table_row(o, H, W, size, p, yuv420) for (o, H, W, p) in rows]
     t = torch.tensor(vals, dtype=torch.int64).reshape(len(vals), TABLE_COLS)
     if out is None:
         return t
     out[:len(vals)].copy_(t)
     return out[:len(vals)]
+
+
+# ------------------------------------------------------------------------------------- planar YUV 4:2:0 frames
+def apply_params_yuv420_np(y, u, v, size, params, matrix="bt601", full_range=False):
+    """the three transforms on the decode of one frame (video.yuv420_to_rgb_host of the WHOLE frame, so chroma replicates
+    at the frame's edge and its parity is the frame coordinate's) -> [size, size, 3]"""
+    from ... import video
+    return apply_params_np(video.yuv420_to_rgb_host(y, u, v, matrix, full_range), size, params)
+
+
+def gather_yuv420_np(pool_bytes, table, S, coeffs):
+    """ofasr_aug_gather_yuv420 restated on the pool's bytes (a 1-D uint8 array), clamping rules included: the
+    definition.  `table`: int64 [n, 12]; `coeffs`: the six decode coefficients (video.yuv_coeffs(...)[0]).  A frame is
+    Y [H, W], U [H/2, W/2], V [H/2, W/2] from its offset on.  With Se = S rounded up to even: H = clamp(H, Se, 2^24) & ~1
+    and W alike, (i, j) into [0, H - S] x [0, W - S], offset into [0, pool bytes], the six rotation coefficients taken
+    modulo 2^32 (the walk wraps in uint32), and every sample's byte address into [0, pool bytes - 1]."""
+    pool = np.asarray(pool_bytes, dtype=np.uint8).reshape(-1)
+    nb, S = int(pool.size), int(S)
+    yo, cy, rv, gu, gv, bu = (int(c) for c in coeffs)
+    y, x = np.mgrid[0:S, 0:S].astype(np.int64)
+    Se, lim, m32 = (S + 1) & ~1, 1 << 24, 0xffffffff
+    table = np.asarray(table, dtype=np.int64).reshape(-1, TABLE_COLS)
+    out = np.zeros((len(table), 3, S, S), np.uint8)
+
+    def walk(c, cy_, cx_):
+        w = ((c & m32) + y * (cy_ & m32) + x * (cx_ & m32)) & m32
+        return (w - ((w >> 31) << 32)) >> 16                      # as int32, arithmetic shift
+
+    def tap(p, last):
+        c0 = p >> 1
+        return c0, np.clip(np.where(p & 1, c0 + 1, c0 - 1), 0, last)
+
+    for n, row in enumerate(table):
+        off, H, W, i, j, flip, a0, a1, a2, a3, a4, a5 = (int(v) for v in row)
+        H, W = min(max(H, Se), lim) & ~1, min(max(W, Se), lim) & ~1
+        i, j = min(max(i, 0), H - S), min(max(j, 0), W - S)
+        off = min(max(off, 0), nb)
+        xin, yin = walk(a2, a1, a0), walk(a5, a4, a3)
+        ok = (xin >= 0) & (xin < S) & (yin >= 0) & (yin < S)
+        xc, yc = np.clip(xin, 0, S - 1), np.clip(yin, 0, S - 1)
+        py, px = i + yc, j + (S - 1 - xc if flip else xc)
+        CH, CW = H >> 1, W >> 1
+        r0, r1 = tap(py, CH - 1)
+        c0, c1 = tap(px, CW - 1)
+
+        def at(b):
+            return pool[np.minimum(b, nb - 1)].astype(np.int32)
+
+        def chroma(base):
+            return ((9 * at(base + r0 * CW + c0) + 3 * at(base + r0 * CW + c1) + 3 * at(base + r1 * CW + c0)
+                     + at(base + r1 * CW + c1) + 8) >> 4) - 128
+
+        ub = off + H * W
+        uu, vv = chroma(ub), chroma(ub + CH * CW)
+        l = cy * (at(off + py * W + px) - yo) + (1 << 13)
+        for c, val in enumerate(((l + rv * vv) >> 14, (l + gu * uu + gv * vv) >> 14, (l + bu * uu) >> 14)):
+            out[n, c] = np.where(ok, np.clip(val, 0, 255), 0)
+    return out
 
 
 # ------------------------------------------------------------------------------------- the resident training set
@@ -194,10 +262,125 @@ class ResidentTrainSet(object):
         return self.pool[off:off + h * w * 3].cpu().numpy().reshape(h, w, 3)
 
 
+# ------------------------------------------------------------------------------------- the resident video frames
+def count_frames(reader):
+    """the number of frames of an open video.Y4MReader / RawYUV420Reader positioned before its first frame, from the
+    header, the FRAME lines and the file size alone: no frame is read and the reader does not move"""
+    if hasattr(reader, "frames"):
+        return reader.frames
+    from ... import video
+    fb = video.frame_bytes(reader.width, reader.height, reader.depth)
+    size, n = os.path.getsize(reader.path), 0
+    with open(reader.path, "rb") as f:
+        f.seek(reader._f.tell())
+        while True:
+            line = f.readline(4096)
+            if not line:
+                return n
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n") or f.tell() + fb > size:
+                raise ValueError("%s: frame %d: bad or truncated frame" % (reader.path, n))
+            f.seek(fb, os.SEEK_CUR)
+            n += 1
+
+
+def video_pool_layout(sources, max_bytes):
+    """(entries, paths, total bytes, largest frame's bytes) of ResidentVideoSet's pool for `sources`, from headers, FRAME
+    lines and file sizes: no frame is read.  Refuses a 10-bit source (ValueError) and a pool above `max_bytes`
+    (MemoryError, which names the size)."""
+    from ... import video
+    entries, paths, total, largest = [], [], 0, 0
+    for path, size, idx in sources:
+        with video.open_reader(path, size) as r:
+            if r.depth != 8:
+                raise ValueError("%s is %d-bit: training input is 8-bit only, because the LR images are Pillow's 8-bit "
+                                 "bicubic of the HR crop (ops.lr_images_from_u8)" % (path, r.depth))
+            n, fb = count_frames(r), video.frame_bytes(r.width, r.height)
+            idx = [int(k) for k in idx]
+            if any(b <= a for a, b in zip(idx, idx[1:])) or (idx and not 0 <= idx[0] <= idx[-1] < n):
+                raise ValueError("%s: frame indices must be strictly increasing inside 0 .. %d" % (path, n - 1))
+            for k in idx:
+                entries.append((total, r.height, r.width))
+                paths.append("%s#%d" % (path, k))
+                total += fb
+            largest = max(largest, fb)
+    if not entries:
+        raise ValueError("ResidentVideoSet: no frames")
+    if total > max_bytes:
+        raise MemoryError("ResidentVideoSet: %d frames take %d bytes (%.2f GiB), above max_bytes = %d (%.2f GiB)"
+                          % (len(entries), total, total / 2.0 ** 30, max_bytes, max_bytes / 2.0 ** 30))
+    return entries, paths, total, largest
+
+
+class ResidentVideoSet(object):
+    """The selected frames of raw 8-bit YUV 4:2:0 videos in ONE uint8 pool on `device`, each frame's bytes as they are in
+    the file (Y [H, W], U [H/2, W/2], V [H/2, W/2]), back to back: half the bytes of an RGB pool, and no RGB frame is ever
+    formed -- `gather` decodes inside the augmentation gather (ops.aug_gather_yuv420) by video.py's pinned conversion,
+    the one the tile gather of the upscaler feeds the network.  `sources` is a list of (path, (width, height) or None,
+    frame indices, strictly increasing), opened through video.open_reader; `entries[k] = (offset of the Y plane, H, W)`
+    and `paths[k]` names frame k ("file#index"), in source order.  The pool's size is known from the headers and the file
+    sizes before any frame is read: above `max_bytes` the constructor raises, it never truncates.  Frames travel through
+    one pinned staging buffer; frames that are not selected are skipped (skip_frame), not read."""
+    yuv420 = True           # make_table: the entries are 4:2:0 frames
+
+    def __init__(self, sources, device, matrix="bt601", full_range=False, max_bytes=32 << 30):
+        from ... import video
+        video.yuv_coeffs(matrix, full_range)        # refuses an unknown matrix here, not at the first batch
+        self.matrix, self.full_range = matrix, bool(full_range)
+        self.sources = [(p, None if sz is None else (int(sz[0]), int(sz[1])), [int(k) for k in idx])
+                        for (p, sz, idx) in sources]
+        # what the files are is checked before where they would go: a 10-bit source is refused on any device
+        self.entries, self.paths, total, largest = video_pool_layout(self.sources, max_bytes)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            from ... import _C
+            raise _C.OfasrError("ResidentVideoSet keeps the frames on the GPU (got device %s)" % (self.device,))
+        self.nbytes = total
+        self.pool = torch.empty(total, dtype=torch.uint8, device=self.device)
+        stage = torch.empty(largest, dtype=torch.uint8).pin_memory()
+        at = 0
+        for path, size, idx in self.sources:
+            with video.open_reader(path, size, depth=8) as r:
+                for k in idx:
+                    while r.frames_read < k:
+                        if not r.skip_frame():
+                            raise ValueError("%s ended before frame %d" % (path, k))
+                    off, h, w = self.entries[at]
+                    fb = video.frame_bytes(w, h)
+                    if r.read_frame(out=stage.numpy()[:fb]) is None:
+                        raise ValueError("%s ended before frame %d" % (path, k))
+                    self.pool[off:off + fb].copy_(stage[:fb])      # synchronous: the staging buffer is free again
+                    at += 1
+
+    def __len__(self):
+        return len(self.entries)
+
+    def frame_planes_np(self, k):
+        """frame k back on the host as its (y, u, v) planes"""
+        from ... import video
+        off, h, w = self.entries[k]
+        return video.split_frame(self.pool[off:off + video.frame_bytes(w, h)].cpu().numpy(), w, h)
+
+    def frame_planes(self, k):
+        """frame k's (y, u, v) planes as views of the pool"""
+        from ... import video
+        off, h, w = self.entries[k]
+        return video.split_frame(self.pool[off:off + video.frame_bytes(w, h)], w, h)
+
+    def image_np(self, k):
+        """frame k as [H, W, 3] RGB by the host definition (video.yuv420_to_rgb_host)"""
+        from ... import video
+        return video.yuv420_to_rgb_host(*self.frame_planes_np(k), matrix=self.matrix, full_range=self.full_range)
+
+    def gather(self, table, n, S, want_f32=False):
+        from ... import ops
+        return ops.aug_gather_yuv420(self.pool, table, n, S, self.matrix, self.full_range, want_f32=want_f32)
+
+
 class ResidentTrainLoader(object):
     """The DataLoader of the training crops, on the GPU: per batch the N parameter sets are drawn on the host in batch
     order (draw_train_params, torch global RNG), written into one pinned table, copied to the device once, and one
-    ofasr_aug_gather_u8 launch writes the batch.  Yields {'image_u8': uint8 [N, 3, S, S]} (+ 'image', the same batch as
+    ofasr_aug_gather_u8 launch writes the batch (a set with a `gather` of its own, ResidentVideoSet, is asked instead:
+    one ofasr_aug_gather_yuv420 launch; everything else is the same).  Yields {'image_u8': uint8 [N, 3, S, S]} (+ 'image', the same batch as
     fp32 / 255, when `want_f32`); utils.device_batch makes the LR images from it.  `sampler` is any index sampler over the
     set (RankShardSampler with its set_epoch contract when sharded, a fresh permutation per epoch otherwise).
     The only host wait is on the pinned table of `ring` batches ago, before it is overwritten."""
@@ -230,13 +413,18 @@ class ResidentTrainLoader(object):
         self._turn = (slot + 1) % len(self._host)
         if self._done[slot] is not None:
             self._done[slot].synchronize()     # the upload that last read this pinned table
-        host = make_table([ds.entries[k] + (p,) for k, p in zip(indices, params)], S, out=self._host[slot])
+        gather = getattr(ds, "gather", None)       # a set that decodes in its own gather (ResidentVideoSet)
+        host = make_table([ds.entries[k] + (p,) for k, p in zip(indices, params)], S, out=self._host[slot],
+                          yuv420=getattr(ds, "yuv420", False))
         with torch.cuda.device(ds.device):
             table = host.to(ds.device, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             self._done[slot] = ev
-            out = ops.aug_gather_u8(ds.pool, table, len(indices), S, want_f32=self.want_f32)
+            if gather is not None:
+                out = gather(table, len(indices), S, want_f32=self.want_f32)
+            else:
+                out = ops.aug_gather_u8(ds.pool, table, len(indices), S, want_f32=self.want_f32)
         self.last_indices, self.last_params = list(indices), list(params)
         if self.want_f32:
             return {"image_u8": out[0], "image": out[1]}

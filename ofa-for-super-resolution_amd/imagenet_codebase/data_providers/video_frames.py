@@ -1,0 +1,192 @@
+"""Training, search and evaluation data straight from raw 8-bit YUV 4:2:0 video (Y4M, or headerless yuv420p with its
+size): the frames stay on the GPU as they are in the file and the colour decode is fused into the augmentation gather
+(augment.ResidentVideoSet, csrc/augment.hip: ofasr_aug_gather_yuv420), so the RGB the network is trained on is the RGB
+it sees when upscale_video_ofa_net_sr.py feeds it the same video -- video.py's pinned conversion -- and no PNG and no
+RGB frame exists anywhere.  The provider has Div2K_SetXXDataProvider's interface.
+
+The split.  Within each video's selected frames (`frames` = (A, B): frames A .. B-1, as --frames of the upscaler), the
+frames at positions 0, K, 2K, ... (K = `valid_every`) are the evaluation set and the rest are the training set;
+K = 0: every frame trains and the first one evaluates.  Evaluation items are whole frames, ModCrop(4), batch 1, on
+every rank, in file order.
+
+This module also holds the command-line flags of the entry scripts (add_video_args / take_video_args); nothing at
+module level needs torch.
+"""
+import argparse
+
+VIDEO_FLAGS = ("video", "video_size", "video_frames", "video_valid_every", "matrix", "range")
+
+
+# ---------------------------------------------------------------------------------------------- command line
+def parse_video_size(text):
+    try:
+        w, h = text.lower().split("x")
+        w, h = int(w), int(h)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected WxH, got %r" % text)
+    if w < 2 or h < 2 or w % 2 or h % 2:
+        raise argparse.ArgumentTypeError("a 4:2:0 frame needs even, positive sides, got %r" % text)
+    return w, h
+
+
+def parse_video_frames(text):
+    """A:B -> (A, B or None): frames A .. B-1 (the meaning of --frames of upscale_video_ofa_net_sr.py)"""
+    try:
+        a, b = text.split(":")
+        a, b = (int(a) if a else 0), (int(b) if b else None)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected A:B, got %r" % text)
+    if a < 0 or (b is not None and b <= a):
+        raise argparse.ArgumentTypeError("empty or negative frame range %r" % text)
+    return a, b
+
+
+def add_video_args(ap):
+    """the flags that select raw-video input, the same on every entry script"""
+    g = ap.add_argument_group("raw YUV 4:2:0 video input (instead of the DIV2K image folders)")
+    g.add_argument("--video", action="append", default=None, metavar="PATH",
+                   help="train / calibrate / evaluate on the frames of this 8-bit YUV 4:2:0 video (*.y4m, or headerless "
+                        "yuv420p with --video-size); repeatable")
+    g.add_argument("--video-size", type=parse_video_size, default=None, metavar="WxH", help="frame size of headerless files")
+    g.add_argument("--video-frames", type=parse_video_frames, default=None, metavar="A:B",
+                   help="frames A .. B-1 of every video only")
+    g.add_argument("--video-valid-every", type=int, default=10, metavar="K",
+                   help="every K-th selected frame of a video evaluates, the rest train (0: all train, the first evaluates)")
+    g.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
+    g.add_argument("--range", default="tv", choices=["tv", "pc"], help="tv: limited (16..235), pc: full range")
+    return ap
+
+
+def take_video_args(a):
+    """Remove the flags of add_video_args from the parsed namespace `a` and return them as VideoFramesRunConfig's keyword
+    arguments, or None without --video (the namespace is then what it was before the flags existed; a video flag
+    given without --video is an error)."""
+    vals = {k: a.__dict__.pop(k) for k in VIDEO_FLAGS}
+    if not vals["video"]:
+        if vals["video_size"] is not None or vals["video_frames"] is not None:
+            raise SystemExit("--video-size / --video-frames need --video")
+        return None
+    if vals["video_valid_every"] < 0:
+        raise SystemExit("--video-valid-every must be >= 0")
+    return dict(videos=list(vals["video"]), video_size=vals["video_size"], video_frames=vals["video_frames"],
+                video_valid_every=vals["video_valid_every"], matrix=vals["matrix"], full_range=vals["range"] == "pc")
+
+
+# ---------------------------------------------------------------------------------------------- the split
+def select_frames(n_frames, frames=None, valid_every=10):
+    """(selected, train, evaluation) frame indices of one video of `n_frames` frames: `frames` = (A, B) selects
+    A .. min(B, n_frames) - 1 (None: all), then positions 0, K, 2K, ... of the selection evaluate and the rest train;
+    K = 0: all train and the first evaluates.  Each list is increasing."""
+    a, b = (0, None) if frames is None else frames
+    K = int(valid_every)
+    if K < 0:
+        raise ValueError("valid_every must be >= 0, got %d" % K)
+    selected = list(range(int(a), n_frames if b is None else min(int(b), n_frames)))
+    if not selected:
+        raise ValueError("frames %s:%s select nothing of %d frames" % (a, "" if b is None else b, n_frames))
+    if K == 0:
+        return selected, list(selected), selected[:1]
+    return selected, [f for p, f in enumerate(selected) if p % K], selected[::K]
+
+
+class _EvalFrames(object):
+    """a re-iterable, len()-able loader of whole frames of a ResidentVideoSet: batch-1 dicts {'image_u8': uint8
+    [1, 3, H', W']} on the GPU, H', W' = ModCrop(4) of the frame, decoded by ops.yuv420_to_rgb_u8 when iterated (the
+    decoded frames are not kept)"""
+
+    def __init__(self, dataset, indices):
+        self.dataset, self.indices = dataset, list(indices)
+
+    def __len__(self):
+        return len(self.indices)
+
+    def __iter__(self):
+        import torch
+        from ... import ops
+        ds = self.dataset
+        for k in self.indices:
+            _, h, w = ds.entries[k]
+            with torch.cuda.device(ds.device):
+                rgb = ops.yuv420_to_rgb_u8(*ds.frame_planes(k), matrix=ds.matrix, full_range=ds.full_range)
+                yield {"image_u8": rgb[:h - h % 4, :w - w % 4].permute(2, 0, 1).contiguous().unsqueeze(0)}
+
+
+class VideoFramesDataProvider(object):
+    """`train` / `valid` / `test`, `data_shape`, `assign_active_img_size`, `build_sub_train_loader` of
+    Div2K_SetXXDataProvider over the frames of `videos` (paths; `video_size` = (width, height) for headerless files).
+    `train` is an augment.ResidentTrainLoader over one augment.ResidentVideoSet holding every selected frame (training
+    and evaluation frames alike); `valid` is `test`."""
+    SUB_SEED = 937162211     # DataProvider.SUB_SEED of div2k_setxx.py
+
+    def __init__(self, videos, video_size=None, frames=None, valid_every=10, matrix="bt601", full_range=False,
+                 train_batch_size=16, test_batch_size=1, image_size=32, num_replicas=None, rank=None,
+                 resident_max_bytes=32 << 30):
+        import torch
+        from ... import video
+        from .augment import ResidentTrainLoader, ResidentVideoSet, count_frames
+        from .div2k_setxx import RankShardSampler
+        self.videos = [videos] if isinstance(videos, str) else list(videos)
+        if not self.videos:
+            raise ValueError("VideoFramesDataProvider: no videos")
+        sizes = sorted(image_size) if isinstance(image_size, (list, tuple)) else [image_size]
+        self.image_size = image_size if isinstance(image_size, int) else sizes
+        self.active_img_size = sizes[-1]
+        self.test_batch_size = test_batch_size       # evaluation items are whole frames, batch 1, whatever this says
+        sources, self.train_indices, self.eval_indices, at = [], [], [], 0
+        for path in self.videos:
+            with video.open_reader(path, video_size) as r:     # header only; a 10-bit file is refused by the set below
+                n = count_frames(r)
+            selected, train, evaluation = select_frames(n, frames, valid_every)
+            where = {f: at + p for p, f in enumerate(selected)}
+            self.train_indices += [where[f] for f in train]
+            self.eval_indices += [where[f] for f in evaluation]
+            sources.append((path, video_size, selected))
+            at += len(selected)
+        if not self.train_indices:
+            raise ValueError("VideoFramesDataProvider: valid_every=%d leaves no training frame among the %d selected"
+                             % (valid_every, at))
+        self.resident_set = ResidentVideoSet(sources, torch.device("cuda", torch.cuda.current_device()), matrix,
+                                             full_range, max_bytes=resident_max_bytes)
+        self._shard = (num_replicas, rank) if num_replicas is not None and num_replicas > 1 else None
+        if self._shard:
+            sampler = RankShardSampler(self.train_indices, num_replicas, rank)
+        else:
+            sampler = torch.utils.data.SubsetRandomSampler(self.train_indices)
+        self.train = ResidentTrainLoader(self.resident_set, train_batch_size, sampler, self.active_img_size,
+                                         drop_last=True, want_f32=True)
+        self.test = _EvalFrames(self.resident_set, self.eval_indices)
+        self.valid = self.test
+
+    @staticmethod
+    def name():
+        return "video_frames"
+
+    @property
+    def data_shape(self):
+        return 3, self.active_img_size, self.active_img_size
+
+    @property
+    def n_classes(self):
+        return 1
+
+    def assign_active_img_size(self, new_img_size):
+        """evaluation is ModCrop(4) of the whole frame at every size, as in the image provider"""
+        self.active_img_size = new_img_size
+
+    def build_sub_train_loader(self, n_images, batch_size, num_worker=None, num_replicas=None, rank=None):
+        """`n_images` fixed training frames (seed SUB_SEED) as a cached list of batches, for BN re-calibration"""
+        import torch
+        from .augment import ResidentTrainLoader
+        from .div2k_setxx import RankShardSampler
+        cache = self.__dict__.setdefault("_sub_train_cache", {})
+        key = (self.active_img_size, n_images, batch_size)
+        if key not in cache:
+            perm = torch.randperm(len(self.train_indices), generator=torch.Generator().manual_seed(self.SUB_SEED))
+            chosen = [self.train_indices[p] for p in perm[:n_images].tolist()]
+            if num_replicas is not None and num_replicas > 1:
+                sampler = RankShardSampler(chosen, num_replicas, rank)
+            else:
+                sampler = torch.utils.data.SubsetRandomSampler(chosen)
+            cache[key] = list(ResidentTrainLoader(self.resident_set, batch_size, sampler, self.active_img_size,
+                                                  drop_last=False))
+        return cache[key]

@@ -1,7 +1,8 @@
 """Per-dataset run configs (mirror of reference ofa/imagenet_codebase/run_manager/__init__.py:127-232).
 `Div2K_SetXXRunConfig(**args.__dict__)` keeps working; its lazy `data_provider` resolves to the real
 DIV2K provider when the dataset directory exists.  A missing directory is an ERROR unless synthetic data was asked
-for explicitly (`allow_synthetic=True` or OFASR_ALLOW_SYNTHETIC_DATA=1): a mistyped path must not train on noise."""
+for explicitly (`allow_synthetic=True` or OFASR_ALLOW_SYNTHETIC_DATA=1): a mistyped path must not train on noise.
+`VideoFramesRunConfig` takes the images from the frames of raw YUV 4:2:0 video instead (data_providers/video_frames.py)."""
 import os
 
 from .sr_run_manager import RunConfig, SRRunManager  # noqa: F401
@@ -85,4 +86,44 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                     "DIV2K/SetXX dataset not found: %s must hold train/ and val/ (set OFASR_DIV2K_ROOT).  Pass "
                     "allow_synthetic=True / --synthetic or set OFASR_ALLOW_SYNTHETIC_DATA=1 to run on synthetic "
                     "images instead." % root)
+        return self.__dict__["_data_provider"]
+
+
+class VideoFramesRunConfig(SyntheticSRRunConfig):
+    """Div2K_SetXXRunConfig's counterpart for raw 8-bit YUV 4:2:0 video: `data_provider` is a VideoFramesDataProvider
+    (data_providers/video_frames.py) over `videos`, the frames resident on the GPU and decoded inside the augmentation
+    gather.  `dataset` records "video_frames" and the paths, so run.config and every checkpoint say what they were
+    trained on.  There is no synthetic stand-in: a missing file is an error."""
+
+    def __init__(self, videos, video_size=None, video_frames=None, video_valid_every=10, matrix="bt601", full_range=False,
+                 n_epochs=150, init_lr=0.05, lr_schedule_type="cosine", lr_schedule_param=None, dataset=None,
+                 train_batch_size=256, test_batch_size=1, valid_size=None, opt_type="sgd", opt_param=None,
+                 weight_decay=4e-5, label_smoothing=0.1, no_decay_keys=None, mixup_alpha=None, model_init="he_fout",
+                 validation_frequency=1, print_frequency=10, n_worker=0, image_size=32, resident_max_bytes=32 << 30,
+                 **kwargs):
+        videos = [videos] if isinstance(videos, str) else list(videos)
+        super().__init__(n_epochs, init_lr, lr_schedule_type, lr_schedule_param,
+                         "video_frames: " + ", ".join(videos), train_batch_size, test_batch_size, valid_size, opt_type,
+                         opt_param, weight_decay, label_smoothing, no_decay_keys, mixup_alpha, model_init,
+                         validation_frequency, print_frequency, n_worker=n_worker, image_size=image_size)
+        self.videos = videos
+        self.video_size = None if video_size is None else tuple(video_size)
+        self.video_frames = None if video_frames is None else tuple(video_frames)
+        self.video_valid_every = int(video_valid_every)
+        self.matrix, self.full_range = matrix, bool(full_range)
+        self.resident = True
+        self.resident_max_bytes = int(resident_max_bytes)
+
+    @property
+    def data_provider(self):
+        if self.__dict__.get("_data_provider", None) is None:
+            from ... import distributed as dd
+            from ..data_providers.video_frames import VideoFramesDataProvider
+            ws = dd.world_size()
+            self.__dict__["_data_provider"] = VideoFramesDataProvider(
+                self.videos, video_size=self.video_size, frames=self.video_frames, valid_every=self.video_valid_every,
+                matrix=self.matrix, full_range=self.full_range, train_batch_size=self.train_batch_size,
+                test_batch_size=self.test_batch_size, image_size=self.image_size,
+                num_replicas=ws if ws > 1 else None, rank=dd.rank() if ws > 1 else None,
+                resident_max_bytes=self.resident_max_bytes)
         return self.__dict__["_data_provider"]

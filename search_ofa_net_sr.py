@@ -48,7 +48,10 @@ def parse_args(argv=None):
                     help="what a candidate is scored by: psnr = the host Y-PSNR (the default), psnr-gpu / ssim = Y-PSNR / "
                          "Y-SSIM by the HIP metric kernel (search.quality_fitness)")
     ap.add_argument("--shave", type=int, default=0, help="border pixels the GPU metric leaves out")
+    vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
+    vf.add_video_args(ap)
     a = ap.parse_args(argv)
+    a.video_kw = vf.take_video_args(a)      # --video: calibrate and validate on the frames of raw YUV 4:2:0 video
     if a.test_sizes:
         a.test_sizes = [tuple(int(v) for v in s.split("x")) for s in a.test_sizes.split(",")]
     return a
@@ -67,10 +70,13 @@ def main(argv=None):
     kw = dict(ks_list=[3, 5, 7], expand_ratio_list=[3, 4, 6], depth_list=[2, 3, 4], pixelshuffle_depth_list=[1, 2])
     net = nets.OFAMobileNetS4(**kw) if a.net == "s4" else nets.OFAMobileNetX4(**kw)
     n_batches = max(1, (a.calib_images + a.calib_batch - 1) // a.calib_batch)
-    cfg = rm.Div2K_SetXXRunConfig(n_epochs=1, init_lr=1e-3, opt_type="adam", no_decay_keys="bn#bias",
-                                  label_smoothing=0.0, train_batch_size=a.calib_batch, test_batch_size=1,
-                                  image_size=a.image_size, test_sizes=a.test_sizes or TEST_SIZES,
-                                  n_train_batches=n_batches, allow_synthetic=True if a.synthetic else None)
+    kw = dict(n_epochs=1, init_lr=1e-3, opt_type="adam", no_decay_keys="bn#bias", label_smoothing=0.0,
+              train_batch_size=a.calib_batch, test_batch_size=1, image_size=a.image_size)
+    if a.video_kw:
+        cfg = rm.VideoFramesRunConfig(**dict(kw, **a.video_kw))
+    else:
+        cfg = rm.Div2K_SetXXRunConfig(test_sizes=a.test_sizes or TEST_SIZES, n_train_batches=n_batches,
+                                      allow_synthetic=True if a.synthetic else None, **kw)
     mgr = rm.SRRunManager(a.path, net, cfg, init=a.checkpoint is None, mix_prec="f32", num_gpus=1)
     if a.checkpoint:
         net.load_weights_from_net(torch.load(a.checkpoint, map_location="cpu", weights_only=True)["state_dict"])

@@ -6,9 +6,14 @@
    of utils.device_batch, GPU time included) and the DataLoader path of the same provider with n_worker=16 (batch on the
    device, LR images included), both on a directory of synthetic PNGs the tool writes itself (32 files of 2040x1356
    under 256 names).
+ * the YUV leg (--yuv-frames F, default 64: a 199 MB pool against 398 MB of RGB; --only-yuv runs nothing else): ops.aug_gather_yuv420 at N=16, S=256 on F
+   resident 1920x1080 YUV 4:2:0 frames against ops.aug_gather_u8 on the same crops from an RGB pool of the same frames
+   made with ops.yuv420_to_rgb_u8 (equal bytes out, checked): both kernel times and their ratio.  The fused gather
+   issues 9 byte loads per pixel against 3.
 Prints one JSON line.
 usage: python tools/bench_augment.py [--files 32] [--entries 256] [--height 1356] [--width 2040] [--batches 200]
-                                     [--warmup 10] [--host-batches 200] [--workers 16] [--skip-host]"""
+                                     [--warmup 10] [--host-batches 200] [--workers 16] [--skip-host]
+                                     [--yuv-frames 64] [--only-yuv]"""
 import argparse
 import importlib
 import json
@@ -61,6 +66,61 @@ def loader_rate(loader, batches, warmup, step, sync):
     return images / (time.perf_counter() - t0)
 
 
+def kernel_us(C, L, fn, tables, name):
+    """mean time of the launches of kernel `name` over fn(table) for every table (library per-launch events)"""
+    import torch
+    fn(tables[0])
+    torch.cuda.synchronize()
+    L.ofasr_profile_enable(1)
+    C.profile_read()
+    for t in tables:
+        fn(t)
+    prof = C.profile_read()
+    L.ofasr_profile_enable(0)
+    return sum(v["total_us"] for k, v in prof.items() if name in k) / len(tables)
+
+
+def yuv_leg(C, L, ops, aug, dev, N, S, frames, reps, H=1080, W=1920):
+    """the fused gather on resident YUV 4:2:0 frames against aug_gather_u8 on the decoded frames, same crops"""
+    import numpy as np
+    import torch
+    rng = np.random.RandomState(1)
+    yy, xx = np.mgrid[0:H, 0:W]
+    fb = H * W * 3 // 2
+    pool = torch.empty(frames * fb, dtype=torch.uint8, device=dev)
+    rgb_pool = torch.empty(frames * H * W * 3, dtype=torch.uint8, device=dev)
+    ybase = 126 + 100 * np.sin(yy / 41.0) * np.cos(xx / 59.0)
+    cbase = [128 + 90 * np.sin(yy[::2, ::2] / (67.0 + 9 * j)) * np.cos(xx[::2, ::2] / 83.0) for j in range(2)]
+    for k in range(frames):      # smooth luma and chroma fields, shifted per frame, with mild noise, in the legal ranges
+        y = np.clip(np.roll(ybase, 61 * k, axis=1) + rng.randint(-5, 6, (H, W)), 16, 235)
+        c = [np.clip(np.roll(cb, 29 * k, axis=1) + rng.randint(-3, 4, (H // 2, W // 2)), 16, 240) for cb in cbase]
+        host = np.concatenate([p.astype(np.uint8).reshape(-1) for p in (y, c[0], c[1])])
+        pool[k * fb:(k + 1) * fb].copy_(torch.from_numpy(host))
+        f = pool[k * fb:(k + 1) * fb]
+        planes = (f[:H * W].view(H, W), f[H * W:H * W * 5 // 4].view(H // 2, W // 2), f[H * W * 5 // 4:].view(H // 2, W // 2))
+        rgb_pool[k * H * W * 3:(k + 1) * H * W * 3].copy_(ops.yuv420_to_rgb_u8(*planes).reshape(-1))
+    torch.manual_seed(0)
+    ty, tr = [], []
+    for r in range(reps):
+        idx = torch.randint(0, frames, (N,)).tolist()
+        params = [aug.draw_train_params(H, W, S) for _ in idx]
+        ty.append(aug.make_table([(k * fb, H, W, p) for k, p in zip(idx, params)], S, yuv420=True).to(dev))
+        tr.append(aug.make_table([(k * H * W * 3, H, W, p) for k, p in zip(idx, params)], S).to(dev))
+    res = {"frames": frames, "frame_hw": [H, W], "yuv_pool_bytes": pool.numel(), "rgb_pool_bytes": rgb_pool.numel(),
+           "launches": reps}
+    for want_f32 in (False, True):
+        a = ops.aug_gather_yuv420(pool, ty[0], N, S, want_f32=want_f32)
+        b = ops.aug_gather_u8(rgb_pool, tr[0], N, S, want_f32=want_f32)
+        same = torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) if want_f32 else torch.equal(a, b)
+        if not same:
+            raise SystemExit("aug_gather_yuv420 and aug_gather_u8 of the decoded frames differ")
+        us_y = kernel_us(C, L, lambda t: ops.aug_gather_yuv420(pool, t, N, S, want_f32=want_f32), ty,
+                         "aug_gather_yuv420_kernel")
+        us_r = kernel_us(C, L, lambda t: ops.aug_gather_u8(rgb_pool, t, N, S, want_f32=want_f32), tr, "aug_gather_u8_kernel")
+        res["f32" if want_f32 else "u8"] = {"yuv420_kernel_us": us_y, "rgb_kernel_us": us_r, "ratio": us_y / us_r}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=32)
@@ -73,6 +133,8 @@ def main():
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--yuv-frames", type=int, default=64, help="1920x1080 frames of the YUV leg (0: skip it)")
+    ap.add_argument("--only-yuv", action="store_true", help="run the YUV leg alone")
     a = ap.parse_args()
     import torch
     C = importlib.import_module(PKG + "._C")
@@ -86,6 +148,11 @@ def main():
     N, S = 16, 256
     out = {"N": N, "S": S, "copy_TBps": COPY_TBPS, "files": a.files, "entries": max(a.entries, a.files),
            "file_hw": [a.height, a.width]}
+    if a.yuv_frames > 0:
+        out["yuv420"] = yuv_leg(C, L, ops, aug, dev, N, S, a.yuv_frames, a.reps)
+    if a.only_yuv:
+        print(json.dumps(out), flush=True)
+        return
     root = tempfile.mkdtemp(prefix="bench_augment_")
     try:
         t0 = time.perf_counter()

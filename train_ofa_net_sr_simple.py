@@ -8,7 +8,8 @@ the same `args` attribute names, reference :21-132), one process per GPU:
 
 Differences from the reference script: hyper-parameters that it edits in source are flags here
 (--net s4|x4, --teacher-path, --path, --mix-prec); with --synthetic the synthetic provider stands in for a missing
-DIV2K directory (otherwise a missing dataset is an error); multi-GPU is RCCL data parallelism (one flat all-reduce per step)."""
+DIV2K directory (otherwise a missing dataset is an error); --video PATH trains on the frames of raw 8-bit YUV 4:2:0
+video instead (data_providers/video_frames.py); multi-GPU is RCCL data parallelism (one flat all-reduce per step)."""
 import argparse
 import importlib
 import os
@@ -35,7 +36,10 @@ def main():
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic images when DIV2K is absent")
     ap.add_argument("--resident", action="store_true",
                     help="keep the decoded training images on the GPU and augment them there")
+    vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
+    vf.add_video_args(ap)
     args = ap.parse_args()
+    video_kw = vf.take_video_args(args)     # None without --video: `args` is then what it always was
 
     import numpy as np
     import torch
@@ -104,7 +108,10 @@ def main():
     ps = importlib.import_module(PKG + ".elastic_nn.training.progressive_shrinking")
 
     args.allow_synthetic = True if args.synthetic else None
-    run_config = rm.Div2K_SetXXRunConfig(**args.__dict__)
+    if video_kw:
+        run_config = rm.VideoFramesRunConfig(**dict(args.__dict__, **video_kw))
+    else:
+        run_config = rm.Div2K_SetXXRunConfig(**args.__dict__)
     dop.DynamicSeparableConv2d.KERNEL_TRANSFORM_MODE = args.dy_conv_scaling_mode
     to_list = lambda s, f: [f(x) for x in s.split(",")]
     args.ks_list = to_list(args.ks_list, int)

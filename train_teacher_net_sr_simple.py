@@ -27,7 +27,10 @@ def main():
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic images when DIV2K is absent")
     ap.add_argument("--resident", action="store_true",
                     help="keep the decoded training images on the GPU and augment them there")
+    vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
+    vf.add_video_args(ap)
     a = ap.parse_args()
+    video_kw = vf.take_video_args(a)
 
     import numpy as np
     import torch
@@ -42,10 +45,12 @@ def main():
     rm = importlib.import_module(PKG + ".imagenet_codebase.run_manager")
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
     args = argparse.Namespace(teacher_model=None, kd_ratio=0, kd_type="ce")
-    cfg = rm.Div2K_SetXXRunConfig(n_epochs=a.n_epochs, init_lr=1e-3, opt_type="adam", weight_decay=3e-5,
-                                  no_decay_keys="bn#bias", label_smoothing=0.0, train_batch_size=a.batch,
-                                  test_batch_size=1, image_size=a.image_size, n_worker=8,
-                                  allow_synthetic=True if a.synthetic else None, resident=a.resident)
+    kw = dict(n_epochs=a.n_epochs, init_lr=1e-3, opt_type="adam", weight_decay=3e-5, no_decay_keys="bn#bias",
+              label_smoothing=0.0, train_batch_size=a.batch, test_batch_size=1, image_size=a.image_size, n_worker=8)
+    if video_kw:      # --video: the frames of raw YUV 4:2:0 video, resident on the GPU
+        cfg = rm.VideoFramesRunConfig(**dict(kw, **video_kw))
+    else:
+        cfg = rm.Div2K_SetXXRunConfig(allow_synthetic=True if a.synthetic else None, resident=a.resident, **kw)
     net = nets.OFAMobileNetS4(ks_list=[a.ks], expand_ratio_list=[a.expand], depth_list=[a.depth],
                               pixelshuffle_depth_list=[a.pixelshuffle_depth])
     mgr = rm.SRRunManager(a.path, net, cfg, mix_prec=a.mix_prec, num_gpus=int(os.environ.get("WORLD_SIZE", "1")),
