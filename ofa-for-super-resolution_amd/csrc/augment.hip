@@ -17,8 +17,9 @@
 // (1 + sqrt 2) + 0.71) < 3.25e8.  The sum stays below 7.1e8 < 2^31; the same holds for the second row.  The kernel adds
 // in uint32 all the same, so a table of garbage wraps instead of being undefined, and what it yields is clamped.
 //
-// Nothing leaves the pool whatever the table holds: H and W are clamped to [S, 2^24], (i, j) to [0, H - S] x [0, W - S],
-// offset to [0, pool_bytes], and the byte address of every pixel to [0, pool_bytes - 3].  Addresses are 64-bit.
+// Nothing leaves the pool whatever the table holds (aug_row below states it once for both kernels): H and W are clamped
+// to [S, 2^24], (i, j) to [0, H - S] x [0, W - S], offset to [0, pool_bytes], and the byte address of every pixel to
+// [0, pool_bytes - 3].  Addresses are 64-bit.
 //
 // Access.  A lane owns 4 adjacent output columns of one row.  Its 12 source bytes are 12 byte loads: after a rotation
 // neighbouring output pixels are not neighbours in the source, and a pixel's 3 bytes have no alignment.  Every load is
@@ -27,55 +28,65 @@
 // plane, before any address is formed).  Stores: one dword per plane for the uint8 batch and one 16-byte vector per
 // plane for the fp32 batch when S % 4 == 0 and the outputs are aligned for them; element stores otherwise (S = 30: rows
 // are not dword-aligned).
-#include "ofasr_common.h"
 #include "yuv_block.h"
 
 namespace ofasr {
 
-// grid: (x: lanes over S * ceil(S / 4) groups, y: sample)
-template <bool VEC, bool F32>
-__global__ void __launch_bounds__(256) aug_gather_u8_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
-                                                            const long long* __restrict__ table, int S,
-                                                            uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
-    const long long n = blockIdx.y;
+// row n of the table, clamped as stated above; `yuv`: the frame's sides are even, Se = S rounded up to even in H's and W's
+// lower bound (the header of ofasr_aug_gather_yuv420 below)
+struct AugRow {
+    long long off, H, W, ci, cj;
+    bool flip;
+    uint32_t a0, a1, a2, a3, a4, a5;
+};
+__device__ __forceinline__ AugRow aug_row(const long long* __restrict__ table, long long n, int S, long long pool_bytes, bool yuv) {
     const long long* t = table + 12 * n;
-    long long off = t[0], H = t[1], W = t[2], ci = t[3], cj = t[4];
-    const bool flip = t[5] != 0;
-    const uint32_t a0 = (uint32_t)t[6], a1 = (uint32_t)t[7], a2 = (uint32_t)t[8];
-    const uint32_t a3 = (uint32_t)t[9], a4 = (uint32_t)t[10], a5 = (uint32_t)t[11];
-    const long long lim = 1LL << 24;
-    H = H < S ? S : (H > lim ? lim : H);
-    W = W < S ? S : (W > lim ? lim : W);
-    ci = ci < 0 ? 0 : (ci > H - S ? H - S : ci);
-    cj = cj < 0 ? 0 : (cj > W - S ? W - S : cj);
-    off = off < 0 ? 0 : (off > pool_bytes ? pool_bytes : off);
-    const long long last = pool_bytes - 3;
+    AugRow r;
+    r.flip = t[5] != 0;
+    r.a0 = (uint32_t)t[6], r.a1 = (uint32_t)t[7], r.a2 = (uint32_t)t[8];
+    r.a3 = (uint32_t)t[9], r.a4 = (uint32_t)t[10], r.a5 = (uint32_t)t[11];
+    const long long lim = 1LL << 24, Se = yuv ? (S + 1) & ~1 : S;
+    r.H = clampll(t[1], Se, lim);
+    r.W = clampll(t[2], Se, lim);
+    if (yuv) r.H &= ~1LL, r.W &= ~1LL;
+    r.ci = clampll(t[3], 0, r.H - S);
+    r.cj = clampll(t[4], 0, r.W - S);
+    r.off = clampll(t[0], 0, pool_bytes);
+    return r;
+}
+
+// the lane's group of 4 output columns (y, x0 .. x0 + 3) and the fixed-point walk at its first column; false for whole
+// lanes past the end of the plane, which leave before any address is formed
+struct AugWalk { int y, x0; uint32_t fx, fy; };
+__device__ __forceinline__ bool aug_walk_start(const AugRow& r, int S, AugWalk& w) {
     const int gw = (S + 3) >> 2;
     const int total = S * gw;
     const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (e >= total) return;   // whole lanes past the end of the plane; nothing below branches around a load
-    const int y = e / gw;
-    const int x0 = (e - y * gw) * 4;
-    uint32_t fx = a2 + (uint32_t)y * a1 + (uint32_t)x0 * a0;
-    uint32_t fy = a5 + (uint32_t)y * a4 + (uint32_t)x0 * a3;
-    uint32_t v[4][3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int xin = (int)fx >> 16, yin = (int)fy >> 16;
-        const bool ok = xin >= 0 && xin < S && yin >= 0 && yin < S;
-        const int xc = xin < 0 ? 0 : (xin > S - 1 ? S - 1 : xin);
-        const int yc = yin < 0 ? 0 : (yin > S - 1 ? S - 1 : yin);
-        const int col = flip ? S - 1 - xc : xc;
-        long long b = off + ((ci + yc) * W + cj + col) * 3;
-        b = b > last ? last : b;
-        const uint8_t* p = pool + b;
-        const uint32_t r0 = p[0], r1 = p[1], r2 = p[2];
-        v[k][0] = ok ? r0 : 0u;
-        v[k][1] = ok ? r1 : 0u;
-        v[k][2] = ok ? r2 : 0u;
-        fx += a0;
-        fy += a3;
-    }
+    if (e >= total) return false;
+    w.y = e / gw;
+    w.x0 = (e - w.y * gw) * 4;
+    w.fx = r.a2 + (uint32_t)w.y * r.a1 + (uint32_t)w.x0 * r.a0;
+    w.fy = r.a5 + (uint32_t)w.y * r.a4 + (uint32_t)w.x0 * r.a3;
+    return true;
+}
+// one column of the walk: the source row yc and column col inside the crop (clamped into it, the flip applied) and
+// whether the pixel is inside at all; then one step to the right
+__device__ __forceinline__ bool aug_walk_step(const AugRow& r, int S, AugWalk& w, int& yc, int& col) {
+    const int xin = (int)w.fx >> 16, yin = (int)w.fy >> 16;
+    const bool ok = xin >= 0 && xin < S && yin >= 0 && yin < S;
+    const int xc = xin < 0 ? 0 : (xin > S - 1 ? S - 1 : xin);
+    yc = yin < 0 ? 0 : (yin > S - 1 ? S - 1 : yin);
+    col = r.flip ? S - 1 - xc : xc;
+    w.fx += r.a0;
+    w.fy += r.a3;
+    return ok;
+}
+
+// the store tail: v[k][c] of the group's 4 columns into the uint8 batch and, with F32, v / 255 into the fp32 batch; VEC:
+// one dword / one float4 per plane, element stores otherwise
+template <bool VEC, bool F32>
+__device__ __forceinline__ void aug_store4(const uint32_t (&v)[4][3], long long n, int S, int y, int x0,
+                                           uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
     const long long plane = (long long)S * S;
     const long long o = n * 3 * plane + (long long)y * S + x0;
 #pragma unroll
@@ -104,13 +115,30 @@ __global__ void __launch_bounds__(256) aug_gather_u8_kernel(const uint8_t* __res
     }
 }
 
+// grid: (x: lanes over S * ceil(S / 4) groups, y: sample)
 template <bool VEC, bool F32>
-static void aug_launch(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, void* out_u8,
-                       void* out_f32, hipStream_t st) {
-    const dim3 grid((unsigned)cdiv(S * cdiv(S, 4), 256), (unsigned)n);
-    prof_note((double)n * (double)(S * S) * 3.0 * (F32 ? 6.0 : 2.0), 0.0);
-    OFASR_LAUNCH((aug_gather_u8_kernel<VEC, F32>), grid, dim3(256), 0, st, (const uint8_t*)pool, (long long)pool_bytes,
-                 (const long long*)table, (int)S, (uint8_t*)out_u8, (float*)out_f32);
+__global__ void __launch_bounds__(256) aug_gather_u8_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                            const long long* __restrict__ table, int S,
+                                                            uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
+    const long long n = blockIdx.y;
+    const AugRow R = aug_row(table, n, S, pool_bytes, false);
+    const long long last = pool_bytes - 3;
+    AugWalk wk;
+    if (!aug_walk_start(R, S, wk)) return;   // nothing below branches around a load
+    uint32_t v[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int yc, col;
+        const bool ok = aug_walk_step(R, S, wk, yc, col);
+        long long b = R.off + ((R.ci + yc) * R.W + R.cj + col) * 3;
+        b = b > last ? last : b;
+        const uint8_t* p = pool + b;
+        const uint32_t r0 = p[0], r1 = p[1], r2 = p[2];
+        v[k][0] = ok ? r0 : 0u;
+        v[k][1] = ok ? r1 : 0u;
+        v[k][2] = ok ? r2 : 0u;
+    }
+    aug_store4<VEC, F32>(v, n, S, wk.y, wk.x0, out_u8, out_f32);
 }
 
 // ---- the same gather from a pool of planar YUV 4:2:0 frames (ofasr_aug_gather_yuv420) --------------------------------
@@ -144,42 +172,24 @@ __global__ void __launch_bounds__(256) aug_gather_yuv420_kernel(const uint8_t* _
                                                                 const long long* __restrict__ table, int S, YuvDec D,
                                                                 uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
     const long long n = blockIdx.y;
-    const long long* t = table + 12 * n;
-    long long off = t[0], H = t[1], W = t[2], ci = t[3], cj = t[4];
-    const bool flip = t[5] != 0;
-    const uint32_t a0 = (uint32_t)t[6], a1 = (uint32_t)t[7], a2 = (uint32_t)t[8];
-    const uint32_t a3 = (uint32_t)t[9], a4 = (uint32_t)t[10], a5 = (uint32_t)t[11];
-    const long long lim = 1LL << 24, Se = (S + 1) & ~1;
-    H = (H < Se ? Se : (H > lim ? lim : H)) & ~1LL;
-    W = (W < Se ? Se : (W > lim ? lim : W)) & ~1LL;
-    ci = ci < 0 ? 0 : (ci > H - S ? H - S : ci);
-    cj = cj < 0 ? 0 : (cj > W - S ? W - S : cj);
-    off = off < 0 ? 0 : (off > pool_bytes ? pool_bytes : off);
+    const AugRow R = aug_row(table, n, S, pool_bytes, true);
     const long long last = pool_bytes - 1;
-    const long long CW = W >> 1;
-    const int chl = (int)(H >> 1) - 1, cwl = (int)CW - 1;      // H, W <= 2^24: frame coordinates fit int32
-    const long long ub = off + H * W, vb = ub + (H >> 1) * CW;
-    const int gw = (S + 3) >> 2;
-    const int total = S * gw;
-    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (e >= total) return;   // whole lanes past the end of the plane; nothing below branches around a load
-    const int y = e / gw;
-    const int x0 = (e - y * gw) * 4;
-    uint32_t fx = a2 + (uint32_t)y * a1 + (uint32_t)x0 * a0;
-    uint32_t fy = a5 + (uint32_t)y * a4 + (uint32_t)x0 * a3;
+    const long long CW = R.W >> 1;
+    const int chl = (int)(R.H >> 1) - 1, cwl = (int)CW - 1;    // H, W <= 2^24: frame coordinates fit int32
+    const long long ub = R.off + R.H * R.W, vb = ub + (R.H >> 1) * CW;
+    AugWalk wk;
+    if (!aug_walk_start(R, S, wk)) return;   // nothing below branches around a load
     int Y[4], U[4][4], V[4][4];
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int xin = (int)fx >> 16, yin = (int)fy >> 16;
-        ok[k] = xin >= 0 && xin < S && yin >= 0 && yin < S;
-        const int xc = xin < 0 ? 0 : (xin > S - 1 ? S - 1 : xin);
-        const int yc = yin < 0 ? 0 : (yin > S - 1 ? S - 1 : yin);
-        const int py = (int)ci + yc, px = (int)cj + (flip ? S - 1 - xc : xc);
+        int yc, col;
+        ok[k] = aug_walk_step(R, S, wk, yc, col);
+        const int py = (int)R.ci + yc, px = (int)R.cj + col;
         const long long r0 = (long long)(py >> 1) * CW, r1 = (long long)aug_tap(py, chl) * CW;
         const long long c0 = px >> 1, c1 = aug_tap(px, cwl);
-        const long long by = off + (long long)py * W + px;
-        const long long q[4] = {r0 + c0, r0 + c1, r1 + c0, r1 + c1};
+        const long long by = R.off + (long long)py * R.W + px;
+        const long long q[4] = {r0 + c0, r0 + c1, r1 + c0, r1 + c1};   // the taps in yuv_decode_px's 9-3-3-1 order
         Y[k] = pool[by > last ? last : by];
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -187,68 +197,62 @@ __global__ void __launch_bounds__(256) aug_gather_yuv420_kernel(const uint8_t* _
             U[k][m] = pool[bu > last ? last : bu];
             V[k][m] = pool[bv > last ? last : bv];
         }
-        fx += a0;
-        fy += a3;
     }
+    __builtin_amdgcn_sched_barrier(0);   // the 36 loads stay in front of the decode: none is moved behind a wait
     uint32_t v[4][3];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int u = ((9 * U[k][0] + 3 * U[k][1] + 3 * U[k][2] + U[k][3] + 8) >> 4) - 128;
-        const int w = ((9 * V[k][0] + 3 * V[k][1] + 3 * V[k][2] + V[k][3] + 8) >> 4) - 128;
-        const int l = D.cy * (Y[k] - D.yo) + (1 << 13);
-        v[k][0] = ok[k] ? (uint32_t)yuv_clampv<uint8_t>((l + D.rv * w) >> 14) : 0u;
-        v[k][1] = ok[k] ? (uint32_t)yuv_clampv<uint8_t>((l + D.gu * u + D.gv * w) >> 14) : 0u;
-        v[k][2] = ok[k] ? (uint32_t)yuv_clampv<uint8_t>((l + D.bu * u) >> 14) : 0u;
+        int rgb[3];
+        yuv_decode_px<uint8_t>(D, Y[k], U[k], V[k], rgb);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[k][c] = ok[k] ? (uint32_t)rgb[c] : 0u;   // the zero fill, selected after the decode
     }
-    const long long plane = (long long)S * S;
-    const long long o = n * 3 * plane + (long long)y * S + x0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        uint8_t* d8 = out_u8 + o + c * plane;
-        if (VEC) {
-            *reinterpret_cast<uint32_t*>(d8) = v[0][c] | v[1][c] << 8 | v[2][c] << 16 | v[3][c] << 24;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (x0 + k < S) d8[k] = (uint8_t)v[k][c];
-        }
-        if (F32) {
-            float f[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) f[k] = __fdiv_rn((float)v[k][c], 255.0f);
-            float* df = out_f32 + o + c * plane;
-            if (VEC) {
-                *reinterpret_cast<float4*>(df) = make_float4(f[0], f[1], f[2], f[3]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (x0 + k < S) df[k] = f[k];
-            }
-        }
-    }
+    aug_store4<VEC, F32>(v, n, S, wk.y, wk.x0, out_u8, out_f32);
 }
 
-template <bool VEC, bool F32>
-static void aug_yuv_launch(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, const YuvDec& D,
-                           void* out_u8, void* out_f32, hipStream_t st) {
+// the launch of either kernel (YUV: the 4:2:0 one, which takes D) and the one VEC / F32 ladder
+template <bool YUV, bool VEC, bool F32>
+static void aug_launch(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, const YuvDec& D,
+                       void* out_u8, void* out_f32, hipStream_t st) {
     const dim3 grid((unsigned)cdiv(S * cdiv(S, 4), 256), (unsigned)n);
-    prof_note((double)n * (double)(S * S) * (F32 ? 18.0 : 6.0), 0.0);
-    OFASR_LAUNCH((aug_gather_yuv420_kernel<VEC, F32>), grid, dim3(256), 0, st, (const uint8_t*)pool, (long long)pool_bytes,
-                 (const long long*)table, (int)S, D, (uint8_t*)out_u8, (float*)out_f32);
+    prof_note((double)n * (double)(S * S) * 3.0 * (F32 ? 6.0 : 2.0), 0.0);
+    if constexpr (YUV)
+        OFASR_LAUNCH((aug_gather_yuv420_kernel<VEC, F32>), grid, dim3(256), 0, st, (const uint8_t*)pool, (long long)pool_bytes,
+                     (const long long*)table, (int)S, D, (uint8_t*)out_u8, (float*)out_f32);
+    else
+        OFASR_LAUNCH((aug_gather_u8_kernel<VEC, F32>), grid, dim3(256), 0, st, (const uint8_t*)pool, (long long)pool_bytes,
+                     (const long long*)table, (int)S, (uint8_t*)out_u8, (float*)out_f32);
+}
+template <bool YUV>
+static void aug_gather(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, const YuvDec& D,
+                       void* out_u8, void* out_f32, hipStream_t st) {
+    const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(out_u8) % 4 == 0 &&
+                     reinterpret_cast<uintptr_t>(out_f32) % 16 == 0;
+    if (out_f32) {
+        if (vec) aug_launch<YUV, true, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+        else aug_launch<YUV, false, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+    } else {
+        if (vec) aug_launch<YUV, true, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+        else aug_launch<YUV, false, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+    }
 }
 
 }  // namespace ofasr
 
 using namespace ofasr;
 
+// the checks the two entry points share
+#define AUG_REQUIRE_SIZES(n, S, pool_bytes)                                                                              \
+    OFASR_REQUIRE((n) > 0 && (S) > 0 && (pool_bytes) > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);         \
+    OFASR_REQUIRE((S) <= 4096, OFASR_ERR_UNSUPPORTED, "%s: crop side %lld above 4096 (the fixed-point walk is int32)", name, \
+                  (long long)(S));                                                                                       \
+    OFASR_REQUIRE((n) <= 65535, OFASR_ERR_UNSUPPORTED, "%s: %lld samples in one launch (at most 65535)", name, (long long)(n))
+
 OFASR_EXPORT int ofasr_aug_gather_yuv420(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S,
                                          const int32_t* coeffs, void* out_u8, void* out_f32, void* stream) {
     const char* name = "ofasr_aug_gather_yuv420";
     OFASR_REQUIRE(pool && table && coeffs && out_u8, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
-    OFASR_REQUIRE(n > 0 && S > 0 && pool_bytes > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    OFASR_REQUIRE(S <= 4096, OFASR_ERR_UNSUPPORTED, "%s: crop side %lld above 4096 (the fixed-point walk is int32)", name,
-                  (long long)S);
-    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: %lld samples in one launch (at most 65535)", name, (long long)n);
+    AUG_REQUIRE_SIZES(n, S, pool_bytes);
     OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
     // the table lives on the device: the smallest pool that can hold one even-sided frame with H, W >= S is what the
     // host can check
@@ -256,17 +260,7 @@ OFASR_EXPORT int ofasr_aug_gather_yuv420(const void* pool, int64_t pool_bytes, c
     OFASR_REQUIRE(pool_bytes >= Se * Se * 3 / 2, OFASR_ERR_UNSUPPORTED,
                   "%s: a pool of %lld bytes holds no 4:2:0 frame of at least %lldx%lld (even H, W >= S)", name,
                   (long long)pool_bytes, (long long)Se, (long long)Se);
-    hipStream_t st = as_stream(stream);
-    const YuvDec D = yuv_dec(coeffs);
-    const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(out_u8) % 4 == 0 &&
-                     reinterpret_cast<uintptr_t>(out_f32) % 16 == 0;
-    if (out_f32) {
-        if (vec) aug_yuv_launch<true, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-        else aug_yuv_launch<false, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-    } else {
-        if (vec) aug_yuv_launch<true, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-        else aug_yuv_launch<false, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-    }
+    aug_gather<true>(pool, pool_bytes, table, n, S, yuv_dec(coeffs), out_u8, out_f32, as_stream(stream));
     return check_launch(name);
 }
 
@@ -274,23 +268,11 @@ OFASR_EXPORT int ofasr_aug_gather_u8(const void* pool, int64_t pool_bytes, const
                                      void* out_u8, void* out_f32, void* stream) {
     const char* name = "ofasr_aug_gather_u8";
     OFASR_REQUIRE(pool && table && out_u8, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
-    OFASR_REQUIRE(n > 0 && S > 0 && pool_bytes > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    OFASR_REQUIRE(S <= 4096, OFASR_ERR_UNSUPPORTED, "%s: crop side %lld above 4096 (the fixed-point walk is int32)", name,
-                  (long long)S);
-    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: %lld samples in one launch (at most 65535)", name, (long long)n);
+    AUG_REQUIRE_SIZES(n, S, pool_bytes);
     // the table lives on the device: the smallest pool that can hold one H, W >= S image is what the host can check
     OFASR_REQUIRE(pool_bytes >= 3 * S * S, OFASR_ERR_UNSUPPORTED,
                   "%s: a pool of %lld bytes holds no image of at least %lldx%lld (H, W >= S)", name, (long long)pool_bytes,
                   (long long)S, (long long)S);
-    hipStream_t st = as_stream(stream);
-    const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(out_u8) % 4 == 0 &&
-                     reinterpret_cast<uintptr_t>(out_f32) % 16 == 0;
-    if (out_f32) {
-        if (vec) aug_launch<true, true>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
-        else aug_launch<false, true>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
-    } else {
-        if (vec) aug_launch<true, false>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
-        else aug_launch<false, false>(pool, pool_bytes, table, n, S, out_u8, out_f32, st);
-    }
+    aug_gather<false>(pool, pool_bytes, table, n, S, YuvDec{}, out_u8, out_f32, as_stream(stream));
     return check_launch(name);
 }

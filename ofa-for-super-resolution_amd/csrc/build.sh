@@ -8,7 +8,11 @@ objs=()
 pids=()
 for src in api.hip pixel_shuffle.hip ktransform.hip dwconv.hip pwconv.hip bnact.hip mbconv.hip conv2d.hip conv2d_f32.hip conv_thin.hip mbfused.hip mbfused_f32.hip mbrecal_f32.hip resample.hip tile_io.hip d4.hip add.hip quality.hip augment.hip yuv.hip reuse.hip route.hip resize_scatter.hip mode_io.hip; do
     obj="${src%.hip}.o"
-    if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ ofasr_common.h -nt "$obj" ] || [ yuv_block.h -nt "$obj" ] || [ pw_wgrad_stream.h -nt "$obj" ] || [ ../../include/ofasr.h -nt "$obj" ]; then
+    stale=0                                # no object, or one older than its source or than ANY header of csrc/
+    for dep in "$src" *.h ../../include/ofasr.h; do
+        if [ ! -f "$obj" ] || [ "$dep" -nt "$obj" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
         rm -f "$obj"                       # a failed compile must not leave a stale object to link
         hipcc $FLAGS -c "$src" -o "$obj" &
         pids+=($!)

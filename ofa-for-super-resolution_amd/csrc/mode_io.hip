@@ -28,15 +28,13 @@
 // counts are clamped to kh / kw, every source index into the alpha plane, every LDS row into the tile's span, and loads
 // sit inside the branch that bounds them.  A wrong table gives wrong values, never a fault.  The accumulators are
 // unsigned, so a wild coefficient wraps instead of overflowing.
-#include "ofasr_common.h"
+#include "tile_table.h"
 
 namespace ofasr {
 
 constexpr int MP_TY = 16, MP_TX = 64, MP_ROWS = 24, MP_TAPS = 7, MP_BITS = 22;
 constexpr int MP_SLOTS = MP_TX + 1;      // aligned dwords that can cover one row of a tile: (3 + 64 * 4 + 3) / 4
 
-__device__ __forceinline__ int mp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int mp_clampl(long long v, long long lo, long long hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 __device__ __forceinline__ uint32_t mp_clip8(uint32_t acc) {
     const int v = (int)acc >> MP_BITS;
     return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
@@ -111,16 +109,16 @@ __global__ void __launch_bounds__(256) mode_pack_kernel(const uint8_t* __restric
         vt = vtab + r0 * vs;                                   // rows r0 .. r0 + nr - 1 < TH
         const int* ht = htab + c0 * hs;
         // the source rows of the tile: from the first row's first tap to the last row's last
-        ylo = mp_clampl((long long)vt[0], 0, H - 1);
+        ylo = clampi((long long)vt[0], 0, H - 1);
         const int* vl = vt + (long long)(nr - 1) * vs;
-        const long long yhi = (long long)vl[0] + mp_clampi(vl[1], 0, kh);
-        span = mp_clampl(yhi - ylo, 1, MP_ROWS);
+        const long long yhi = (long long)vl[0] + clampi(vl[1], 0, kh);
+        span = clampi(yhi - ylo, 1, MP_ROWS);
         span = span > H - ylo ? (int)(H - ylo) : span;
         const uint8_t* sn = alpha + (long long)ylo * W;
         if (col < nc) {
             // the column's taps once, in registers, for every source row of the tile
             const int* h = ht + (long long)col * hs;
-            const int cnt = mp_clampi(h[1], 0, kw);
+            const int cnt = clampi(h[1], 0, kw);
             const long long x0 = (long long)h[0];
             uint32_t kc[MP_TAPS];
             int xl[MP_TAPS];
@@ -128,7 +126,7 @@ __global__ void __launch_bounds__(256) mode_pack_kernel(const uint8_t* __restric
             for (int k = 0; k < MP_TAPS; ++k) {
                 kc[k] = 0u;
                 if (k < cnt) kc[k] = (uint32_t)h[2 + k];
-                xl[k] = mp_clampl(x0 + k, 0, W - 1);
+                xl[k] = clampi(x0 + k, 0, W - 1);
             }
             for (int row = wrow; row < span; row += WAVES) {
                 const uint8_t* s = sn + (long long)row * W;
@@ -148,11 +146,11 @@ __global__ void __launch_bounds__(256) mode_pack_kernel(const uint8_t* __restric
             uint32_t a = 0u;
             if constexpr (C != 1) {
                 const int* vrow = vt + (long long)r * vs;
-                const int cnt = mp_clampi(vrow[1], 0, kh);
+                const int cnt = clampi(vrow[1], 0, kh);
                 const long long y0 = (long long)vrow[0] - ylo;   // first tap's row inside the tile's span
                 uint32_t acc = 1u << (MP_BITS - 1);
                 for (int k = 0; k < cnt; ++k) {
-                    const int yl = mp_clampl(y0 + k, 0, span - 1);
+                    const int yl = clampi(y0 + k, 0, span - 1);
                     acc += (uint32_t)mid[yl * MP_TX + col] * (uint32_t)vrow[2 + k];
                 }
                 a = mp_clip8(acc);

@@ -21,20 +21,16 @@
 //      yuv_store_block, the code the full-size scatter uses).
 // LDS: 3 * 96 * 64 samples = 18 KiB (8-bit) / 36 KiB (16-bit).  No scratch.
 //
-// Addressing is 64-bit.  Every access stays inside its tensor whatever the device tables hold: the table row is clamped
-// as in ofasr_tile_scatter_u8, the target rectangle to the target frame, xmin / count to the table's width, every source
-// index into the window and every LDS row into the tile's span.  A wrong table gives wrong values, never a fault.  All
-// loads sit inside the branch that bounds them.  The accumulators are unsigned, so a wild coefficient wraps instead of
-// overflowing; with tables of resize.py they stay inside int32 as Pillow's do.
-#include "ofasr_common.h"
+// Addressing is 64-bit.  Every access stays inside its tensor whatever the device tables hold: the table row's target
+// rectangle is clamped by scatter_dest (tile_table.h: the destination half of ofasr_tile_scatter_u8's rule), xmin /
+// count to the table's width, every source index into the window and every LDS row into the tile's span.  A wrong table
+// gives wrong values, never a fault.  All loads sit inside the branch that bounds them.  The accumulators are unsigned,
+// so a wild coefficient wraps instead of overflowing; with tables of resize.py they stay inside int32 as Pillow's do.
 #include "yuv_block.h"
 
 namespace ofasr {
 
 constexpr int RS_TY = 16, RS_TX = 64, RS_ROWS = 96, RS_TAPS = 25;
-
-__device__ __forceinline__ int rsz_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int rsz_clampl(long long v, long long lo, long long hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 
 struct RszSinkRgb { uint8_t* img; };
 template <typename P> struct RszSinkYuv { P* y; P* u; P* v; YuvEnc E; };
@@ -43,11 +39,11 @@ template <typename P> struct RszSinkYuv { P* y; P* u; P* v; YuvEnc E; };
 template <typename P, int BITS>
 __device__ __forceinline__ void rsz_vertical(const P* mid, const int* __restrict__ vrow, int kh, long long ybase, int span, int col,
                                              int (&rgb)[3]) {
-    const int cnt = rsz_clampi(vrow[1], 0, kh);
+    const int cnt = clampi(vrow[1], 0, kh);
     const long long y0 = (long long)vrow[0] - ybase;       // first tap's row inside the tile's span
     uint32_t acc[3] = {1u << (BITS - 1), 1u << (BITS - 1), 1u << (BITS - 1)};
     for (int k = 0; k < cnt; ++k) {
-        const int yl = rsz_clampl(y0 + k, 0, span - 1);
+        const int yl = clampi(y0 + k, 0, span - 1);
         const uint32_t w = (uint32_t)vrow[2 + k];
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[c] += (uint32_t)mid[(c * RS_ROWS + yl) * RS_TX + col] * w;
@@ -68,18 +64,8 @@ __global__ void __launch_bounds__(256) tile_resize_scatter_kernel(const T* __res
     constexpr int BITS = 32 - (sizeof(P) == 1 ? 8 : 10) - 2;
     __shared__ P mid[3 * RS_ROWS * RS_TX];
     const long long n = blockIdx.y;
-    const long long* t = table + 6 * n;
-    const long long oy = t[0], ox = t[1];
-    long long dy = t[2], dx = t[3], eh = t[4], ew = t[5];
-    dy = dy < 0 ? 0 : (dy > TH ? TH : dy);
-    dx = dx < 0 ? 0 : (dx > TW ? TW : dx);
-    eh = eh < 0 ? 0 : eh;
-    ew = ew < 0 ? 0 : ew;
-    eh = eh > max_eh ? max_eh : eh;
-    ew = ew > max_ew ? max_ew : ew;
-    eh = eh > TH - dy ? TH - dy : eh;
-    ew = ew > TW - dx ? TW - dx : ew;
-    if (YUV) dy &= ~1LL, dx &= ~1LL, eh &= ~1LL, ew &= ~1LL;   // whole 2 x 2 blocks only, as the full-size scatter
+    const ScatterRow t = scatter_dest(table, n, TH, TW, max_eh, max_ew, YUV);   // YUV: whole 2 x 2 blocks only
+    const long long oy = t.sy, ox = t.sx, dy = t.dy, dx = t.dx, eh = t.eh, ew = t.ew;
     const long long tiles_x = (max_ew + RS_TX - 1) / RS_TX;
     const long long ty = (long long)blockIdx.x / tiles_x, tx = (long long)blockIdx.x - ty * tiles_x;
     const long long r0 = ty * RS_TY, c0 = tx * RS_TX;
@@ -89,10 +75,10 @@ __global__ void __launch_bounds__(256) tile_resize_scatter_kernel(const T* __res
     const int* vt = vtab + (dy + r0) * vs;                     // rows dy + r0 .. dy + r0 + nr - 1 < TH
     const int* ht = htab + (dx + c0) * hs;
     // the source rows of the tile, window-local: from the first row's first tap to the last row's last
-    const int ylo = rsz_clampl((long long)vt[0] - oy, 0, sh_ - 1);
+    const int ylo = clampi((long long)vt[0] - oy, 0, sh_ - 1);
     const int* vl = vt + (long long)(nr - 1) * vs;
-    const long long yhi = (long long)vl[0] + rsz_clampi(vl[1], 0, kh) - oy;
-    int span = rsz_clampl(yhi - ylo, 1, RS_ROWS);
+    const long long yhi = (long long)vl[0] + clampi(vl[1], 0, kh) - oy;
+    int span = clampi(yhi - ylo, 1, RS_ROWS);
     span = span > sh_ - ylo ? (int)(sh_ - ylo) : span;
     const long long plane = sh_ * sw;
     const T* sn = src + n * 3 * plane + (long long)ylo * sw;
@@ -102,15 +88,15 @@ __global__ void __launch_bounds__(256) tile_resize_scatter_kernel(const T* __res
         const int row = e / RS_TX, col = e % RS_TX;
         if (col < nc) {
             const int* h = ht + (long long)col * hs;
-            const int cnt = rsz_clampi(h[1], 0, kw);
+            const int cnt = clampi(h[1], 0, kw);
             const long long x0 = (long long)h[0] - ox;
             const T* s = sn + (long long)row * sw;
             uint32_t acc[3] = {1u << (BITS - 1), 1u << (BITS - 1), 1u << (BITS - 1)};
             for (int k = 0; k < cnt; ++k) {
-                const int xl = rsz_clampl(x0 + k, 0, sw - 1);
+                const int xl = clampi(x0 + k, 0, sw - 1);
                 const uint32_t w = (uint32_t)h[2 + k];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) acc[c] += (uint32_t)yuv_quant<P>(to_float(s[c * plane + xl])) * w;
+                for (int c = 0; c < 3; ++c) acc[c] += (uint32_t)quant<yuv_px<P>::maxv>(to_float(s[c * plane + xl])) * w;
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) mid[(c * RS_ROWS + row) * RS_TX + col] = (P)yuv_clampv<P>((int)acc[c] >> BITS);
@@ -175,8 +161,7 @@ static int rsz_dispatch(const char* name, const void* src, int64_t n, int64_t sh
     OFASR_REQUIRE(src && table && vtab && htab, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && TH > 0 && TW > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG,
                   "%s: non-positive size", name);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
+    TILE_REQUIRE_DTYPE(dtype);
     OFASR_REQUIRE(kh >= 1 && kw >= 1, OFASR_ERR_INVALID_ARG, "%s: a coefficient table without taps", name);
     OFASR_REQUIRE(kh <= RS_TAPS && kw <= RS_TAPS, OFASR_ERR_UNSUPPORTED,
                   "%s: %d x %d taps; at most %d per axis (lanczos at a 4 : 1 reduction)", name, kh, kw, RS_TAPS);
@@ -185,9 +170,9 @@ static int rsz_dispatch(const char* name, const void* src, int64_t n, int64_t sh
                       cdiv(max_eh, RS_TY) * cdiv(max_ew, RS_TX) <= 0x7fffffffLL,
                   OFASR_ERR_UNSUPPORTED, "%s: too many windows or too large an image", name);
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F32) rsz_launch<float, P, YUV>(src, n, sh, sw, table, vtab, kh, htab, kw, sink, TH, TW, max_eh, max_ew, st);
-    else if (dtype == OFASR_BF16) rsz_launch<bf16_t, P, YUV>(src, n, sh, sw, table, vtab, kh, htab, kw, sink, TH, TW, max_eh, max_ew, st);
-    else rsz_launch<f16_t, P, YUV>(src, n, sh, sw, table, vtab, kh, htab, kw, sink, TH, TW, max_eh, max_ew, st);
+    dispatch_float(dtype, [&](auto t) {
+        rsz_launch<typename decltype(t)::type, P, YUV>(src, n, sh, sw, table, vtab, kh, htab, kw, sink, TH, TW, max_eh, max_ew, st);
+    });
     return check_launch(name);
 }
 

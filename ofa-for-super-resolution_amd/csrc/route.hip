@@ -13,18 +13,17 @@
 //          aligned for them (upper and lower row decided separately), everything else sample by sample.  Every load is
 //          predicated on the sample lying inside the window rectangle, which lies inside the plane.  A work item sums at
 //          most 32 differences of at most 65535 in int32; everything above it is int64.  64-bit addressing.
-// route:   ONE workgroup, as window_compact_kernel.  Per round of 256 windows: fold the S partials, compare with limit,
-//          fold the S' changed flags if there are any; per class ballot + popcount inside the wave, the four wave totals
-//          through LDS; rows go out in plan order, class 0 (hard) and class 1 (easy) into their own tables.
-#include "ofasr_common.h"
+//          The origin is window_origin's, the rows of a slab slab_rows' (tile_table.h).
+// route:   ONE workgroup, as window_compact_kernel: window_compact_by_class (tile_table.h) with two classes.  Per round
+//          of 256 windows: fold the S partials, compare with limit, fold the S' changed flags if there are any; per
+//          class ballot + popcount inside the wave, the four wave totals through LDS; rows go out in plan order, class 0
+//          (hard) and class 1 (easy) into their own tables.
+#include "tile_table.h"
 
 namespace ofasr {
 
-static const int ROUTE_THREADS = 256;
-static const int ROUTE_MAX_SLABS = 64;
+static const int ROUTE_THREADS = WINDOW_THREADS;
 static const long long ROUTE_SLAB_SAMPLES = 16384;    // samples of a window per workgroup, about
-
-__device__ __forceinline__ long long route_clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // sample j of a row: BPS 1 / 2: the stored sample; BPS 3: the luma of the RGB pixel
 template <int BPS> __device__ __forceinline__ int route_sample(const uint8_t* p, long long j) {
@@ -80,9 +79,10 @@ __global__ void __launch_bounds__(ROUTE_THREADS) window_activity_kernel(
     long long* __restrict__ partial) {
     __shared__ long long red[ROUTE_THREADS];
     const long long n = blockIdx.y, s = blockIdx.x, S = gridDim.x;
-    const long long y0 = route_clampll(origins[2 * n], 0, H - h), x0 = route_clampll(origins[2 * n + 1], 0, W - w);
-    const long long per = (h + S - 1) / S;
-    const long long lo = s * per < h ? s * per : h, hi = lo + per < h ? lo + per : h;
+    const WindowOrigin o0 = window_origin(origins, n, H, W, h, w);
+    const long long y0 = o0.y0, x0 = o0.x0;
+    long long lo, hi;
+    slab_rows(h, s, S, lo, hi);
     const long long K = ((w + 15) >> 4) + 1;           // the head and the chunks behind it
     const long long items = (hi - lo) * K;
     long long acc = 0;
@@ -131,78 +131,21 @@ __global__ void __launch_bounds__(ROUTE_THREADS) window_route_kernel(
     const long long* __restrict__ origins, const long long* __restrict__ table, long long n, long long B,
     long long* __restrict__ out_origins, long long* __restrict__ out_table, long long* __restrict__ out_index,
     long long* __restrict__ count) {
-    __shared__ long long wave_total[2][ROUTE_THREADS / 64];
-    __shared__ long long last[2];                       // plan index of the class's last window so far
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    const long long rows = (n + B - 1) / B * B;
-    if (threadIdx.x < 2) last[threadIdx.x] = 0;
-    long long m[2] = {0, 0};                            // windows of each class before this round (the same in every thread)
-    for (long long i0 = 0; i0 < n; i0 += ROUTE_THREADS) {
-        const long long i = i0 + threadIdx.x;
-        int cls = -1;                                   // -1: not in either list
-        if (i < n) {
-            int f = 1;
-            if (changed) {
-                f = 0;
-                for (long long s = 0; s < CS; ++s) f |= changed[i * CS + s];
-            }
-            if (f) {
-                long long A = 0;
-                for (long long s = 0; s < S; ++s) A += partial[i * S + s];
-                cls = A <= limit ? 1 : 0;
-            }
+    const auto cls_of = [&](long long i) {              // 0: hard, 1: easy, -1: unchanged, in neither list
+        int f = 1;
+        if (changed) {
+            f = 0;
+            for (long long s = 0; s < CS; ++s) f |= changed[i * CS + s];
         }
-        unsigned long long mask[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            mask[c] = __ballot(cls == c);
-            if (lane == 0) wave_total[c][wave] = __popcll(mask[c]);
+        int cls = -1;
+        if (f) {
+            long long A = 0;
+            for (long long s = 0; s < S; ++s) A += partial[i * S + s];
+            cls = A <= limit ? 1 : 0;
         }
-        __syncthreads();
-        long long tot[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            long long before = m[c];
-            tot[c] = 0;
-#pragma unroll
-            for (int q = 0; q < ROUTE_THREADS / 64; ++q) {
-                before += q < wave ? wave_total[c][q] : 0;
-                tot[c] += wave_total[c][q];
-            }
-            if (cls == c) {
-                const long long pos = before + __popcll(mask[c] & ((1ull << lane) - 1ull));   // < n: positions are distinct
-                long long* oo = out_origins + (c * rows + pos) * 2;
-                oo[0] = origins[2 * i];
-                oo[1] = origins[2 * i + 1];
-                long long* ot = out_table + (c * n + pos) * 6;
-#pragma unroll
-                for (int q = 0; q < 6; ++q) ot[q] = table[6 * i + q];
-                out_index[c * n + pos] = i;
-                if (pos == m[c] + tot[c] - 1) last[c] = i;   // one thread per class and round at most
-            }
-            m[c] += tot[c];
-        }
-        __syncthreads();                                 // wave_total is rewritten by the next round
-    }
-    // each class's last batch is filled up by repeating its last window (an empty class: nothing to fill)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const long long padded = (m[c] + B - 1) / B * B; // <= rows
-        const long long li = last[c];
-        for (long long j = m[c] + threadIdx.x; j < padded; j += ROUTE_THREADS) {
-            out_origins[(c * rows + j) * 2] = origins[2 * li];
-            out_origins[(c * rows + j) * 2 + 1] = origins[2 * li + 1];
-        }
-    }
-    if (threadIdx.x < 2) count[threadIdx.x] = threadIdx.x == 0 ? m[0] : m[1];
-}
-
-static int64_t route_slabs(int64_t h, int64_t w) {
-    if (h <= 0 || w <= 0) return 0;
-    int64_t s = h <= (1LL << 40) / w ? cdiv(h * w, ROUTE_SLAB_SAMPLES) : ROUTE_MAX_SLABS;
-    s = s < ROUTE_MAX_SLABS ? s : ROUTE_MAX_SLABS;
-    s = s < h ? s : h;
-    return s < 1 ? 1 : s;
+        return cls;
+    };
+    window_compact_by_class<2>(cls_of, origins, table, n, B, out_origins, out_table, out_index, count);
 }
 
 template <int BPS>
@@ -210,11 +153,9 @@ static int route_window_activity(const char* name, const void* src, int64_t H, i
                                  int64_t h, int64_t w, int64_t* partial, void* stream) {
     OFASR_REQUIRE(src && origins && partial, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && h > 0 && w > 0 && H > 0 && W > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    OFASR_REQUIRE(H <= (1LL << 40) / W, OFASR_ERR_UNSUPPORTED, "%s: too large a frame", name);
-    OFASR_REQUIRE(h <= H && w <= W, OFASR_ERR_INVALID_ARG, "%s: window %lldx%lld larger than the frame %lldx%lld", name,
-                  (long long)h, (long long)w, (long long)H, (long long)W);
-    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
-    const int64_t S = route_slabs(h, w);
+    TILE_REQUIRE_FRAME_CAP(H, W);
+    TILE_REQUIRE_WINDOWS(n, h, w, H, W, "frame", "too many windows");
+    const int64_t S = window_slabs(h, w, ROUTE_SLAB_SAMPLES);
     prof_note((double)n * (double)(h * w) * BPS, 0.0);
     OFASR_LAUNCH(window_activity_kernel<BPS>, dim3((unsigned)S, (unsigned)n), dim3(ROUTE_THREADS), 0, as_stream(stream),
                  (const uint8_t*)src, (long long)H, (long long)W, (const long long*)origins, (long long)h, (long long)w,
@@ -226,7 +167,7 @@ static int route_window_activity(const char* name, const void* src, int64_t H, i
 
 using namespace ofasr;
 
-OFASR_EXPORT int64_t ofasr_window_activity_slabs(int64_t h, int64_t w) { return route_slabs(h, w); }
+OFASR_EXPORT int64_t ofasr_window_activity_slabs(int64_t h, int64_t w) { return window_slabs(h, w, ROUTE_SLAB_SAMPLES); }
 
 OFASR_EXPORT int ofasr_window_activity_rgb8(const void* img, int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h,
                                             int64_t w, int64_t* partial, void* stream) {
@@ -253,8 +194,8 @@ OFASR_EXPORT int ofasr_window_route(const int64_t* partial, int64_t slabs, int64
     OFASR_REQUIRE(n > 0 && batch > 0 && slabs > 0 && (!changed || changed_slabs > 0), OFASR_ERR_INVALID_ARG,
                   "%s: non-positive size", name);
     OFASR_REQUIRE(n <= 65535 && batch <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
-    OFASR_REQUIRE(slabs <= ROUTE_MAX_SLABS && (!changed || changed_slabs <= ROUTE_MAX_SLABS), OFASR_ERR_INVALID_ARG,
-                  "%s: more than %d slabs", name, ROUTE_MAX_SLABS);
+    OFASR_REQUIRE(slabs <= WINDOW_MAX_SLABS && (!changed || changed_slabs <= WINDOW_MAX_SLABS), OFASR_ERR_INVALID_ARG,
+                  "%s: more than %d slabs", name, WINDOW_MAX_SLABS);
     prof_note((double)n * (8.0 * (double)slabs + (changed ? 4.0 * (double)changed_slabs : 0.0) + 136.0), 0.0);
     OFASR_LAUNCH(window_route_kernel, dim3(1), dim3(ROUTE_THREADS), 0, as_stream(stream), (const long long*)partial,
                  (long long)slabs, (long long)limit, (const int*)changed, (long long)(changed ? changed_slabs : 0),

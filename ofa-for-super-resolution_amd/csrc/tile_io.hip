@@ -7,8 +7,9 @@
 //   scatter: img[dy_n + r, dx_n + x, c] = rint(min(max(src[n, c, sy_n + r, sx_n + x], 0), 1) * 255)    (the steps of
 //            utils.tensor2img_np / psnr_y_device: clamp, * 255 in fp32, round half to even)
 // Addressing is 64-bit throughout (a 4x output of an 8K input is > 2^31 bytes).  Every access stays inside its tensor
-// whatever the device tables hold: origins and offsets are clamped into range in the kernel, and the uint8 side's
-// aligned dword loads fall back to byte loads for the (at most two) words that straddle the ends of the image.
+// whatever the device tables hold: origins and table rows are clamped into range in the kernel (window_origin /
+// scatter_row, tile_table.h), and the uint8 side's aligned dword loads fall back to byte loads for the (at most two)
+// words that straddle the ends of the image.
 //
 // Access widths.  gather: a lane owns 4 consecutive pixels of one window row: 12 bytes of HWC input read as 4 aligned
 // dwords (funnel-shifted into place with v_alignbyte), 3 row-contiguous 4-element planar stores (16 B for fp32, 8 B for
@@ -16,7 +17,7 @@
 // the 4 pixels of an aligned 4-pixel group of the destination image (12 bytes = 3 aligned dwords, stored as one
 // dwordx3) -- groups cut by the edge of a core are written byte by byte, since their other bytes belong to a neighbour
 // core; the planar source reads are consecutive across the lanes of a wave.
-#include "ofasr_common.h"
+#include "tile_table.h"
 
 namespace ofasr {
 
@@ -32,29 +33,14 @@ __device__ __forceinline__ uint32_t tio_word(uintptr_t q, uintptr_t b, uintptr_t
     return v;
 }
 
-template <typename T> struct tio_vec4;
-template <> struct tio_vec4<float> { typedef float4 type; };
-template <> struct tio_vec4<bf16_t> { typedef uint2 type; };
-template <> struct tio_vec4<f16_t> { typedef uint2 type; };
-
-template <typename T> __device__ __forceinline__ typename tio_vec4<T>::type tio_pack4(const float* v);
-template <> __device__ __forceinline__ float4 tio_pack4<float>(const float* v) { return make_float4(v[0], v[1], v[2], v[3]); }
-template <> __device__ __forceinline__ uint2 tio_pack4<bf16_t>(const float* v) {
-    return make_uint2(pack2<bf16_t>(v[0], v[1]), pack2<bf16_t>(v[2], v[3]));
-}
-template <> __device__ __forceinline__ uint2 tio_pack4<f16_t>(const float* v) {
-    return make_uint2(pack2<f16_t>(v[0], v[1]), pack2<f16_t>(v[2], v[3]));
-}
-
 // grid: (x: lanes over h * ceil(w / 4) in a grid-stride loop, y: window)
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) tile_gather_u8_kernel(const uint8_t* __restrict__ img, long long H, long long W,
                                                              const long long* __restrict__ origins, long long h,
                                                              long long w, T* __restrict__ out) {
     const long long n = blockIdx.y;
-    long long y0 = origins[2 * n], x0 = origins[2 * n + 1];
-    y0 = y0 < 0 ? 0 : (y0 > H - h ? H - h : y0);
-    x0 = x0 < 0 ? 0 : (x0 > W - w ? W - w : x0);
+    const WindowOrigin o0 = window_origin(origins, n, H, W, h, w);
+    const long long y0 = o0.y0, x0 = o0.x0;
     const uintptr_t ib = reinterpret_cast<uintptr_t>(img), ie = ib + (uintptr_t)(H * W * 3);
     const long long gw = (w + 3) >> 2;
     const long long plane = h * w;
@@ -81,7 +67,7 @@ __global__ void __launch_bounds__(256) tile_gather_u8_kernel(const uint8_t* __re
             }
             T* dst = on + c * plane + o;
             if (VEC) {
-                *reinterpret_cast<typename tio_vec4<T>::type*>(dst) = tio_pack4<T>(v);
+                *reinterpret_cast<typename vec4<T>::type*>(dst) = pack4<T>(v);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -91,11 +77,6 @@ __global__ void __launch_bounds__(256) tile_gather_u8_kernel(const uint8_t* __re
     }
 }
 
-__device__ __forceinline__ uint32_t tio_quant(float v) {
-    const float f = fminf(fmaxf(v, 0.0f), 1.0f);
-    return (uint32_t)rintf(__fmul_rn(f, 255.0f));
-}
-
 // table[6 n ..]: sy, sx, dy, dx, eh, ew.  grid: (x: lanes over max_eh * (max_ew / 4 + 2) groups, y: window)
 template <typename T, bool WIDE>
 __global__ void __launch_bounds__(256) tile_scatter_u8_kernel(const T* __restrict__ src, long long sh_, long long sw,
@@ -103,20 +84,8 @@ __global__ void __launch_bounds__(256) tile_scatter_u8_kernel(const T* __restric
                                                               long long OH, long long OW, long long max_eh,
                                                               long long max_ew) {
     const long long n = blockIdx.y;
-    const long long* t = table + 6 * n;
-    long long sy = t[0], sx = t[1], dy = t[2], dx = t[3], eh = t[4], ew = t[5];
-    sy = sy < 0 ? 0 : (sy > sh_ ? sh_ : sy);
-    sx = sx < 0 ? 0 : (sx > sw ? sw : sx);
-    dy = dy < 0 ? 0 : (dy > OH ? OH : dy);
-    dx = dx < 0 ? 0 : (dx > OW ? OW : dx);
-    eh = eh < 0 ? 0 : eh;
-    ew = ew < 0 ? 0 : ew;
-    eh = eh > max_eh ? max_eh : eh;
-    ew = ew > max_ew ? max_ew : ew;
-    eh = eh > sh_ - sy ? sh_ - sy : eh;
-    eh = eh > OH - dy ? OH - dy : eh;
-    ew = ew > sw - sx ? sw - sx : ew;
-    ew = ew > OW - dx ? OW - dx : ew;
+    const ScatterRow t = scatter_row(table, n, sh_, sw, OH, OW, max_eh, max_ew);
+    const long long sy = t.sy, sx = t.sx, dy = t.dy, dx = t.dx, eh = t.eh, ew = t.ew;
     const long long G = (max_ew >> 2) + 2;
     const long long plane = sh_ * sw;
     const T* sn = src + n * 3 * plane;
@@ -133,7 +102,7 @@ __global__ void __launch_bounds__(256) tile_scatter_u8_kernel(const T* __restric
             const long long p = p0 + j;
             in[j] = p >= F && p < F + ew;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) q[j][c] = in[j] ? tio_quant(to_float(s[c * plane + p])) : 0u;
+            for (int c = 0; c < 3; ++c) q[j][c] = in[j] ? (uint32_t)quant<255>(to_float(s[c * plane + p])) : 0u;
         }
         uint8_t* d = img + p0 * 3;
         if (WIDE && in[0] && in[3]) {
@@ -153,17 +122,12 @@ __global__ void __launch_bounds__(256) tile_scatter_u8_kernel(const T* __restric
     }
 }
 
-static unsigned tio_blocks(long long work) {
-    const long long b = cdiv(work, 256);
-    return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
-
 template <typename T>
 static void tio_gather(const void* img, int64_t H, int64_t W, const int64_t* origins, int64_t n, int64_t h, int64_t w,
                        void* out, hipStream_t st) {
     const size_t al = sizeof(T) == 4 ? 16 : 8;
     const bool vec = w % 4 == 0 && reinterpret_cast<uintptr_t>(out) % al == 0;
-    const dim3 grid(tio_blocks(h * cdiv(w, 4)), (unsigned)n);
+    const dim3 grid(grid_blocks(h * cdiv(w, 4)), (unsigned)n);
     prof_note((double)n * (double)(h * w) * (3.0 + 3.0 * sizeof(T)), 0.0);
     if (vec)
         OFASR_LAUNCH((tile_gather_u8_kernel<T, true>), grid, dim3(256), 0, st, (const uint8_t*)img, (long long)H,
@@ -177,7 +141,7 @@ template <typename T>
 static void tio_scatter(const void* src, int64_t n, int64_t sh, int64_t sw, const int64_t* table, void* img, int64_t OH,
                         int64_t OW, int64_t max_eh, int64_t max_ew, hipStream_t st) {
     const bool wide = reinterpret_cast<uintptr_t>(img) % 4 == 0;
-    const dim3 grid(tio_blocks(max_eh * ((max_ew >> 2) + 2)), (unsigned)n);
+    const dim3 grid(grid_blocks(max_eh * ((max_ew >> 2) + 2)), (unsigned)n);
     prof_note((double)n * (double)(max_eh * max_ew) * (3.0 + 3.0 * sizeof(T)), 0.0);
     if (wide)
         OFASR_LAUNCH((tile_scatter_u8_kernel<T, true>), grid, dim3(256), 0, st, (const T*)src, (long long)sh,
@@ -198,16 +162,10 @@ OFASR_EXPORT int ofasr_tile_gather_u8(const void* img, int64_t H, int64_t W, con
     const char* name = "ofasr_tile_gather_u8";
     OFASR_REQUIRE(img && origins && out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(H > 0 && W > 0 && n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
-    OFASR_REQUIRE(h <= H && w <= W, OFASR_ERR_INVALID_ARG, "%s: window %lldx%lld larger than the image %lldx%lld", name,
-                  (long long)h, (long long)w, (long long)H, (long long)W);
-    OFASR_REQUIRE(n <= 65535 && H <= (1LL << 40) / W, OFASR_ERR_UNSUPPORTED, "%s: too many windows or too large an image",
-                  name);
+    TILE_REQUIRE_DTYPE(dtype);
+    TILE_REQUIRE_WINDOWS(n, h, w, H, W, "image", "too many windows or too large an image");
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F32) tio_gather<float>(img, H, W, origins, n, h, w, out, st);
-    else if (dtype == OFASR_BF16) tio_gather<bf16_t>(img, H, W, origins, n, h, w, out, st);
-    else tio_gather<f16_t>(img, H, W, origins, n, h, w, out, st);
+    dispatch_float(dtype, [&](auto t) { tio_gather<typename decltype(t)::type>(img, H, W, origins, n, h, w, out, st); });
     return check_launch(name);
 }
 
@@ -217,15 +175,13 @@ OFASR_EXPORT int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, i
     OFASR_REQUIRE(src && table && img, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && OH > 0 && OW > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG,
                   "%s: non-positive size", name);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
+    TILE_REQUIRE_DTYPE(dtype);
     OFASR_REQUIRE(max_eh <= sh && max_ew <= sw, OFASR_ERR_INVALID_ARG, "%s: extent bound larger than the source window",
                   name);
-    OFASR_REQUIRE(n <= 65535 && OH <= (1LL << 40) / OW, OFASR_ERR_UNSUPPORTED,
-                  "%s: too many windows or too large an image", name);
+    TILE_REQUIRE_COUNT(n, OH, OW, "too many windows or too large an image");
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F32) tio_scatter<float>(src, n, sh, sw, table, img, OH, OW, max_eh, max_ew, st);
-    else if (dtype == OFASR_BF16) tio_scatter<bf16_t>(src, n, sh, sw, table, img, OH, OW, max_eh, max_ew, st);
-    else tio_scatter<f16_t>(src, n, sh, sw, table, img, OH, OW, max_eh, max_ew, st);
+    dispatch_float(dtype, [&](auto t) {
+        tio_scatter<typename decltype(t)::type>(src, n, sh, sw, table, img, OH, OW, max_eh, max_ew, st);
+    });
     return check_launch(name);
 }

@@ -11,9 +11,10 @@
 //           U = clamp(((sum over the 2x2 block of (ur R + ug G + ub B) + 2^15) >> 16) + 128), V alike
 // The tile moves are the ones of tile_io.hip with these in front / behind:
 //   gather:  out[n, c, r, x] = (T)(RGB_c(y0_n + r, x0_n + x) / 255.0f), RGB the decode at frame coordinates
-//   scatter: the 2x2 blocks of tio_quant(src) (clamp, * 255 in fp32, rintf) encoded into the three planes
+//   scatter: the 2x2 blocks of quant<255>(src) (clamp, * 255 in fp32, rintf) encoded into the three planes
 // so no RGB frame exists on either side of the network.  Addressing is 64-bit throughout.  Every access stays inside its
-// tensor whatever the device tables hold: origins, offsets and extents are clamped in the kernels.
+// tensor whatever the device tables hold: origins, offsets and extents are clamped in the kernels by window_origin and
+// scatter_row with its `even` rule (tile_table.h).
 //
 // Access widths.  A lane owns a 2-row x 4-column pixel block whose corner is even in both frame coordinates, i.e. two
 // whole chroma samples per plane: a decode fetches the 3 x 4 chroma neighbourhood of the block once per plane (byte loads
@@ -28,7 +29,6 @@
 // widths double in bytes and stay the same in samples: a luma row of a block is one 8-byte access, a chroma pair one
 // 32-bit store, under the same conditions (address aligned for it, block whole), samples one by one elsewhere.  Every
 // stored word is <= 1023.  The 8-bit instantiations are what they were before the sample type became a parameter.
-#include "ofasr_common.h"
 #include "yuv_block.h"
 
 namespace ofasr {
@@ -44,9 +44,9 @@ __device__ __forceinline__ void yuv_decode_block(const P* __restrict__ yp, const
     const long long cy = by >> 1, cx = bx >> 1;
     long long rows[3], cols[4];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) rows[i] = yuv_clampll(cy - 1 + i, 0, CH - 1) * CW;
+    for (int i = 0; i < 3; ++i) rows[i] = clampll(cy - 1 + i, 0, CH - 1) * CW;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) cols[j] = yuv_clampll(cx - 1 + j, 0, CW - 1);
+    for (int j = 0; j < 4; ++j) cols[j] = clampll(cx - 1 + j, 0, CW - 1);
     int cu[3][4], cv[3][4];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -73,12 +73,9 @@ __device__ __forceinline__ void yuv_decode_block(const P* __restrict__ yp, const
         for (int k = 0; k < 4; ++k) {
             const int c0 = 1 + (k >> 1);
             const int nc = (k & 1) ? c0 + 1 : c0 - 1;    // left for the even column, right for the odd
-            const int u = ((9 * cu[1][c0] + 3 * cu[1][nc] + 3 * cu[nr][c0] + cu[nr][nc] + 8) >> 4) - px::mid;
-            const int v = ((9 * cv[1][c0] + 3 * cv[1][nc] + 3 * cv[nr][c0] + cv[nr][nc] + 8) >> 4) - px::mid;
-            const int l = D.cy * (Y[r][k] - D.yo) + (1 << 13);
-            rgb[r][k][0] = yuv_clampv<P>((l + D.rv * v) >> 14);
-            rgb[r][k][1] = yuv_clampv<P>((l + D.gu * u + D.gv * v) >> 14);
-            rgb[r][k][2] = yuv_clampv<P>((l + D.bu * u) >> 14);
+            const int tu[4] = {cu[1][c0], cu[1][nc], cu[nr][c0], cu[nr][nc]};
+            const int tv[4] = {cv[1][c0], cv[1][nc], cv[nr][c0], cv[nr][nc]};
+            yuv_decode_px<P>(D, Y[r][k], tu, tv, rgb[r][k]);
         }
     }
 }
@@ -157,32 +154,6 @@ __global__ void __launch_bounds__(256) rgb_to_yuv420_kernel(const uint8_t* __res
 }
 
 // ---- tiles ---------------------------------------------------------------------------------------------------------
-template <typename T> struct yuv_vec4;
-template <> struct yuv_vec4<float> { typedef float4 type; };
-template <> struct yuv_vec4<bf16_t> { typedef uint2 type; };
-template <> struct yuv_vec4<f16_t> { typedef uint2 type; };
-
-template <typename T> __device__ __forceinline__ typename yuv_vec4<T>::type yuv_pack4(const float* v);
-template <> __device__ __forceinline__ float4 yuv_pack4<float>(const float* v) { return make_float4(v[0], v[1], v[2], v[3]); }
-template <> __device__ __forceinline__ uint2 yuv_pack4<bf16_t>(const float* v) {
-    return make_uint2(pack2<bf16_t>(v[0], v[1]), pack2<bf16_t>(v[2], v[3]));
-}
-template <> __device__ __forceinline__ uint2 yuv_pack4<f16_t>(const float* v) {
-    return make_uint2(pack2<f16_t>(v[0], v[1]), pack2<f16_t>(v[2], v[3]));
-}
-template <typename T> __device__ __forceinline__ void yuv_unpack4(typename yuv_vec4<T>::type p, float* v);
-template <> __device__ __forceinline__ void yuv_unpack4<float>(float4 p, float* v) {
-    v[0] = p.x, v[1] = p.y, v[2] = p.z, v[3] = p.w;
-}
-template <> __device__ __forceinline__ void yuv_unpack4<bf16_t>(uint2 p, float* v) {
-    unpack2<bf16_t>(p.x, v[0], v[1]);
-    unpack2<bf16_t>(p.y, v[2], v[3]);
-}
-template <> __device__ __forceinline__ void yuv_unpack4<f16_t>(uint2 p, float* v) {
-    unpack2<f16_t>(p.x, v[0], v[1]);
-    unpack2<f16_t>(p.y, v[2], v[3]);
-}
-
 // grid: (x: lanes over (h / 2 + 1) * (w / 4 + 1) blocks of the even-aligned superset of the window, y: window).
 // vec_ok: w % 4 == 0 and `out` aligned for 4-element stores (then a window with an even x0 stores whole rows of a block)
 template <typename T, typename P>
@@ -191,7 +162,8 @@ __global__ void __launch_bounds__(256) tile_gather_yuv420_kernel(const P* __rest
                                                                  YuvDec D, const long long* __restrict__ origins, long long h,
                                                                  long long w, T* __restrict__ out, int vec_ok) {
     const long long n = blockIdx.y;
-    const long long y0 = yuv_clampll(origins[2 * n], 0, H - h), x0 = yuv_clampll(origins[2 * n + 1], 0, W - w);
+    const WindowOrigin o0 = window_origin(origins, n, H, W, h, w);
+    const long long y0 = o0.y0, x0 = o0.x0;
     const long long ey0 = y0 & ~1LL, ex0 = x0 & ~1LL;
     const long long G = (w >> 2) + 1;                 // ceil((w + 1) / 4) <= w / 4 + 1 columns of blocks
     const long long R = (h >> 1) + 1;
@@ -216,7 +188,7 @@ __global__ void __launch_bounds__(256) tile_gather_yuv420_kernel(const P* __rest
                 for (int k = 0; k < 4; ++k) v[k] = __fdiv_rn((float)rgb[r][k][c], (float)yuv_px<P>::maxv);
                 T* dst = on + c * plane + wr * w + wx;
                 if (vec) {                              // x0 even and w % 4 == 0: wx % 4 == 0 and the block is whole
-                    *reinterpret_cast<typename yuv_vec4<T>::type*>(dst) = yuv_pack4<T>(v);
+                    *reinterpret_cast<typename vec4<T>::type*>(dst) = pack4<T>(v);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -236,21 +208,8 @@ __global__ void __launch_bounds__(256) tile_scatter_yuv420_kernel(const T* __res
                                                                   long long OH, long long OW, long long max_eh,
                                                                   long long max_ew) {
     const long long n = blockIdx.y;
-    const long long* t = table + 6 * n;
-    long long sy = t[0], sx = t[1], dy = t[2], dx = t[3], eh = t[4], ew = t[5];
-    sy = sy < 0 ? 0 : (sy > sh_ ? sh_ : sy);
-    sx = sx < 0 ? 0 : (sx > sw ? sw : sx);
-    dy = dy < 0 ? 0 : (dy > OH ? OH : dy);
-    dx = dx < 0 ? 0 : (dx > OW ? OW : dx);
-    eh = eh < 0 ? 0 : eh;
-    ew = ew < 0 ? 0 : ew;
-    eh = eh > max_eh ? max_eh : eh;
-    ew = ew > max_ew ? max_ew : ew;
-    eh = eh > sh_ - sy ? sh_ - sy : eh;
-    eh = eh > OH - dy ? OH - dy : eh;
-    ew = ew > sw - sx ? sw - sx : ew;
-    ew = ew > OW - dx ? OW - dx : ew;
-    dy &= ~1LL, dx &= ~1LL, eh &= ~1LL, ew &= ~1LL;      // whole 2 x 2 blocks only: no chroma sample is half-owned
+    const ScatterRow t = scatter_row(table, n, sh_, sw, OH, OW, max_eh, max_ew, true);   // even: whole 2 x 2 blocks only
+    const long long sy = t.sy, sx = t.sx, dy = t.dy, dx = t.dx, eh = t.eh, ew = t.ew;
     const long long G = (max_ew + 3) >> 2;
     const long long plane = sh_ * sw;
     const T* sn = src + n * 3 * plane;
@@ -267,13 +226,13 @@ __global__ void __launch_bounds__(256) tile_scatter_yuv420_kernel(const T* __res
                 const T* s = sn + c * plane + (sy + r0 + r) * sw + sx + c0;
                 float v[4];
                 if (valid == 4 && (reinterpret_cast<uintptr_t>(s) & (4 * sizeof(T) - 1)) == 0) {
-                    yuv_unpack4<T>(*reinterpret_cast<const typename yuv_vec4<T>::type*>(s), v);
+                    unpack4<T>(*reinterpret_cast<const typename vec4<T>::type*>(s), v);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) v[k] = k < valid ? to_float(s[k]) : 0.0f;
                 }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) rgb[r][k][c] = yuv_quant<P>(v[k]);
+                for (int k = 0; k < 4; ++k) rgb[r][k][c] = quant<yuv_px<P>::maxv>(v[k]);
             }
         int Y[2][4], U[2], V[2];
         yuv_encode_block<P>(rgb, E, Y, U, V);
@@ -281,17 +240,12 @@ __global__ void __launch_bounds__(256) tile_scatter_yuv420_kernel(const T* __res
     }
 }
 
-static unsigned yuv_blocks(long long work) {
-    const long long b = cdiv(work, 256);
-    return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
-
 template <typename T, typename P>
 static void yuv_gather(const void* y, const void* u, const void* v, int64_t H, int64_t W, YuvDec D, const int64_t* origins,
                        int64_t n, int64_t h, int64_t w, void* out, hipStream_t st) {
     const size_t al = sizeof(T) == 4 ? 16 : 8;
     const int vec = w % 4 == 0 && reinterpret_cast<uintptr_t>(out) % al == 0;
-    const dim3 grid(yuv_blocks((h / 2 + 1) * (w / 4 + 1)), (unsigned)n);
+    const dim3 grid(grid_blocks((h / 2 + 1) * (w / 4 + 1)), (unsigned)n);
     prof_note((double)n * (double)(h * w) * (1.5 * sizeof(P) + 3.0 * sizeof(T)), 0.0);
     OFASR_LAUNCH((tile_gather_yuv420_kernel<T, P>), grid, dim3(256), 0, st, (const P*)y, (const P*)u, (const P*)v,
                  (long long)H, (long long)W, D, (const long long*)origins, (long long)h, (long long)w, (T*)out, vec);
@@ -300,7 +254,7 @@ static void yuv_gather(const void* y, const void* u, const void* v, int64_t H, i
 template <typename T, typename P>
 static void yuv_scatter(const void* src, int64_t n, int64_t sh, int64_t sw, const int64_t* table, YuvEnc E, void* y, void* u,
                         void* v, int64_t OH, int64_t OW, int64_t max_eh, int64_t max_ew, hipStream_t st) {
-    const dim3 grid(yuv_blocks(cdiv(max_eh, 2) * cdiv(max_ew, 4)), (unsigned)n);
+    const dim3 grid(grid_blocks(cdiv(max_eh, 2) * cdiv(max_ew, 4)), (unsigned)n);
     prof_note((double)n * (double)(max_eh * max_ew) * (1.5 * sizeof(P) + 3.0 * sizeof(T)), 0.0);
     OFASR_LAUNCH((tile_scatter_yuv420_kernel<T, P>), grid, dim3(256), 0, st, (const T*)src, (long long)sh, (long long)sw,
                  (const long long*)table, E, (P*)y, (P*)u, (P*)v, (long long)OH, (long long)OW, (long long)max_eh,
@@ -319,17 +273,12 @@ static int yuv_tile_gather(const char* name, const void* y, const void* u, const
     OFASR_REQUIRE(y && u && v && coeffs && origins && out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
     YUV_REQUIRE_FRAME(H, W);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
-    OFASR_REQUIRE(h <= H && w <= W, OFASR_ERR_INVALID_ARG, "%s: window %lldx%lld larger than the frame %lldx%lld", name,
-                  (long long)h, (long long)w, (long long)H, (long long)W);
-    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
+    TILE_REQUIRE_DTYPE(dtype);
+    TILE_REQUIRE_WINDOWS(n, h, w, H, W, "frame", "too many windows");
     OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
     hipStream_t st = as_stream(stream);
     const YuvDec D = yuv_dec(coeffs);
-    if (dtype == OFASR_F32) yuv_gather<float, P>(y, u, v, H, W, D, origins, n, h, w, out, st);
-    else if (dtype == OFASR_BF16) yuv_gather<bf16_t, P>(y, u, v, H, W, D, origins, n, h, w, out, st);
-    else yuv_gather<f16_t, P>(y, u, v, H, W, D, origins, n, h, w, out, st);
+    dispatch_float(dtype, [&](auto t) { yuv_gather<typename decltype(t)::type, P>(y, u, v, H, W, D, origins, n, h, w, out, st); });
     return check_launch(name);
 }
 
@@ -340,17 +289,16 @@ static int yuv_tile_scatter(const char* name, const void* src, int64_t n, int64_
     OFASR_REQUIRE(src && table && coeffs && y && u && v, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
     YUV_REQUIRE_FRAME(OH, OW);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
+    TILE_REQUIRE_DTYPE(dtype);
     OFASR_REQUIRE(max_eh <= sh && max_ew <= sw, OFASR_ERR_INVALID_ARG, "%s: extent bound larger than the source window",
                   name);
-    OFASR_REQUIRE(n <= 65535, OFASR_ERR_UNSUPPORTED, "%s: too many windows", name);
+    TILE_REQUIRE_COUNT(n, OH, OW, "too many windows");
     OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 10), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
     hipStream_t st = as_stream(stream);
     const YuvEnc E = yuv_enc(coeffs);
-    if (dtype == OFASR_F32) yuv_scatter<float, P>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
-    else if (dtype == OFASR_BF16) yuv_scatter<bf16_t, P>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
-    else yuv_scatter<f16_t, P>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    dispatch_float(dtype, [&](auto t) {
+        yuv_scatter<typename decltype(t)::type, P>(src, n, sh, sw, table, E, y, u, v, OH, OW, max_eh, max_ew, st);
+    });
     return check_launch(name);
 }
 
@@ -361,7 +309,7 @@ OFASR_EXPORT int ofasr_yuv420_to_rgb_u8(const void* y, const void* u, const void
     YUV_REQUIRE_FRAME(H, W);
     OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
     prof_note((double)(H * W) * 4.5, 0.0);
-    OFASR_LAUNCH(yuv420_to_rgb_kernel, dim3(yuv_blocks((H / 2) * cdiv(W, 4))), dim3(256), 0, as_stream(stream),
+    OFASR_LAUNCH(yuv420_to_rgb_kernel, dim3(grid_blocks((H / 2) * cdiv(W, 4))), dim3(256), 0, as_stream(stream),
                  (const uint8_t*)y, (const uint8_t*)u, (const uint8_t*)v, (long long)H, (long long)W, yuv_dec(coeffs),
                  (uint8_t*)rgb_hwc);
     return check_launch(name);
@@ -374,7 +322,7 @@ OFASR_EXPORT int ofasr_rgb_to_yuv420_u8(const void* rgb_hwc, int64_t H, int64_t 
     YUV_REQUIRE_FRAME(H, W);
     OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 10), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
     prof_note((double)(H * W) * 4.5, 0.0);
-    OFASR_LAUNCH(rgb_to_yuv420_kernel, dim3(yuv_blocks((H / 2) * cdiv(W, 4))), dim3(256), 0, as_stream(stream),
+    OFASR_LAUNCH(rgb_to_yuv420_kernel, dim3(grid_blocks((H / 2) * cdiv(W, 4))), dim3(256), 0, as_stream(stream),
                  (const uint8_t*)rgb_hwc, (long long)H, (long long)W, yuv_enc(coeffs), (uint8_t*)y, (uint8_t*)u, (uint8_t*)v);
     return check_launch(name);
 }

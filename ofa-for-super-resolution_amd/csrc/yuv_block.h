@@ -1,9 +1,11 @@
 // yuv_block.h -- what the kernels that read or write planar YUV 4:2:0 frames share: the sample types of a plane,
-// the 14-bit coefficient structs and their checks, the quantisation of network output, and the encode + store of one
-// 2 x 4 pixel block.  yuv.hip (the whole-frame conversions and the tile moves) and resize_scatter.hip (the resampling
-// scatter) include it, so there is one statement of the encode.
+// the 14-bit coefficient structs and their checks, the decode of one pixel from its luma and four chroma taps, and the
+// encode + store of one 2 x 4 pixel block.  yuv.hip (the whole-frame conversions and the tile moves), resize_scatter.hip
+// (the resampling scatter), augment.hip (the training gather) and reuse.hip (the frame checks) include it, so there is
+// one statement of the decode and one of the encode.  The table rules and quant<MAXV> are tile_table.h's.
 #pragma once
-#include "ofasr_common.h"
+#include "tile_table.h"
+#include <initializer_list>
 
 namespace ofasr {
 
@@ -40,7 +42,18 @@ template <> struct yuv_px<uint16_t> {
 };
 
 template <typename P> __device__ __forceinline__ int yuv_clampv(int v) { return v < 0 ? 0 : (v > yuv_px<P>::maxv ? yuv_px<P>::maxv : v); }
-__device__ __forceinline__ long long yuv_clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// RGB of one pixel from its luma sample and the four chroma taps of each plane in 9-3-3-1 order: the sample the pixel lies
+// in, its neighbour in the row, its neighbour in the column, the diagonal one (yuv.hip's header states the siting)
+template <typename P>
+__device__ __forceinline__ void yuv_decode_px(const YuvDec& D, int Y, const int (&U)[4], const int (&V)[4], int (&rgb)[3]) {
+    const int u = ((9 * U[0] + 3 * U[1] + 3 * U[2] + U[3] + 8) >> 4) - yuv_px<P>::mid;
+    const int v = ((9 * V[0] + 3 * V[1] + 3 * V[2] + V[3] + 8) >> 4) - yuv_px<P>::mid;
+    const int l = D.cy * (Y - D.yo) + (1 << 13);
+    rgb[0] = yuv_clampv<P>((l + D.rv * v) >> 14);
+    rgb[1] = yuv_clampv<P>((l + D.gu * u + D.gv * v) >> 14);
+    rgb[2] = yuv_clampv<P>((l + D.bu * u) >> 14);
+}
 
 // luma of the 2 x 4 block rgb (columns < valid, valid = 2 or 4) and its one or two chroma pairs
 template <typename P>
@@ -98,9 +111,11 @@ __device__ __forceinline__ void yuv_store_block(P* __restrict__ yp, P* __restric
     }
 }
 
-template <typename P> __device__ __forceinline__ int yuv_quant(float v) {
-    const float f = fminf(fmaxf(v, 0.0f), 1.0f);
-    return (int)rintf(__fmul_rn(f, (float)yuv_px<P>::maxv));
+// the plane pointers of a 16-bit frame are aligned for their samples
+inline bool yuv_planes_aligned2(std::initializer_list<const void*> planes) {
+    uintptr_t bits = 0;
+    for (const void* p : planes) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 1) == 0;
 }
 
 static YuvDec yuv_dec(const int32_t* c) { return YuvDec{c[0], c[1], c[2], c[3], c[4], c[5]}; }
@@ -121,10 +136,10 @@ static bool yuv_coeffs_ok(const int32_t* c, int n) {
     OFASR_REQUIRE((H) >= 2 && (W) >= 2, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);                          \
     OFASR_REQUIRE((H) % 2 == 0 && (W) % 2 == 0, OFASR_ERR_INVALID_ARG, "%s: a 4:2:0 frame needs even sides, got %lldx%lld", \
                   name, (long long)(H), (long long)(W));                                                                 \
-    OFASR_REQUIRE((H) <= (1LL << 40) / (W), OFASR_ERR_UNSUPPORTED, "%s: too large a frame", name)
+    TILE_REQUIRE_FRAME_CAP(H, W)
 
-// 16-bit planes: the one depth this library defines, and plane pointers aligned for their samples
-#define YUV_REQUIRE_P16(depth, y, u, v)                                                                                  \
+// 16-bit planes: the one depth this library defines, and plane pointers (any number) aligned for their samples
+#define YUV_REQUIRE_P16(depth, ...)                                                                                      \
     OFASR_REQUIRE((depth) == 10, OFASR_ERR_INVALID_ARG, "%s: depth %d is not supported (10 only)", name, (int)(depth));  \
-    OFASR_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(v)) & 1) == 0, \
-                  OFASR_ERR_INVALID_ARG, "%s: a 16-bit plane pointer is not 2-byte aligned", name)
+    OFASR_REQUIRE(ofasr::yuv_planes_aligned2({__VA_ARGS__}), OFASR_ERR_INVALID_ARG,                                      \
+                  "%s: a 16-bit plane pointer is not 2-byte aligned", name)

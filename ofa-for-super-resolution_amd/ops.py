@@ -221,25 +221,31 @@ def _unit_lut(device):
 
 
 # ------------------------------------------------------------- training augmentation on resident images
+def _aug_gather(name, pool, table, n, S, extra, want_f32):
+    """what aug_gather_u8 and aug_gather_yuv420 share: the checks of pool and table, the outputs and the call of
+    ofasr_<name>, whose arguments between S and the outputs are `extra`"""
+    _gpu(pool, table)
+    n, S = int(n), int(S)
+    if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
+        raise _C.OfasrError("%s: pool is a contiguous 1-D uint8 tensor, got %s %s" % (name, pool.dtype, tuple(pool.shape)))
+    if table.dtype != torch.int64 or table.dim() != 2 or table.size(1) != 12 or table.size(0) < n or \
+            not table.is_contiguous() or table.device != pool.device:
+        raise _C.OfasrError("%s: table is a contiguous int64 [>= %d, 12] tensor on %s, got %s %s on %s"
+                            % (name, n, pool.device, table.dtype, tuple(table.shape), table.device))
+    out = torch.empty((max(n, 0), 3, max(S, 0), max(S, 0)), dtype=torch.uint8, device=pool.device)
+    f32 = torch.empty(out.shape, dtype=torch.float32, device=pool.device) if want_f32 else None
+    with _timed(name, out.numel() * (6 if want_f32 else 2)):
+        _C.check(getattr(_C.lib(), "ofasr_" + name)(*((_p(pool), pool.numel(), _p(table), n, S) + extra +
+                                                      (_p(out), _p(f32) if want_f32 else None, _stream()))), name)
+    return (out, f32) if want_f32 else out
+
+
 def aug_gather_u8(pool, table, n, S, want_f32=False):
     """The augmented HR batch [n, 3, S, S] (uint8; with `want_f32` the pair (uint8, float32 = u8 / 255)) gathered from a
     resident uint8 image pool: crop -> horizontal flip -> nearest rotation with zero fill per row of the int64 [n, 12]
     device table (offset, H, W, i, j, flip, a0 .. a5), bit-equal to the PIL transforms of div2k_setxx.py
     (ofasr_aug_gather_u8, csrc/augment.hip; the table is made by data_providers/augment.make_table)."""
-    _gpu(pool, table)
-    n, S = int(n), int(S)
-    if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
-        raise _C.OfasrError("aug_gather_u8: pool is a contiguous 1-D uint8 tensor, got %s %s" % (pool.dtype, tuple(pool.shape)))
-    if table.dtype != torch.int64 or table.dim() != 2 or table.size(1) != 12 or table.size(0) < n or \
-            not table.is_contiguous() or table.device != pool.device:
-        raise _C.OfasrError("aug_gather_u8: table is a contiguous int64 [>= %d, 12] tensor on %s, got %s %s on %s"
-                            % (n, pool.device, table.dtype, tuple(table.shape), table.device))
-    out = torch.empty((max(n, 0), 3, max(S, 0), max(S, 0)), dtype=torch.uint8, device=pool.device)
-    f32 = torch.empty(out.shape, dtype=torch.float32, device=pool.device) if want_f32 else None
-    with _timed("aug_gather_u8", out.numel() * (6 if want_f32 else 2)):
-        _C.check(_C.lib().ofasr_aug_gather_u8(_p(pool), pool.numel(), _p(table), n, S, _p(out),
-                                              _p(f32) if want_f32 else None, _stream()), "aug_gather_u8")
-    return (out, f32) if want_f32 else out
+    return _aug_gather("aug_gather_u8", pool, table, n, S, (), want_f32)
 
 
 def aug_gather_yuv420(pool, table, n, S, matrix="bt601", full_range=False, want_f32=False):
@@ -247,22 +253,7 @@ def aug_gather_yuv420(pool, table, n, S, matrix="bt601", full_range=False, want_
     [H/2, W/2], contiguous; the table's offset is the Y plane's byte offset): the batch that aug_gather_u8 gives on
     yuv420_to_rgb_u8 of every frame, byte for byte, with no RGB frame anywhere (ofasr_aug_gather_yuv420,
     csrc/augment.hip; the definition is data_providers/augment.gather_yuv420_np)."""
-    _gpu(pool, table)
-    n, S = int(n), int(S)
-    if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
-        raise _C.OfasrError("aug_gather_yuv420: pool is a contiguous 1-D uint8 tensor, got %s %s"
-                            % (pool.dtype, tuple(pool.shape)))
-    if table.dtype != torch.int64 or table.dim() != 2 or table.size(1) != 12 or table.size(0) < n or \
-            not table.is_contiguous() or table.device != pool.device:
-        raise _C.OfasrError("aug_gather_yuv420: table is a contiguous int64 [>= %d, 12] tensor on %s, got %s %s on %s"
-                            % (n, pool.device, table.dtype, tuple(table.shape), table.device))
-    out = torch.empty((max(n, 0), 3, max(S, 0), max(S, 0)), dtype=torch.uint8, device=pool.device)
-    f32 = torch.empty(out.shape, dtype=torch.float32, device=pool.device) if want_f32 else None
-    with _timed("aug_gather_yuv420", out.numel() * (6 if want_f32 else 2)):
-        _C.check(_C.lib().ofasr_aug_gather_yuv420(_p(pool), pool.numel(), _p(table), n, S,
-                                                  yuv_table(matrix, full_range, False), _p(out),
-                                                  _p(f32) if want_f32 else None, _stream()), "aug_gather_yuv420")
-    return (out, f32) if want_f32 else out
+    return _aug_gather("aug_gather_yuv420", pool, table, n, S, (yuv_table(matrix, full_range, False),), want_f32)
 
 
 # ------------------------------------------------------------------------------ Y-PSNR / Y-SSIM on the GPU

@@ -374,15 +374,39 @@ def default_core(halo, align, px_elems):
 
 
 # ---------------------------------------------------------------------------------------------- kernels
+def _origin_table(origins, name, shaped=True):
+    """the window count of an int64 origin table on the GPU; `shaped`: its [n, 2] shape is part of the caller's contract"""
+    bad = origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous()
+    if shaped:
+        bad = bad or origins.dim() != 2 or origins.size(1) != 2
+    if bad:
+        raise ValueError("%s needs a contiguous int64 origin table%s on the GPU" % (name, " [n, 2]" if shaped else ""))
+    return origins.size(0)
+
+
+def _scatter_table(table, src, name, shaped=False):
+    """the checks of a scatter table against its source batch; `shaped`: [n, 6] with n >= 1 is part of the contract"""
+    bad = table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.size(0) > src.size(0)
+    if shaped:
+        bad = bad or table.dim() != 2 or table.size(1) != 6 or table.size(0) < 1
+    if bad:
+        raise ValueError("%s needs a contiguous int64 table%s on the GPU, one row per source window at most"
+                         % (name, " [n, 6]" if shaped else ""))
+
+
+def _call_depth(base, depth, head, tail):
+    """the 8-bit entry point `base` as it is, or its 16-bit twin `base`p16 with `depth` between head and tail"""
+    name = base if depth == 8 else base + "p16"
+    _C.check(getattr(_C.lib(), name)(*(head + (() if depth == 8 else (depth,)) + tail)), name)
+
+
 def tile_gather(img, origins, h, w, dtype, out=None):
     """img: HWC uint8 [H, W, 3] on the GPU; origins: int64 [n, 2] (y0, x0) on the GPU -> [n, 3, h, w] of dtype,
     u8 / 255 (fp32) then cast (ofasr_tile_gather_u8)"""
     ops._gpu(img)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.size(2) != 3 or not img.is_contiguous():
         raise ValueError("tile_gather needs a contiguous HWC uint8 RGB image")
-    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous():
-        raise ValueError("tile_gather needs a contiguous int64 origin table on the GPU")
-    n = origins.size(0)
+    n = _origin_table(origins, "tile_gather", shaped=False)
     if out is None:
         out = torch.empty(n, 3, h, w, dtype=dtype, device=img.device)
     _C.check(_C.lib().ofasr_tile_gather_u8(img.data_ptr(), img.size(0), img.size(1), origins.data_ptr(), n, h, w,
@@ -398,8 +422,7 @@ def tile_scatter(src, table, img, max_eh, max_ew):
         raise ValueError("tile_scatter needs a contiguous [n, 3, h, w] source")
     if img.dtype != torch.uint8 or img.dim() != 3 or img.size(2) != 3 or not img.is_contiguous():
         raise ValueError("tile_scatter needs a contiguous HWC uint8 RGB destination")
-    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.size(0) > src.size(0):
-        raise ValueError("tile_scatter needs a contiguous int64 table on the GPU, one row per source window at most")
+    _scatter_table(table, src, "tile_scatter")
     _C.check(_C.lib().ofasr_tile_scatter_u8(src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype],
                                             table.data_ptr(), img.data_ptr(), img.size(0), img.size(1), max_eh, max_ew,
                                             ops._stream()), "ofasr_tile_scatter_u8")
@@ -412,21 +435,13 @@ def tile_gather_yuv420(y, u, v, origins, h, w, dtype, matrix="bt601", full_range
     -- tile_gather(ops.yuv420_to_rgb_u8(y, u, v)) bit for bit without the RGB frame (ofasr_tile_gather_yuv420).  uint16
     planes are a 10-bit frame: the decode of depth 10, / 1023 (ofasr_tile_gather_yuv420p16)."""
     H, W = ops.yuv420_planes(y, u, v, "tile_gather_yuv420")
-    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous():
-        raise ValueError("tile_gather_yuv420 needs a contiguous int64 origin table on the GPU")
-    n = origins.size(0)
+    n = _origin_table(origins, "tile_gather_yuv420", shaped=False)
     if out is None:
         out = torch.empty(n, 3, h, w, dtype=dtype, device=y.device)
     depth = ops.YUV_DEPTHS[y.dtype]
     coeffs = ops.yuv_table(matrix, full_range, False, depth)
-    if depth == 8:
-        _C.check(_C.lib().ofasr_tile_gather_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W, coeffs,
-                                                   origins.data_ptr(), n, h, w, out.data_ptr(), _CODES[out.dtype],
-                                                   ops._stream()), "ofasr_tile_gather_yuv420")
-    else:
-        _C.check(_C.lib().ofasr_tile_gather_yuv420p16(y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W, depth, coeffs,
-                                                      origins.data_ptr(), n, h, w, out.data_ptr(), _CODES[out.dtype],
-                                                      ops._stream()), "ofasr_tile_gather_yuv420p16")
+    _call_depth("ofasr_tile_gather_yuv420", depth, (y.data_ptr(), u.data_ptr(), v.data_ptr(), H, W),
+                (coeffs, origins.data_ptr(), n, h, w, out.data_ptr(), _CODES[out.dtype], ops._stream()))
     return out
 
 
@@ -439,20 +454,12 @@ def tile_scatter_yuv420(src, table, y, u, v, max_eh, max_ew, matrix="bt601", ful
     if not src.is_contiguous() or src.dim() != 4 or src.size(1) != 3:
         raise ValueError("tile_scatter_yuv420 needs a contiguous [n, 3, h, w] source")
     OH, OW = ops.yuv420_planes(y, u, v, "tile_scatter_yuv420")
-    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.size(0) > src.size(0):
-        raise ValueError("tile_scatter_yuv420 needs a contiguous int64 table on the GPU, one row per source window at most")
+    _scatter_table(table, src, "tile_scatter_yuv420")
     depth = ops.YUV_DEPTHS[y.dtype]
     coeffs = ops.yuv_table(matrix, full_range, True, depth)
-    if depth == 8:
-        _C.check(_C.lib().ofasr_tile_scatter_yuv420(src.data_ptr(), table.size(0), src.size(2), src.size(3),
-                                                    _CODES[src.dtype], table.data_ptr(), coeffs, y.data_ptr(), u.data_ptr(),
-                                                    v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()),
-                 "ofasr_tile_scatter_yuv420")
-    else:
-        _C.check(_C.lib().ofasr_tile_scatter_yuv420p16(src.data_ptr(), table.size(0), src.size(2), src.size(3),
-                                                       _CODES[src.dtype], table.data_ptr(), depth, coeffs, y.data_ptr(),
-                                                       u.data_ptr(), v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()),
-                 "ofasr_tile_scatter_yuv420p16")
+    _call_depth("ofasr_tile_scatter_yuv420", depth,
+                (src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype], table.data_ptr()),
+                (coeffs, y.data_ptr(), u.data_ptr(), v.data_ptr(), OH, OW, max_eh, max_ew, ops._stream()))
     return y, u, v
 
 
@@ -460,9 +467,7 @@ def _resize_args(name, src, table, vtab, htab, TH, TW):
     ops._gpu(src)
     if not src.is_contiguous() or src.dim() != 4 or src.size(1) != 3:
         raise ValueError("%s needs a contiguous [n, 3, h, w] source" % name)
-    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2 or \
-            table.size(1) != 6 or table.size(0) > src.size(0) or table.size(0) < 1:
-        raise ValueError("%s needs a contiguous int64 table [n, 6] on the GPU, one row per source window at most" % name)
+    _scatter_table(table, src, name, shaped=True)
     for t, rows, what in ((vtab, TH, "vertical"), (htab, TW, "horizontal")):
         if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.size(0) != rows or \
                 not 3 <= t.size(1) <= 2 + resize.MAX_TAPS:
@@ -497,10 +502,7 @@ def tile_resize_scatter_yuv420(src, table, vtab, htab, y, u, v, max_eh, max_ew, 
     head = (src.data_ptr(), table.size(0), src.size(2), src.size(3), _CODES[src.dtype], table.data_ptr(), vtab.data_ptr(),
             vtab.size(1) - 2, htab.data_ptr(), htab.size(1) - 2)
     tail = (coeffs, y.data_ptr(), u.data_ptr(), v.data_ptr(), TH, TW, max_eh, max_ew, ops._stream())
-    if depth == 8:
-        _C.check(_C.lib().ofasr_tile_resize_scatter_yuv420(*(head + tail)), "ofasr_tile_resize_scatter_yuv420")
-    else:
-        _C.check(_C.lib().ofasr_tile_resize_scatter_yuv420p16(*(head + (depth,) + tail)), "ofasr_tile_resize_scatter_yuv420p16")
+    _call_depth("ofasr_tile_resize_scatter_yuv420", depth, head, tail)
     return y, u, v
 
 
@@ -517,24 +519,15 @@ def window_diff_yuv420(y, u, v, py, pu, pv, origins, h, w, flags=None):
     H, W = ops.yuv420_planes(y, u, v, "window_diff_yuv420")
     if ops.yuv420_planes(py, pu, pv, "window_diff_yuv420") != (H, W) or py.dtype != y.dtype:
         raise ValueError("window_diff_yuv420 needs two frames of one size and dtype")
-    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous() or origins.dim() != 2 \
-            or origins.size(1) != 2:
-        raise ValueError("window_diff_yuv420 needs a contiguous int64 origin table [n, 2] on the GPU")
-    n = origins.size(0)
+    n = _origin_table(origins, "window_diff_yuv420")
     S = window_diff_slabs(h, w)
     if flags is None:
         flags = torch.empty(n, max(S, 1), dtype=torch.int32, device=y.device)
     elif flags.dtype != torch.int32 or not flags.is_cuda or not flags.is_contiguous() or flags.numel() != n * S:
         raise ValueError("window_diff_yuv420 needs contiguous int32 flags [n, %d] on the GPU" % S)
-    depth = ops.YUV_DEPTHS[y.dtype]
-    if depth == 8:
-        _C.check(_C.lib().ofasr_window_diff_yuv420(y.data_ptr(), u.data_ptr(), v.data_ptr(), py.data_ptr(), pu.data_ptr(),
-                                                   pv.data_ptr(), H, W, origins.data_ptr(), n, h, w, flags.data_ptr(),
-                                                   ops._stream()), "ofasr_window_diff_yuv420")
-    else:
-        _C.check(_C.lib().ofasr_window_diff_yuv420p16(y.data_ptr(), u.data_ptr(), v.data_ptr(), py.data_ptr(), pu.data_ptr(),
-                                                      pv.data_ptr(), H, W, depth, origins.data_ptr(), n, h, w,
-                                                      flags.data_ptr(), ops._stream()), "ofasr_window_diff_yuv420p16")
+    _call_depth("ofasr_window_diff_yuv420", ops.YUV_DEPTHS[y.dtype],
+                (y.data_ptr(), u.data_ptr(), v.data_ptr(), py.data_ptr(), pu.data_ptr(), pv.data_ptr(), H, W),
+                (origins.data_ptr(), n, h, w, flags.data_ptr(), ops._stream()))
     return flags
 
 
@@ -573,13 +566,6 @@ def window_compact(flags, origins, table, batch, out=None):
 def window_activity_slabs(h, w):
     """row slabs per window of window_activity's partial table (ofasr_window_activity_slabs; host only)"""
     return int(_C.lib().ofasr_window_activity_slabs(h, w))
-
-
-def _origin_table(origins, name):
-    if origins.dtype != torch.int64 or not origins.is_cuda or not origins.is_contiguous() or origins.dim() != 2 \
-            or origins.size(1) != 2:
-        raise ValueError("%s needs a contiguous int64 origin table [n, 2] on the GPU" % name)
-    return origins.size(0)
 
 
 def window_activity(src, origins, h, w, partial=None):

@@ -12,6 +12,8 @@ import pytest
 import torch
 
 from conftest import ROOT, amd
+from placed import check, place
+from test_hip_video_reuse import WILD
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -40,6 +42,7 @@ def test_gather_matches_to_tensor(dtype, pad, h, w):
     origins = [(0, 0), (H - h, W - w), (H - h, 0), (0, W - w)]
     for _ in range(6):
         origins.append((int(torch.randint(0, H - h + 1, (1,), generator=g)), int(torch.randint(0, W - w + 1, (1,), generator=g))))
+    origins += WILD                        # the kernel clamps an origin into [0, H - h] x [0, W - w]
     table = torch.tensor(origins, dtype=torch.int64, device=DEV)
     out = up.tile_gather(img, table, h, w, dtype)
     torch.cuda.synchronize()
@@ -48,6 +51,7 @@ def test_gather_matches_to_tensor(dtype, pad, h, w):
     # GPU kernel multiplies by the rounded reciprocal instead, which differs in the last bit for about half the values)
     host, out = img.cpu(), out.cpu()
     for i, (y, x) in enumerate(origins):
+        y, x = min(max(y, 0), H - h), min(max(x, 0), W - w)
         ref = (host[y:y + h, x:x + w].permute(2, 0, 1).float() / 255).to(dtype)
         assert torch.equal(out[i], ref), (i, y, x)
 
@@ -95,6 +99,72 @@ def test_scatter_64bit_addressing():
     ref = torch.full((40, OW, 3), 7, dtype=torch.uint8)
     ref[23:, OW - 25:] = (src[0, :, 2:19, 3:28].clamp(0, 1) * 255.0).round().to(torch.uint8).permute(1, 2, 0).cpu()
     assert torch.equal(got, ref)
+
+
+# table rows no planner makes: every column far outside its range, up to the ends of int64
+WILD_ROWS = [[-2 ** 40, 2 ** 40, -5, -5, 10 ** 12, 10 ** 12],
+             [2 ** 62, -2 ** 62, 30, 40, 30, 40],
+             [3, 5, 39, 55, 7, 9],
+             [-2 ** 63, 2 ** 63 - 1, 2 ** 63 - 1, -2 ** 63, 2 ** 63 - 1, 2 ** 63 - 1]]
+# one row whose clamped extent is non-empty and odd in every destination column: 7 x 9 at (31, 41), which a 4:2:0
+# destination turns into 6 x 8 at (30, 40)
+ODD_ROWS = [[3, 5, 31, 41, 7, 9]]
+
+
+def _clamped_row(row, sh, sw, OH, OW, max_eh, max_ew, even):
+    """the rule of the scatter kernels (csrc/tile_table.h, scatter_row), restated: offsets into [0, side], the extent
+    non-negative, at most the launch's bound and at most what is left of the source window and of the destination behind
+    the offsets; for a 4:2:0 destination dy, dx, eh, ew then lose their low bit"""
+    sy, sx, dy, dx, eh, ew = row
+    sy, sx = min(max(sy, 0), sh), min(max(sx, 0), sw)
+    dy, dx = min(max(dy, 0), OH), min(max(dx, 0), OW)
+    eh = min(max(eh, 0), max_eh, sh - sy, OH - dy)
+    ew = min(max(ew, 0), max_ew, sw - sx, OW - dx)
+    if even:
+        dy, dx, eh, ew = (t - t % 2 for t in (dy, dx, eh, ew))
+    return [sy, sx, dy, dx, eh, ew]
+
+
+@pytest.mark.parametrize("lead", [0, 4])
+@pytest.mark.parametrize("rows", [WILD_ROWS, ODD_ROWS], ids=["wild", "odd"])
+@pytest.mark.parametrize("kind", ["rgb8", "yuv8", "yuv16"])
+def test_scatter_clamps_wild_rows(kind, rows, lead):
+    """ofasr_tile_scatter_u8 / ofasr_tile_scatter_yuv420 (uint8 and uint16 planes) on WILD_ROWS and on ODD_ROWS, source and
+    destination between guard bands: the destination is what the same scatter gives on the clamped rows, and no guard
+    byte changes"""
+    up = amd("upscale")
+    g = torch.Generator().manual_seed(11)
+    rng = np.random.RandomState(11)
+    n, sh, sw, OH, OW, max_eh, max_ew = 4, 20, 28, 40, 56, 16, 24
+    vals = (torch.rand(n, 3, sh, sw, generator=g) * 1.4 - 0.2).to(DEV)
+    src = place(vals, lead, "in", "src")                 # lead 4: no 16-byte source load is legal
+    dt, top = (np.uint16, 1024) if kind == "yuv16" else (np.uint8, 256)
+    shapes = [(OH, OW, 3)] if kind == "rgb8" else [(OH, OW), (OH // 2, OW // 2), (OH // 2, OW // 2)]
+    base = [torch.from_numpy(rng.randint(0, top, s).astype(dt)).to(DEV) for s in shapes]   # uint16: made and copied only
+    dst = [place(b, lead // 2, "out", "dst%d" % i) for i, b in enumerate(base)]   # lead 2: no dword store is legal
+    for d, b in zip(dst, base):
+        d.copy_(b)
+    tame = [_clamped_row(r, sh, sw, OH, OW, max_eh, max_ew, kind != "rgb8") for r in rows]
+    if rows is WILD_ROWS:
+        assert tame[2] == ([3, 5, 39, 55, 1, 1] if kind == "rgb8" else [3, 5, 38, 54, 0, 0])
+    else:
+        assert tame == ([[3, 5, 31, 41, 7, 9]] if kind == "rgb8" else [[3, 5, 30, 40, 6, 8]])
+    wild = torch.tensor(rows, dtype=torch.int64, device=DEV)
+    if kind == "rgb8":
+        up.tile_scatter(src, wild, dst[0], max_eh, max_ew)
+        exp = [base[0].clone()]
+        for i, (sy, sx, dy, dx, eh, ew) in enumerate(tame):
+            v = vals[i, :, sy:sy + eh, sx:sx + ew].clamp(0, 1) * 255.0
+            exp[0][dy:dy + eh, dx:dx + ew] = v.round().to(torch.uint8).permute(1, 2, 0)
+    else:
+        up.tile_scatter_yuv420(src, wild, dst[0], dst[1], dst[2], max_eh, max_ew)
+        exp = [b.clone() for b in base]
+        up.tile_scatter_yuv420(vals, torch.tensor(tame, dtype=torch.int64, device=DEV), exp[0], exp[1], exp[2], max_eh, max_ew)
+    torch.cuda.synchronize()
+    for d, e in zip(dst, exp):
+        assert np.array_equal(d.cpu().numpy(), e.cpu().numpy())
+        check(d)
+    check(src)
 
 
 # ---------------------------------------------------------------------------------------------- networks
