@@ -716,6 +716,25 @@ int ofasr_aug_gather_u8(const void* pool, int64_t pool_bytes, const int64_t* tab
 int ofasr_aug_gather_yuv420(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S,
                             const int32_t* coeffs, void* out_u8, void* out_f32, void* stream);
 
+/* A paired sample: the HR crop and the LR crop of one draw, from two pools, in ONE launch.  hr_pool holds the frames of
+ * the source video and lr_pool the frames of its decoded low-resolution stream (sides 1/f of the source's), both laid
+ * out as above.  Each side is exactly ofasr_aug_gather_yuv420 of its own pool and table block: the decode of its own
+ * whole frame, the clamps against its own pool's size (host statement: augment.gather_yuv420_pair_np /
+ * apply_pair_params_np).
+ *   table:   device int64 [2][n][12]: block 0 the HR rows for crop side S, block 1 the LR rows for crop side S / f; a
+ *            row's offset is relative to its own pool and its a0 .. a5 are rotate_coeffs(angle, its own side).  The
+ *            host draws (i, j, flip, angle) on the LR grid and gives HR (f*i, f*j, flip, angle) (augment.make_pair_table).
+ *   coeffs:  one decode table for both sides.
+ *   hr_u8:   [n, 3, S, S] uint8.   lr_u8: [n, 3, S/f, S/f] uint8.   hr_f32 / lr_f32: both NULL, or both the same
+ *            batches as fp32, (float)v / 255.0f correctly rounded.
+ * OFASR_ERR_INVALID_ARG: a null pool, table, coeffs or uint8 output; exactly one fp32 output; a non-positive size;
+ * S % f != 0; a coefficient outside the 14-bit tables' range.  OFASR_ERR_UNSUPPORTED: f not 2 or 4; S > 4096;
+ * n > 65535; hr_bytes below Se*Se*3/2 or lr_bytes below se*se*3/2 (Se, se = S, S/f rounded up to even: no frame of the
+ * crop's size fits).  Nothing is launched in either case.  Plain loads and stores, no atomics. */
+int ofasr_aug_gather_yuv420_pair(const void* hr_pool, int64_t hr_bytes, const void* lr_pool, int64_t lr_bytes,
+                                 const int64_t* table, int64_t n, int64_t S, int64_t f, const int32_t* coeffs,
+                                 void* hr_u8, void* hr_f32, void* lr_u8, void* lr_f32, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Y-channel quality metrics: exact SSE (for Y-PSNR) and mean SSIM of two image batches, per image  -- replaces the host
  * round trip of the reference's logged metric (sr_run_manager.py:567-597: tensor2img -> rgb2y -> psnr on numpy arrays)

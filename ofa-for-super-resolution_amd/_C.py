@@ -159,6 +159,8 @@ SIGNATURES = {
     "ofasr_add": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp]),
     "ofasr_aug_gather_u8": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
     "ofasr_aug_gather_yuv420": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "ofasr_aug_gather_yuv420_pair": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp,
+                                              _c_vp, _c_vp, _c_vp]),
     "ofasr_quality_y_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "ofasr_quality_y": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_sz,
                                  _c_vp]),

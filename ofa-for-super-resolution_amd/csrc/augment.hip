@@ -1,5 +1,6 @@
 // augment.hip -- the training augmentation on GPU-resident images (ofasr_aug_gather_u8) and on GPU-resident planar
-// YUV 4:2:0 video frames with the colour decode fused in (ofasr_aug_gather_yuv420, stated before its kernel below).
+// YUV 4:2:0 video frames with the colour decode fused in (ofasr_aug_gather_yuv420, stated before its kernel below; the
+// HR / LR pair of one draw in one launch: ofasr_aug_gather_yuv420_pair, stated before its kernel).
 //
 // The DIV2K training sample is RandomCrop(S) -> RandomHorizontalFlip -> RandomRotation((-90, 90)) of a decoded RGB image
 // (data_providers/div2k_setxx.py).  With the decoded images resident in one uint8 pool, the three transforms are one
@@ -56,12 +57,13 @@ __device__ __forceinline__ AugRow aug_row(const long long* __restrict__ table, l
 }
 
 // the lane's group of 4 output columns (y, x0 .. x0 + 3) and the fixed-point walk at its first column; false for whole
-// lanes past the end of the plane, which leave before any address is formed
+// lanes past the end of the plane, which leave before any address is formed.  `e` is the lane's group index inside the
+// sample: blockIdx.x * blockDim.x + threadIdx.x in the one-batch kernels, counted from its segment's first block in the
+// pair kernel
 struct AugWalk { int y, x0; uint32_t fx, fy; };
-__device__ __forceinline__ bool aug_walk_start(const AugRow& r, int S, AugWalk& w) {
+__device__ __forceinline__ bool aug_walk_start(const AugRow& r, int S, int e, AugWalk& w) {
     const int gw = (S + 3) >> 2;
     const int total = S * gw;
-    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (e >= total) return false;
     w.y = e / gw;
     w.x0 = (e - w.y * gw) * 4;
@@ -124,7 +126,7 @@ __global__ void __launch_bounds__(256) aug_gather_u8_kernel(const uint8_t* __res
     const AugRow R = aug_row(table, n, S, pool_bytes, false);
     const long long last = pool_bytes - 3;
     AugWalk wk;
-    if (!aug_walk_start(R, S, wk)) return;   // nothing below branches around a load
+    if (!aug_walk_start(R, S, (int)(blockIdx.x * blockDim.x + threadIdx.x), wk)) return;   // nothing below branches around a load
     uint32_t v[4][3];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -167,18 +169,20 @@ __device__ __forceinline__ int aug_tap(int p, int last) {      // the neighbour 
     return nb < 0 ? 0 : (nb > last ? last : nb);
 }
 
+// the body of the 4:2:0 gathers: sample n's group e (aug_walk_start) of the S x S crop that row n of `table` cuts from
+// `pool`, into out_u8 / out_f32.  Shared by aug_gather_yuv420_kernel and the two segments of the pair kernel below.
 template <bool VEC, bool F32>
-__global__ void __launch_bounds__(256) aug_gather_yuv420_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
-                                                                const long long* __restrict__ table, int S, YuvDec D,
-                                                                uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
-    const long long n = blockIdx.y;
+__device__ __forceinline__ void aug_yuv420_body(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                const long long* __restrict__ table, long long n, int S, int e,
+                                                const YuvDec& D, uint8_t* __restrict__ out_u8,
+                                                float* __restrict__ out_f32) {
     const AugRow R = aug_row(table, n, S, pool_bytes, true);
     const long long last = pool_bytes - 1;
     const long long CW = R.W >> 1;
     const int chl = (int)(R.H >> 1) - 1, cwl = (int)CW - 1;    // H, W <= 2^24: frame coordinates fit int32
     const long long ub = R.off + R.H * R.W, vb = ub + (R.H >> 1) * CW;
     AugWalk wk;
-    if (!aug_walk_start(R, S, wk)) return;   // nothing below branches around a load
+    if (!aug_walk_start(R, S, e, wk)) return;   // nothing below branches around a load
     int Y[4], U[4][4], V[4][4];
     bool ok[4];
 #pragma unroll
@@ -208,6 +212,69 @@ __global__ void __launch_bounds__(256) aug_gather_yuv420_kernel(const uint8_t* _
         for (int c = 0; c < 3; ++c) v[k][c] = ok[k] ? (uint32_t)rgb[c] : 0u;   // the zero fill, selected after the decode
     }
     aug_store4<VEC, F32>(v, n, S, wk.y, wk.x0, out_u8, out_f32);
+}
+
+// grid: (x: lanes over S * ceil(S / 4) groups, y: sample)
+template <bool VEC, bool F32>
+__global__ void __launch_bounds__(256) aug_gather_yuv420_kernel(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                                const long long* __restrict__ table, int S, YuvDec D,
+                                                                uint8_t* __restrict__ out_u8, float* __restrict__ out_f32) {
+    aug_yuv420_body<VEC, F32>(pool, pool_bytes, table, blockIdx.y, S, (int)(blockIdx.x * blockDim.x + threadIdx.x), D,
+                              out_u8, out_f32);
+}
+
+// ---- a paired sample: the HR crop and the LR crop of one draw in ONE launch (ofasr_aug_gather_yuv420_pair) -----------
+// Two pools of 4:2:0 frames, HR and LR (the decoded low-resolution stream of the same video, sides 1/f of HR's), and a
+// table of two blocks [2][n][12]: block 0 the HR rows (crop side S), block 1 the LR rows (crop side S / f), each row in
+// the layout above with its offset relative to its own pool and a0 .. a5 for its own canvas.  Each side is exactly
+// aug_gather_yuv420 of its pool and its table block: the decode of its own whole frame, chroma parity and edge
+// replication its own frame's, the same clamps against its own pool's size.  The host draws one (i, j, flip, angle) on
+// the LR grid and hands HR (f*i, f*j, flip, angle) (augment.draw_pair_params, make_pair_table).
+//
+// grid: (x: hr_blocks = ceil(S * ceil(S / 4) / 256) blocks of HR lanes, then the blocks of LR lanes; y: sample).  Which
+// side a block serves depends on blockIdx.x alone, so the branch is uniform over the block and no wave diverges; each
+// side then runs the body above with its own operands.  VEC is chosen per side (S = 24, f = 4: vector stores for HR,
+// element stores for the 6-wide LR rows).
+struct AugSide {
+    const uint8_t* pool;
+    long long pool_bytes;
+    const long long* table;
+    int S;
+    uint8_t* out_u8;
+    float* out_f32;
+};
+
+template <bool VEC_HR, bool VEC_LR, bool F32>
+__global__ void __launch_bounds__(256) aug_gather_yuv420_pair_kernel(AugSide hr, AugSide lr, unsigned hr_blocks, YuvDec D) {
+    if (blockIdx.x < hr_blocks)
+        aug_yuv420_body<VEC_HR, F32>(hr.pool, hr.pool_bytes, hr.table, blockIdx.y, hr.S,
+                                     (int)(blockIdx.x * blockDim.x + threadIdx.x), D, hr.out_u8, hr.out_f32);
+    else
+        aug_yuv420_body<VEC_LR, F32>(lr.pool, lr.pool_bytes, lr.table, blockIdx.y, lr.S,
+                                     (int)((blockIdx.x - hr_blocks) * blockDim.x + threadIdx.x), D, lr.out_u8, lr.out_f32);
+}
+
+template <bool VEC_HR, bool VEC_LR, bool F32>
+static void aug_pair_launch(const AugSide& hr, const AugSide& lr, int64_t n, const YuvDec& D, hipStream_t st) {
+    const int64_t hb = cdiv((int64_t)hr.S * cdiv(hr.S, 4), 256), lb = cdiv((int64_t)lr.S * cdiv(lr.S, 4), 256);
+    const dim3 grid((unsigned)(hb + lb), (unsigned)n);
+    prof_note((double)n * ((double)hr.S * hr.S + (double)lr.S * lr.S) * 3.0 * (F32 ? 6.0 : 2.0), 0.0);
+    OFASR_LAUNCH((aug_gather_yuv420_pair_kernel<VEC_HR, VEC_LR, F32>), grid, dim3(256), 0, st, hr, lr, (unsigned)hb, D);
+}
+template <bool VEC_HR, bool VEC_LR>
+static void aug_pair_f32(const AugSide& hr, const AugSide& lr, int64_t n, const YuvDec& D, hipStream_t st) {
+    if (hr.out_f32) aug_pair_launch<VEC_HR, VEC_LR, true>(hr, lr, n, D, st);
+    else aug_pair_launch<VEC_HR, VEC_LR, false>(hr, lr, n, D, st);
+}
+static bool aug_vec_ok(const AugSide& s) {
+    return s.S % 4 == 0 && reinterpret_cast<uintptr_t>(s.out_u8) % 4 == 0 && reinterpret_cast<uintptr_t>(s.out_f32) % 16 == 0;
+}
+static void aug_gather_pair(const AugSide& hr, const AugSide& lr, int64_t n, const YuvDec& D, hipStream_t st) {
+    const bool vh = aug_vec_ok(hr), vl = aug_vec_ok(lr);
+    if (vh && vl) aug_pair_f32<true, true>(hr, lr, n, D, st);
+    else if (vh) aug_pair_f32<true, false>(hr, lr, n, D, st);
+    else if (vl) aug_pair_f32<false, true>(hr, lr, n, D, st);
+    else aug_pair_f32<false, false>(hr, lr, n, D, st);
 }
 
 // the launch of either kernel (YUV: the 4:2:0 one, which takes D) and the one VEC / F32 ladder
@@ -261,6 +328,35 @@ OFASR_EXPORT int ofasr_aug_gather_yuv420(const void* pool, int64_t pool_bytes, c
                   "%s: a pool of %lld bytes holds no 4:2:0 frame of at least %lldx%lld (even H, W >= S)", name,
                   (long long)pool_bytes, (long long)Se, (long long)Se);
     aug_gather<true>(pool, pool_bytes, table, n, S, yuv_dec(coeffs), out_u8, out_f32, as_stream(stream));
+    return check_launch(name);
+}
+
+OFASR_EXPORT int ofasr_aug_gather_yuv420_pair(const void* hr_pool, int64_t hr_bytes, const void* lr_pool, int64_t lr_bytes,
+                                              const int64_t* table, int64_t n, int64_t S, int64_t f, const int32_t* coeffs,
+                                              void* hr_u8, void* hr_f32, void* lr_u8, void* lr_f32, void* stream) {
+    const char* name = "ofasr_aug_gather_yuv420_pair";
+    OFASR_REQUIRE(hr_pool && lr_pool && table && coeffs && hr_u8 && lr_u8, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE((hr_f32 == nullptr) == (lr_f32 == nullptr), OFASR_ERR_INVALID_ARG,
+                  "%s: both fp32 outputs or neither", name);
+    OFASR_REQUIRE(f == 2 || f == 4, OFASR_ERR_UNSUPPORTED, "%s: scale %lld (2 or 4)", name, (long long)f);
+    AUG_REQUIRE_SIZES(n, S, hr_bytes);
+    OFASR_REQUIRE(lr_bytes > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
+    OFASR_REQUIRE(S % f == 0, OFASR_ERR_INVALID_ARG, "%s: crop side %lld is no multiple of the scale %lld", name,
+                  (long long)S, (long long)f);
+    OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
+    // as in ofasr_aug_gather_yuv420, per pool: the smallest even-sided frame of its crop must fit
+    const int64_t s = S / f, Se = (S + 1) & ~(int64_t)1, se = (s + 1) & ~(int64_t)1;
+    OFASR_REQUIRE(hr_bytes >= Se * Se * 3 / 2, OFASR_ERR_UNSUPPORTED,
+                  "%s: an HR pool of %lld bytes holds no 4:2:0 frame of at least %lldx%lld (even H, W >= S)", name,
+                  (long long)hr_bytes, (long long)Se, (long long)Se);
+    OFASR_REQUIRE(lr_bytes >= se * se * 3 / 2, OFASR_ERR_UNSUPPORTED,
+                  "%s: an LR pool of %lld bytes holds no 4:2:0 frame of at least %lldx%lld (even h, w >= S / f)", name,
+                  (long long)lr_bytes, (long long)se, (long long)se);
+    const AugSide hr{(const uint8_t*)hr_pool, (long long)hr_bytes, (const long long*)table, (int)S, (uint8_t*)hr_u8,
+                     (float*)hr_f32};
+    const AugSide lr{(const uint8_t*)lr_pool, (long long)lr_bytes, (const long long*)table + 12 * n, (int)s,
+                     (uint8_t*)lr_u8, (float*)lr_f32};
+    aug_gather_pair(hr, lr, n, yuv_dec(coeffs), as_stream(stream));
     return check_launch(name);
 }
 

@@ -15,6 +15,11 @@ Video.  The same gather runs on a pool of raw 8-bit YUV 4:2:0 frames with video.
 (ofasr_aug_gather_yuv420, ops.aug_gather_yuv420, ResidentVideoSet): gather_yuv420_np is its definition on the pool's
 bytes and apply_params_yuv420_np the same thing said as "the transforms of the decoded whole frame"
 (tests/test_video_train.py on the host, tests/test_hip_video_train.py on the GPU).
+
+Paired video.  A source video and its decoded low-resolution stream give the HR and the LR crop of ONE draw in one launch
+(ofasr_aug_gather_yuv420_pair, ops.aug_gather_yuv420_pair, ResidentVideoPairSet); the definition -- the pair, the draw,
+the sample, registration -- stands before draw_pair_params below (tests/test_video_pair.py on the host,
+tests/test_hip_video_pair.py on the GPU).
 """
 import math
 import os
@@ -203,6 +208,89 @@ def gather_yuv420_np(pool_bytes, table, S, coeffs):
     return out
 
 
+# ------------------------------------------------------------------------------------- paired HR / LR frames
+# The pair.  An HR video of H x W and an LR video of h x w -- the low-resolution stream after a codec, decoded -- with
+# H = f*h, W = f*w, f in {2, 4}, all four sides even, both 8-bit 4:2:0 with the same number of frames; all pairs of one
+# run share one f (video_pair_layout refuses the rest and names the files and the sizes).  One colour definition
+# (matrix, range) serves both sides.
+#
+# The draw.  draw_pair_params(h, w, S, f) needs S % f == 0, has s = S // f and draws ON THE LR GRID with the calls of
+# draw_train_params(h, w, s), in that order; it returns (i, j, flip, angle) of the LR crop, and the HR crop's parameters
+# are (f*i, f*j, flip, angle) at side S (pair_hr_params).  The RNG consumption is that of the unpaired path on an h x w
+# image with crop s.
+#
+# The sample.  HR = apply_params_yuv420_np(HR frame, S, (f*i, f*j, flip, angle)), LR = apply_params_yuv420_np(LR frame,
+# s, (i, j, flip, angle)): each the three PIL transforms of the decode of its OWN whole frame, so i, j may be odd and
+# chroma parity and edge replication are the frame's.
+#
+# Registration.  With angle = 0 the LR crop [i, i+s) x [j, j+s) covers exactly the HR crop [f*i, f*i+S) x [f*j, f*j+S),
+# flipped or not.  With a free angle the two nearest-neighbour rotations are PIL's on each canvas about the same centre,
+# each sampling its own grid: from pixel to pixel LR and HR can then disagree by up to half an LR pixel.  rotate=False
+# sets the angle to 0.0 AFTER it has been drawn, so the RNG sequence does not move: the setting for artefact restoration.
+PAIR_SCALES = (2, 4)
+
+
+def _pair_sides(S, f):
+    S, f = int(S), int(f)
+    if f not in PAIR_SCALES:
+        raise ValueError("a paired sample has scale 2 or 4, got %d" % f)
+    if S <= 0 or S % f:
+        raise ValueError("a paired sample's crop side %d must be a positive multiple of its scale %d" % (S, f))
+    return S, f, S // f
+
+
+def draw_pair_params(h, w, S, f, rotate=True):
+    """(i, j, flip, angle) of the LR crop of side S // f on the h x w LR frame, drawn exactly as
+    draw_train_params(h, w, S // f) draws; `rotate=False` replaces the drawn angle by 0.0 afterwards"""
+    S, f, s = _pair_sides(S, f)
+    i, j, flip, angle = draw_train_params(h, w, s)
+    return i, j, flip, (angle if rotate else 0.0)
+
+
+def pair_hr_params(params, f):
+    """the HR crop's parameters of the LR crop's `params`"""
+    i, j, flip, angle = params
+    return int(f) * i, int(f) * j, flip, angle
+
+
+def apply_pair_params_np(hr_planes, lr_planes, S, f, params, matrix="bt601", full_range=False):
+    """the paired sample of the LR-grid `params`: ([S, S, 3], [S/f, S/f, 3]), each side the transforms of the decode of
+    its own whole frame ((y, u, v) planes)"""
+    S, f, s = _pair_sides(S, f)
+    return (apply_params_yuv420_np(*hr_planes, size=S, params=pair_hr_params(params, f), matrix=matrix, full_range=full_range),
+            apply_params_yuv420_np(*lr_planes, size=s, params=params, matrix=matrix, full_range=full_range))
+
+
+def make_pair_table(rows, S, f, out=None):
+    """int64 [2, n, 12] host table of ofasr_aug_gather_yuv420_pair from (HR offset, H, W, LR offset, h, w, (i, j, flip,
+    angle) on the LR grid) entries: block 0 the HR rows at side S, block 1 the LR rows at side S / f, both through
+    table_row, which keeps all its refusals.  `out`: an int64 [>= 2n, 12] buffer to build it in."""
+    S, f, s = _pair_sides(S, f)
+    hr, lr = [], []
+    for (ho, H, W, lo, h, w, p) in rows:
+        if H != f * h or W != f * w:
+            raise ValueError("aug_gather_yuv420_pair: an HR frame of %dx%d is not %d times its LR frame of %dx%d"
+                             % (W, H, f, w, h))
+        hr.append(table_row(ho, H, W, S, pair_hr_params(p, f), True))
+        lr.append(table_row(lo, h, w, s, p, True))
+    n = len(hr)
+    t = torch.tensor(hr + lr, dtype=torch.int64).reshape(2 * n, TABLE_COLS)
+    if out is None:
+        return t.view(2, n, TABLE_COLS)
+    out[:2 * n].copy_(t)
+    return out[:2 * n].view(2, n, TABLE_COLS)
+
+
+def gather_yuv420_pair_np(hr_pool, lr_pool, table, S, f, coeffs):
+    """ofasr_aug_gather_yuv420_pair restated on the pools' bytes: gather_yuv420_np of each pool and its block of the
+    int64 [2, n, 12] table -> (uint8 [n, 3, S, S], uint8 [n, 3, S/f, S/f])"""
+    S, f, s = _pair_sides(S, f)
+    table = np.asarray(table, dtype=np.int64)
+    if table.ndim != 3 or table.shape[0] != 2 or table.shape[2] != TABLE_COLS:
+        raise ValueError("gather_yuv420_pair_np: table is [2, n, %d], got %s" % (TABLE_COLS, table.shape))
+    return gather_yuv420_np(hr_pool, table[0], S, coeffs), gather_yuv420_np(lr_pool, table[1], s, coeffs)
+
+
 # ------------------------------------------------------------------------------------- the resident training set
 class ResidentTrainSet(object):
     """Every training image decoded once (Image.open(p).convert("RGB"), on at most 16 threads) into ONE uint8 pool on
@@ -376,6 +464,120 @@ class ResidentVideoSet(object):
         return ops.aug_gather_yuv420(self.pool, table, n, S, self.matrix, self.full_range, want_f32=want_f32)
 
 
+def video_pair_layout(sources, lr_sources, max_bytes):
+    """(f, HR layout, LR layout) of ResidentVideoPairSet's two pools, each layout as video_pool_layout gives it, from
+    headers, FRAME lines and file sizes alone.  `sources` / `lr_sources`: (path, size, frame indices) per video, matched
+    by position; the LR video of a pair is read at the HR video's frame indices.  Refuses (ValueError, naming the files
+    and the sizes) another number of LR videos than HR videos, a 10-bit file on either side, different frame counts,
+    sides that are not exactly 2 or 4 times the LR sides, and pairs of different scales; both pools together above
+    `max_bytes` raise MemoryError."""
+    from ... import video
+    sources, lr_sources = list(sources), list(lr_sources)
+    if len(sources) != len(lr_sources):
+        raise ValueError("paired video: %d LR videos (%s) for %d HR videos (%s): they are matched by position"
+                         % (len(lr_sources), ", ".join(s[0] for s in lr_sources), len(sources),
+                            ", ".join(s[0] for s in sources)))
+    scale = None
+    for (hp, hsz, hidx), (lp, lsz, lidx) in zip(sources, lr_sources):
+        if [int(k) for k in hidx] != [int(k) for k in lidx]:
+            raise ValueError("paired video: %s and %s are read at different frame indices" % (hp, lp))
+        with video.open_reader(hp, hsz) as hr, video.open_reader(lp, lsz) as lr:
+            for r in (hr, lr):
+                if r.depth != 8:
+                    raise ValueError("%s is %d-bit: paired training input is 8-bit only on both sides (pair %s / %s)"
+                                     % (r.path, r.depth, hp, lp))
+            (H, W), (h, w) = (hr.height, hr.width), (lr.height, lr.width)
+            what = "%s (%dx%d) / %s (%dx%d)" % (hp, W, H, lp, w, h)
+            nh, nl = count_frames(hr), count_frames(lr)
+        if nh != nl:
+            raise ValueError("paired video: %s: %d frames against %d" % (what, nh, nl))
+        f = H // h if h else 0
+        if f not in PAIR_SCALES or H != f * h or W != f * w or any(v % 2 for v in (H, W, h, w)):
+            raise ValueError("paired video: %s: the HR sides must be exactly 2 or 4 times the LR sides, all even" % what)
+        if scale is not None and f != scale[0]:
+            raise ValueError("paired video: %s is a x%d pair but %s is a x%d pair: one run has one scale"
+                             % (what, f, scale[1], scale[0]))
+        scale = scale or (f, what)
+    if scale is None:
+        raise ValueError("ResidentVideoPairSet: no videos")
+    hl = video_pool_layout(sources, max_bytes)
+    ll = video_pool_layout(lr_sources, max_bytes)
+    if hl[2] + ll[2] > max_bytes:
+        total = hl[2] + ll[2]
+        raise MemoryError("ResidentVideoPairSet: %d frame pairs take %d + %d = %d bytes (%.2f GiB), above max_bytes = %d "
+                          "(%.2f GiB)" % (len(hl[0]), hl[2], ll[2], total, total / 2.0 ** 30, max_bytes, max_bytes / 2.0 ** 30))
+    return scale[0], hl, ll
+
+
+class ResidentVideoPairSet(object):
+    """The selected frames of HR videos and, at the same frame indices, of their decoded LR streams, in two
+    ResidentVideoSet pools on `device` (both count against `max_bytes`: a x4 LR pool adds 1/16).  `entries`, `paths`,
+    `pool`, `frame_planes`, `image_np` are the HR set's, as a ResidentVideoSet has them; `lr_entries`, `lr_pool`,
+    `lr_frame_planes`, `lr_image_np` stand beside them; `scale` is f.  `gather` is one ofasr_aug_gather_yuv420_pair
+    launch.  A ResidentTrainLoader over this set draws with draw_pair_params (`rotate=False`: the drawn angle becomes
+    0.0), builds the [2, n, 12] table (make_pair_table) and yields {'image_u8', 'lr_u8', 'lr_scale'} (+ 'image', 'lr',
+    the fp32 batches, with want_f32)."""
+    yuv420 = True
+    TABLE_BLOCKS = 2        # ResidentTrainLoader: rows of pinned table per sample
+
+    def __init__(self, sources, lr_sources, device, matrix="bt601", full_range=False, max_bytes=32 << 30, rotate=True):
+        from ... import video
+        video.yuv_coeffs(matrix, full_range)
+        sources, lr_sources = list(sources), list(lr_sources)
+        self.scale, _, _ = video_pair_layout(sources, lr_sources, max_bytes)    # what the files are, before the device
+        self.rotate = bool(rotate)
+        self.hr = ResidentVideoSet(sources, device, matrix, full_range, max_bytes)
+        self.lr = ResidentVideoSet(lr_sources, device, matrix, full_range, max_bytes)
+        self.matrix, self.full_range, self.device = self.hr.matrix, self.hr.full_range, self.hr.device
+        self.sources, self.lr_sources = self.hr.sources, self.lr.sources
+        self.entries, self.paths, self.pool = self.hr.entries, self.hr.paths, self.hr.pool
+        self.lr_entries, self.lr_paths, self.lr_pool = self.lr.entries, self.lr.paths, self.lr.pool
+        self.nbytes = self.hr.nbytes + self.lr.nbytes
+
+    def __len__(self):
+        return len(self.entries)
+
+    def frame_planes_np(self, k):
+        return self.hr.frame_planes_np(k)
+
+    def frame_planes(self, k):
+        return self.hr.frame_planes(k)
+
+    def image_np(self, k):
+        return self.hr.image_np(k)
+
+    def lr_frame_planes_np(self, k):
+        return self.lr.frame_planes_np(k)
+
+    def lr_frame_planes(self, k):
+        return self.lr.frame_planes(k)
+
+    def lr_image_np(self, k):
+        return self.lr.image_np(k)
+
+    # ---- what ResidentTrainLoader asks a set that has them
+    def check_crop(self, S):
+        _pair_sides(S, self.scale)
+
+    def draw_params(self, k, S):
+        _, h, w = self.lr_entries[k]
+        return draw_pair_params(h, w, S, self.scale, self.rotate)
+
+    def make_table(self, indices, params, S, out=None):
+        return make_pair_table([self.entries[k] + self.lr_entries[k] + (p,) for k, p in zip(indices, params)], S,
+                               self.scale, out=out)
+
+    def gather(self, table, n, S, want_f32=False):
+        from ... import ops
+        return ops.aug_gather_yuv420_pair(self.pool, self.lr_pool, table, n, S, self.scale, self.matrix, self.full_range,
+                                          want_f32=want_f32)
+
+    def as_batch(self, out, want_f32):
+        if want_f32:
+            return {"image_u8": out[0], "image": out[1], "lr_u8": out[2], "lr": out[3], "lr_scale": self.scale}
+        return {"image_u8": out[0], "lr_u8": out[1], "lr_scale": self.scale}
+
+
 class ResidentTrainLoader(object):
     """The DataLoader of the training crops, on the GPU: per batch the N parameter sets are drawn on the host in batch
     order (draw_train_params, torch global RNG), written into one pinned table, copied to the device once, and one
@@ -383,7 +585,12 @@ class ResidentTrainLoader(object):
     one ofasr_aug_gather_yuv420 launch; everything else is the same).  Yields {'image_u8': uint8 [N, 3, S, S]} (+ 'image', the same batch as
     fp32 / 255, when `want_f32`); utils.device_batch makes the LR images from it.  `sampler` is any index sampler over the
     set (RankShardSampler with its set_epoch contract when sharded, a fresh permutation per epoch otherwise).
-    The only host wait is on the pinned table of `ring` batches ago, before it is overwritten."""
+    The only host wait is on the pinned table of `ring` batches ago, before it is overwritten.
+
+    A paired set (ResidentVideoPairSet) brings hooks of its own, and only such a set has them: `TABLE_BLOCKS` rows of
+    pinned table per sample, `check_crop(S)`, `draw_params(k, S)` in place of draw_train_params, `make_table(indices,
+    params, S, out)` in place of make_table, and `as_batch(out, want_f32)` for the batch's keys.  For every other set
+    the draws, the table and the batch are what they were."""
 
     def __init__(self, dataset, batch_size, sampler, size, drop_last=True, want_f32=False, ring=4):
         self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
@@ -394,7 +601,10 @@ class ResidentTrainLoader(object):
             if h < self.size or w < self.size:
                 raise ValueError("Required crop size %s is larger than input image size %s (%s)"
                                  % ((self.size, self.size), (h, w), p))
-        self._host = [torch.empty((self.batch_size, TABLE_COLS), dtype=torch.int64).pin_memory() for _ in range(ring)]
+        if hasattr(dataset, "check_crop"):
+            dataset.check_crop(self.size)
+        rows = self.batch_size * getattr(dataset, "TABLE_BLOCKS", 1)
+        self._host = [torch.empty((rows, TABLE_COLS), dtype=torch.int64).pin_memory() for _ in range(ring)]
         self._done = [None] * ring
         self._turn = 0
         self.last_indices, self.last_params = None, None
@@ -407,6 +617,9 @@ class ResidentTrainLoader(object):
         """the batch of images `indices`; `params` (a list of (i, j, flip, angle)) are drawn when not given"""
         from ... import ops
         ds, S = self.dataset, self.size
+        draw = getattr(ds, "draw_params", None)       # a paired set draws on its LR grid
+        if params is None and draw is not None:
+            params = [draw(k, S) for k in indices]
         if params is None:
             params = [draw_train_params(ds.entries[k][1], ds.entries[k][2], S) for k in indices]
         slot = self._turn
@@ -414,8 +627,11 @@ class ResidentTrainLoader(object):
         if self._done[slot] is not None:
             self._done[slot].synchronize()     # the upload that last read this pinned table
         gather = getattr(ds, "gather", None)       # a set that decodes in its own gather (ResidentVideoSet)
-        host = make_table([ds.entries[k] + (p,) for k, p in zip(indices, params)], S, out=self._host[slot],
-                          yuv420=getattr(ds, "yuv420", False))
+        if hasattr(ds, "make_table"):                 # a paired set: [2, n, 12]
+            host = ds.make_table(indices, params, S, out=self._host[slot])
+        else:
+            host = make_table([ds.entries[k] + (p,) for k, p in zip(indices, params)], S, out=self._host[slot],
+                              yuv420=getattr(ds, "yuv420", False))
         with torch.cuda.device(ds.device):
             table = host.to(ds.device, non_blocking=True)
             ev = torch.cuda.Event()
@@ -426,6 +642,8 @@ class ResidentTrainLoader(object):
             else:
                 out = ops.aug_gather_u8(ds.pool, table, len(indices), S, want_f32=self.want_f32)
         self.last_indices, self.last_params = list(indices), list(params)
+        if hasattr(ds, "as_batch"):
+            return ds.as_batch(out, self.want_f32)
         if self.want_f32:
             return {"image_u8": out[0], "image": out[1]}
         return {"image_u8": out}

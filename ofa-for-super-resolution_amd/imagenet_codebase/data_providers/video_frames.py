@@ -9,12 +9,17 @@ frames at positions 0, K, 2K, ... (K = `valid_every`) are the evaluation set and
 K = 0: every frame trains and the first one evaluates.  Evaluation items are whole frames, ModCrop(4), batch 1, on
 every rank, in file order.
 
+Paired video (`videos_lr`, --video-lr): each video comes with its decoded low-resolution stream, 1/2 or 1/4 of its
+sides, and the network input at that scale is the LR stream's frame of the same index instead of Pillow's bicubic of
+the source (augment.ResidentVideoPairSet, ofasr_aug_gather_yuv420_pair; the definition stands in augment.py).
+
 This module also holds the command-line flags of the entry scripts (add_video_args / take_video_args); nothing at
 module level needs torch.
 """
 import argparse
 
 VIDEO_FLAGS = ("video", "video_size", "video_frames", "video_valid_every", "matrix", "range")
+PAIR_FLAGS = ("video_lr", "video_lr_size", "video_no_rotate")
 
 
 # ---------------------------------------------------------------------------------------------- command line
@@ -54,6 +59,15 @@ def add_video_args(ap):
                    help="every K-th selected frame of a video evaluates, the rest train (0: all train, the first evaluates)")
     g.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
     g.add_argument("--range", default="tv", choices=["tv", "pc"], help="tv: limited (16..235), pc: full range")
+    g.add_argument("--video-lr", action="append", default=None, metavar="PATH",
+                   help="the decoded low-resolution stream of the --video at the same position (1/2 or 1/4 of its sides, "
+                        "8-bit 4:2:0, as many frames): the network input at that scale is its frame, not the bicubic of "
+                        "the source; repeatable, one per --video")
+    g.add_argument("--video-lr-size", type=parse_video_size, default=None, metavar="WxH",
+                   help="frame size of headerless --video-lr files")
+    g.add_argument("--video-no-rotate", action="store_true",
+                   help="paired training without the random rotation (the angle is drawn and set to 0): LR and HR crops "
+                        "then cover exactly the same area; needs --video-lr")
     return ap
 
 
@@ -62,14 +76,33 @@ def take_video_args(a):
     arguments, or None without --video (the namespace is then what it was before the flags existed; a video flag
     given without --video is an error)."""
     vals = {k: a.__dict__.pop(k) for k in VIDEO_FLAGS}
+    pair = {k: a.__dict__.pop(k) for k in PAIR_FLAGS}
+    if not pair["video_lr"] and (pair["video_lr_size"] is not None or pair["video_no_rotate"]):
+        raise SystemExit("--video-lr-size / --video-no-rotate need --video-lr")
     if not vals["video"]:
         if vals["video_size"] is not None or vals["video_frames"] is not None:
             raise SystemExit("--video-size / --video-frames need --video")
+        if pair["video_lr"]:
+            raise SystemExit("--video-lr needs --video")
         return None
     if vals["video_valid_every"] < 0:
         raise SystemExit("--video-valid-every must be >= 0")
-    return dict(videos=list(vals["video"]), video_size=vals["video_size"], video_frames=vals["video_frames"],
-                video_valid_every=vals["video_valid_every"], matrix=vals["matrix"], full_range=vals["range"] == "pc")
+    kw = dict(videos=list(vals["video"]), video_size=vals["video_size"], video_frames=vals["video_frames"],
+              video_valid_every=vals["video_valid_every"], matrix=vals["matrix"], full_range=vals["range"] == "pc")
+    if pair["video_lr"]:      # without --video-lr the keyword arguments are what they were before the flag existed
+        if len(pair["video_lr"]) != len(kw["videos"]):
+            raise SystemExit("%d --video-lr (%s) for %d --video (%s): they are matched by position"
+                             % (len(pair["video_lr"]), ", ".join(pair["video_lr"]), len(kw["videos"]),
+                                ", ".join(kw["videos"])))
+        kw.update(videos_lr=list(pair["video_lr"]), video_lr_size=pair["video_lr_size"],
+                  video_rotate=not pair["video_no_rotate"])
+    return kw
+
+
+def refuse_pair_for_hr_input(video_kw, input_key, what):
+    """the entry scripts' refusal of --video-lr for a network whose input is the HR image itself (the X4 family)"""
+    if video_kw and video_kw.get("videos_lr") and input_key == "image":
+        raise SystemExit("--video-lr: %s takes the HR image as its input ('image'), it has no LR input to replace" % what)
 
 
 # ---------------------------------------------------------------------------------------------- the split
@@ -92,7 +125,8 @@ def select_frames(n_frames, frames=None, valid_every=10):
 class _EvalFrames(object):
     """a re-iterable, len()-able loader of whole frames of a ResidentVideoSet: batch-1 dicts {'image_u8': uint8
     [1, 3, H', W']} on the GPU, H', W' = ModCrop(4) of the frame, decoded by ops.yuv420_to_rgb_u8 when iterated (the
-    decoded frames are not kept)"""
+    decoded frames are not kept).  Of a ResidentVideoPairSet of scale f the items carry 'lr_u8', the decoded LR frame
+    cut to [1, 3, H'/f, W'/f], and 'lr_scale' = f beside it."""
 
     def __init__(self, dataset, indices):
         self.dataset, self.indices = dataset, list(indices)
@@ -108,26 +142,40 @@ class _EvalFrames(object):
             _, h, w = ds.entries[k]
             with torch.cuda.device(ds.device):
                 rgb = ops.yuv420_to_rgb_u8(*ds.frame_planes(k), matrix=ds.matrix, full_range=ds.full_range)
-                yield {"image_u8": rgb[:h - h % 4, :w - w % 4].permute(2, 0, 1).contiguous().unsqueeze(0)}
+                item = {"image_u8": rgb[:h - h % 4, :w - w % 4].permute(2, 0, 1).contiguous().unsqueeze(0)}
+                f = getattr(ds, "scale", None)
+                if f is not None:
+                    lr = ops.yuv420_to_rgb_u8(*ds.lr_frame_planes(k), matrix=ds.matrix, full_range=ds.full_range)
+                    item["lr_u8"] = lr[:(h - h % 4) // f, :(w - w % 4) // f].permute(2, 0, 1).contiguous().unsqueeze(0)
+                    item["lr_scale"] = f
+                yield item
 
 
 class VideoFramesDataProvider(object):
     """`train` / `valid` / `test`, `data_shape`, `assign_active_img_size`, `build_sub_train_loader` of
     Div2K_SetXXDataProvider over the frames of `videos` (paths; `video_size` = (width, height) for headerless files).
     `train` is an augment.ResidentTrainLoader over one augment.ResidentVideoSet holding every selected frame (training
-    and evaluation frames alike); `valid` is `test`."""
+    and evaluation frames alike); `valid` is `test`.  With `videos_lr` (one per video; `video_lr_size` for headerless
+    files) the set is an augment.ResidentVideoPairSet and every batch and evaluation item carries the decoded LR
+    stream's crop / frame; `rotate=False` trains without the rotation."""
     SUB_SEED = 937162211     # DataProvider.SUB_SEED of div2k_setxx.py
 
     def __init__(self, videos, video_size=None, frames=None, valid_every=10, matrix="bt601", full_range=False,
                  train_batch_size=16, test_batch_size=1, image_size=32, num_replicas=None, rank=None,
-                 resident_max_bytes=32 << 30):
+                 resident_max_bytes=32 << 30, videos_lr=None, video_lr_size=None, rotate=True):
         import torch
         from ... import video
-        from .augment import ResidentTrainLoader, ResidentVideoSet, count_frames
+        from .augment import ResidentTrainLoader, ResidentVideoPairSet, ResidentVideoSet, count_frames
         from .div2k_setxx import RankShardSampler
         self.videos = [videos] if isinstance(videos, str) else list(videos)
         if not self.videos:
             raise ValueError("VideoFramesDataProvider: no videos")
+        self.videos_lr = None if videos_lr is None else ([videos_lr] if isinstance(videos_lr, str) else list(videos_lr))
+        if self.videos_lr is None and not rotate:
+            raise ValueError("VideoFramesDataProvider: rotate=False is for paired video (videos_lr)")
+        if self.videos_lr is not None and len(self.videos_lr) != len(self.videos):
+            raise ValueError("VideoFramesDataProvider: %d LR videos (%s) for %d videos (%s): they are matched by position"
+                             % (len(self.videos_lr), ", ".join(self.videos_lr), len(self.videos), ", ".join(self.videos)))
         sizes = sorted(image_size) if isinstance(image_size, (list, tuple)) else [image_size]
         self.image_size = image_size if isinstance(image_size, int) else sizes
         self.active_img_size = sizes[-1]
@@ -145,8 +193,13 @@ class VideoFramesDataProvider(object):
         if not self.train_indices:
             raise ValueError("VideoFramesDataProvider: valid_every=%d leaves no training frame among the %d selected"
                              % (valid_every, at))
-        self.resident_set = ResidentVideoSet(sources, torch.device("cuda", torch.cuda.current_device()), matrix,
-                                             full_range, max_bytes=resident_max_bytes)
+        if self.videos_lr is not None:
+            lr_sources = [(p, video_lr_size, idx) for p, (_, _, idx) in zip(self.videos_lr, sources)]
+            self.resident_set = ResidentVideoPairSet(sources, lr_sources, torch.device("cuda", torch.cuda.current_device()),
+                                                     matrix, full_range, max_bytes=resident_max_bytes, rotate=rotate)
+        else:
+            self.resident_set = ResidentVideoSet(sources, torch.device("cuda", torch.cuda.current_device()), matrix,
+                                                 full_range, max_bytes=resident_max_bytes)
         self._shard = (num_replicas, rank) if num_replicas is not None and num_replicas > 1 else None
         if self._shard:
             sampler = RankShardSampler(self.train_indices, num_replicas, rank)

@@ -93,17 +93,28 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
     """Div2K_SetXXRunConfig's counterpart for raw 8-bit YUV 4:2:0 video: `data_provider` is a VideoFramesDataProvider
     (data_providers/video_frames.py) over `videos`, the frames resident on the GPU and decoded inside the augmentation
     gather.  `dataset` records "video_frames" and the paths, so run.config and every checkpoint say what they were
-    trained on.  There is no synthetic stand-in: a missing file is an error."""
+    trained on.  There is no synthetic stand-in: a missing file is an error.  `videos_lr` (one decoded LR stream per
+    video; `video_lr_size`, `video_rotate`) makes it paired video: the dataset string then names the LR files too, and
+    only then does the config carry these three keys."""
 
     def __init__(self, videos, video_size=None, video_frames=None, video_valid_every=10, matrix="bt601", full_range=False,
                  n_epochs=150, init_lr=0.05, lr_schedule_type="cosine", lr_schedule_param=None, dataset=None,
                  train_batch_size=256, test_batch_size=1, valid_size=None, opt_type="sgd", opt_param=None,
                  weight_decay=4e-5, label_smoothing=0.1, no_decay_keys=None, mixup_alpha=None, model_init="he_fout",
                  validation_frequency=1, print_frequency=10, n_worker=0, image_size=32, resident_max_bytes=32 << 30,
-                 **kwargs):
+                 videos_lr=None, video_lr_size=None, video_rotate=True, **kwargs):
         videos = [videos] if isinstance(videos, str) else list(videos)
+        name = "video_frames: " + ", ".join(videos)
+        if videos_lr is not None:
+            videos_lr = [videos_lr] if isinstance(videos_lr, str) else list(videos_lr)
+            if len(videos_lr) != len(videos):
+                raise ValueError("VideoFramesRunConfig: %d LR videos (%s) for %d videos (%s): they are matched by position"
+                                 % (len(videos_lr), ", ".join(videos_lr), len(videos), ", ".join(videos)))
+            name = "video_frames: " + ", ".join("%s (lr: %s)" % hl for hl in zip(videos, videos_lr))
+        elif not video_rotate or video_lr_size is not None:
+            raise ValueError("VideoFramesRunConfig: video_rotate=False and video_lr_size are for paired video (videos_lr)")
         super().__init__(n_epochs, init_lr, lr_schedule_type, lr_schedule_param,
-                         "video_frames: " + ", ".join(videos), train_batch_size, test_batch_size, valid_size, opt_type,
+                         name, train_batch_size, test_batch_size, valid_size, opt_type,
                          opt_param, weight_decay, label_smoothing, no_decay_keys, mixup_alpha, model_init,
                          validation_frequency, print_frequency, n_worker=n_worker, image_size=image_size)
         self.videos = videos
@@ -113,6 +124,10 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
         self.matrix, self.full_range = matrix, bool(full_range)
         self.resident = True
         self.resident_max_bytes = int(resident_max_bytes)
+        if videos_lr is not None:
+            self.videos_lr = videos_lr
+            self.video_lr_size = None if video_lr_size is None else tuple(video_lr_size)
+            self.video_rotate = bool(video_rotate)
 
     @property
     def data_provider(self):
@@ -125,5 +140,7 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
                 matrix=self.matrix, full_range=self.full_range, train_batch_size=self.train_batch_size,
                 test_batch_size=self.test_batch_size, image_size=self.image_size,
                 num_replicas=ws if ws > 1 else None, rank=dd.rank() if ws > 1 else None,
-                resident_max_bytes=self.resident_max_bytes)
+                resident_max_bytes=self.resident_max_bytes,
+                **({} if self.__dict__.get("videos_lr") is None else dict(
+                    videos_lr=self.videos_lr, video_lr_size=self.video_lr_size, rotate=self.video_rotate)))
         return self.__dict__["_data_provider"]

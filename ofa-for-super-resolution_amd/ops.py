@@ -189,19 +189,24 @@ def bicubic_resize_u8(img, out_h, out_w):
     return out
 
 
-def lr_images_from_u8(hr_u8, image=None):
+def lr_images_from_u8(hr_u8, image=None, given=None):
     """{'image', '2x_down_image', '4x_down_image'} (float32 in [0, 1], the loader contract of the reference's
     Div2K_SetXXDataset.__getitem__, div2k_setxx.py:288-298) from a uint8 HR batch [N, 3, H, W] already on the GPU:
     Scale(1/2) and Scale(1/4) as PIL computes them (output size int(h/f) x int(w/f)), then ToTensor's /255.
     `image`: the fp32 HR batch where the caller already has it (aug_gather_u8's second output: u8 / 255 with a correctly
-    rounded division, ToTensor's bits), reused as it is; the LR images are then divided exactly as well."""
+    rounded division, ToTensor's bits), reused as it is; the LR images are then divided exactly as well.
+    `given`: {f: float32 [N, 3, H/f, W/f]} LR batches that exist already (the decoded LR stream of a paired video
+    batch); they take the place of the bicubic at their scale."""
     _, _, H, W = hr_u8.shape
     if image is not None and (image.dtype != torch.float32 or image.shape != hr_u8.shape or image.device != hr_u8.device):
         raise _C.OfasrError("lr_images_from_u8: image= must be the float32 batch of hr_u8 (%s on %s), got %s %s on %s"
                             % (tuple(hr_u8.shape), hr_u8.device, image.dtype, tuple(image.shape), image.device))
     out = {"image": hr_u8.float().div_(255.0) if image is None else image}
     for f in (2, 4):
-        lr = bicubic_resize_u8(hr_u8, int(H * (1.0 / f)), int(W * (1.0 / f)))
+        if given and f in given:       # a paired batch brings this scale's LR images: no bicubic is computed for it
+            out["%dx_down_image" % f] = given[f]
+            continue
+        lr =bicubic_resize_u8(hr_u8, int(H * (1.0 / f)), int(W * (1.0 / f)))
         # ATen's GPU division by a host scalar multiplies by the rounded reciprocal: up to 1 ulp from ToTensor's v / 255.
         # Beside an exact `image` the LR images are exact too (a table of the 256 quotients), so the whole batch equals
         # the host provider's bit for bit; without `image` the values stay what they were.
@@ -254,6 +259,38 @@ def aug_gather_yuv420(pool, table, n, S, matrix="bt601", full_range=False, want_
     yuv420_to_rgb_u8 of every frame, byte for byte, with no RGB frame anywhere (ofasr_aug_gather_yuv420,
     csrc/augment.hip; the definition is data_providers/augment.gather_yuv420_np)."""
     return _aug_gather("aug_gather_yuv420", pool, table, n, S, (yuv_table(matrix, full_range, False),), want_f32)
+
+
+def aug_gather_yuv420_pair(hr_pool, lr_pool, table, n, S, f, matrix="bt601", full_range=False, want_f32=False):
+    """The HR batch [n, 3, S, S] and the LR batch [n, 3, S/f, S/f] of one draw in one launch, from a pool of source
+    frames and a pool of the decoded low-resolution stream's frames (both as aug_gather_yuv420's pool): (hr_u8, lr_u8),
+    with `want_f32` (hr_u8, hr_f32, lr_u8, lr_f32).  `table`: int64 [2, >= n, 12] on the pools' device, block 0 the HR
+    rows and block 1 the LR rows (data_providers/augment.make_pair_table); each side equals aug_gather_yuv420 of its pool
+    and block (ofasr_aug_gather_yuv420_pair, csrc/augment.hip; the definition is augment.gather_yuv420_pair_np)."""
+    name = "aug_gather_yuv420_pair"
+    _gpu(hr_pool, lr_pool, table)
+    n, S, f = int(n), int(S), int(f)
+    for what, pool in (("hr_pool", hr_pool), ("lr_pool", lr_pool)):
+        if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous() or pool.device != hr_pool.device:
+            raise _C.OfasrError("%s: %s is a contiguous 1-D uint8 tensor on %s, got %s %s on %s"
+                                % (name, what, hr_pool.device, pool.dtype, tuple(pool.shape), pool.device))
+    if table.dtype != torch.int64 or table.dim() != 3 or table.size(0) != 2 or table.size(2) != 12 or table.size(1) < n or \
+            not table.is_contiguous() or table.device != hr_pool.device:
+        raise _C.OfasrError("%s: table is a contiguous int64 [2, >= %d, 12] tensor on %s, got %s %s on %s"
+                            % (name, n, hr_pool.device, table.dtype, tuple(table.shape), table.device))
+    if table.size(1) != n:          # the library reads block 1 at row n
+        table = table[:, :n].contiguous()
+    s = S // f if f > 0 else 0
+    hr = torch.empty((max(n, 0), 3, max(S, 0), max(S, 0)), dtype=torch.uint8, device=hr_pool.device)
+    lr = torch.empty((max(n, 0), 3, max(s, 0), max(s, 0)), dtype=torch.uint8, device=hr_pool.device)
+    hr32 = torch.empty(hr.shape, dtype=torch.float32, device=hr.device) if want_f32 else None
+    lr32 = torch.empty(lr.shape, dtype=torch.float32, device=hr.device) if want_f32 else None
+    with _timed(name, (hr.numel() + lr.numel()) * (6 if want_f32 else 2)):
+        _C.check(_C.lib().ofasr_aug_gather_yuv420_pair(
+            _p(hr_pool), hr_pool.numel(), _p(lr_pool), lr_pool.numel(), _p(table), n, S, f,
+            yuv_table(matrix, full_range, False), _p(hr), _p(hr32) if want_f32 else None, _p(lr),
+            _p(lr32) if want_f32 else None, _stream()), name)
+    return (hr, hr32, lr, lr32) if want_f32 else (hr, lr)
 
 
 # ------------------------------------------------------------------------------ Y-PSNR / Y-SSIM on the GPU

@@ -222,11 +222,21 @@ def device_batch(mini_batch, device):
     """a loader batch on `device` under the reference's keys.  Batches of a provider built with lr_on_device=True carry
     only 'image_u8' (uint8 HR): the LR images are then made on the GPU with PIL's exact bicubic arithmetic
     (ops.lr_images_from_u8) instead of by the host-side PIL calls of div2k_setxx.py:288-298.  A resident loader
-    (data_providers/augment.py) may hand over the fp32 HR batch beside it ('image'), which is then reused."""
+    (data_providers/augment.py) may hand over the fp32 HR batch beside it ('image'), which is then reused.  A batch of
+    a paired video set carries 'lr_u8' and 'lr_scale' = f as well (and 'lr', the fp32 batch, from the training loader):
+    the decoded LR stream's crop becomes '<f>x_down_image' (the kernel's fp32 output, else lr_u8 / 255 correctly
+    rounded); the other scale's key stays Pillow's bicubic of the HR crop."""
     if "image_u8" in mini_batch:
         image = mini_batch.get("image")
+        given = None
+        if "lr_u8" in mini_batch:
+            lr = mini_batch.get("lr")
+            if lr is None:
+                lr_u8 = mini_batch["lr_u8"].to(device, non_blocking=True)
+                lr = ops._unit_lut(lr_u8.device)[lr_u8.long()]
+            given = {int(mini_batch["lr_scale"]): lr.to(device, non_blocking=True)}
         return ops.lr_images_from_u8(mini_batch["image_u8"].to(device, non_blocking=True),
-                                     image=None if image is None else image.to(device, non_blocking=True))
+                                     image=None if image is None else image.to(device, non_blocking=True), given=given)
     return {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in mini_batch.items()}
 
 

@@ -52,6 +52,7 @@ def parse_args(argv=None):
     vf.add_video_args(ap)
     a = ap.parse_args(argv)
     a.video_kw = vf.take_video_args(a)      # --video: calibrate and validate on the frames of raw YUV 4:2:0 video
+    vf.refuse_pair_for_hr_input(a.video_kw, "image" if a.net == "x4" else None, "--net x4")
     if a.test_sizes:
         a.test_sizes = [tuple(int(v) for v in s.split("x")) for s in a.test_sizes.split(",")]
     return a

@@ -10,10 +10,14 @@
    resident 1920x1080 YUV 4:2:0 frames against ops.aug_gather_u8 on the same crops from an RGB pool of the same frames
    made with ops.yuv420_to_rgb_u8 (equal bytes out, checked): both kernel times and their ratio.  The fused gather
    issues 9 byte loads per pixel against 3.
+ * the pair leg (--only-pair runs nothing else; --yuv-frames F frame pairs): ops.aug_gather_yuv420_pair at N=16, S=256,
+   f=4 on F resident 1920x1080 frames and their 480x270 LR frames against the two separate ops.aug_gather_yuv420
+   launches that produce the same bytes (checked), on the same crops: the one launch's time, the two launches' times
+   and their sum.
 Prints one JSON line.
 usage: python tools/bench_augment.py [--files 32] [--entries 256] [--height 1356] [--width 2040] [--batches 200]
                                      [--warmup 10] [--host-batches 200] [--workers 16] [--skip-host]
-                                     [--yuv-frames 64] [--only-yuv]"""
+                                     [--yuv-frames 64] [--only-yuv] [--only-pair]"""
 import argparse
 import importlib
 import json
@@ -121,6 +125,60 @@ def yuv_leg(C, L, ops, aug, dev, N, S, frames, reps, H=1080, W=1920):
     return res
 
 
+def synthetic_yuv_pool(dev, frames, H, W, seed):
+    """`frames` H x W 4:2:0 frames back to back on `dev`: smooth luma and chroma fields, shifted per frame, with mild
+    noise, in the legal ranges"""
+    import numpy as np
+    import torch
+    rng = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    fb = H * W * 3 // 2
+    pool = torch.empty(frames * fb, dtype=torch.uint8, device=dev)
+    ybase = 126 + 100 * np.sin(yy * (26.3 / H)) * np.cos(xx * (32.5 / W))
+    cbase = [128 + 90 * np.sin(yy[::2, ::2] * ((16.1 - 2 * j) / H)) * np.cos(xx[::2, ::2] * (23.1 / W)) for j in range(2)]
+    for k in range(frames):
+        y = np.clip(np.roll(ybase, (61 * k) % W, axis=1) + rng.randint(-5, 6, (H, W)), 16, 235)
+        c = [np.clip(np.roll(cb, (29 * k) % (W // 2), axis=1) + rng.randint(-3, 4, (H // 2, W // 2)), 16, 240) for cb in cbase]
+        host = np.concatenate([p.astype(np.uint8).reshape(-1) for p in (y, c[0], c[1])])
+        pool[k * fb:(k + 1) * fb].copy_(torch.from_numpy(host))
+    return pool, fb
+
+
+def pair_leg(C, L, ops, aug, dev, N, S, frames, reps, f=4, h=270, w=480):
+    """one ofasr_aug_gather_yuv420_pair launch against the two ofasr_aug_gather_yuv420 launches that write the same two
+    batches, on the same crops"""
+    import torch
+    H, W, s = f * h, f * w, S // f
+    hr_pool, hfb = synthetic_yuv_pool(dev, frames, H, W, 1)
+    lr_pool, lfb = synthetic_yuv_pool(dev, frames, h, w, 2)
+    torch.manual_seed(0)
+    tables = []
+    for r in range(reps):
+        idx = torch.randint(0, frames, (N,)).tolist()
+        rows = [(k * hfb, H, W, k * lfb, h, w, aug.draw_pair_params(h, w, S, f)) for k in idx]
+        t = aug.make_pair_table(rows, S, f).to(dev)
+        tables.append((t, t[0].contiguous(), t[1].contiguous()))
+    res = {"frames": frames, "hr_hw": [H, W], "lr_hw": [h, w], "f": f, "hr_pool_bytes": hr_pool.numel(),
+           "lr_pool_bytes": lr_pool.numel(), "launches": reps}
+    for want_f32 in (False, True):
+        t = tables[0]
+        pair = ops.aug_gather_yuv420_pair(hr_pool, lr_pool, t[0], N, S, f, want_f32=want_f32)
+        a = ops.aug_gather_yuv420(hr_pool, t[1], N, S, want_f32=want_f32)
+        b = ops.aug_gather_yuv420(lr_pool, t[2], N, s, want_f32=want_f32)
+        two = (a + b) if want_f32 else (a, b)
+        if len(pair) != len(two) or not all(torch.equal(x, y) for x, y in zip(pair, two)):
+            raise SystemExit("aug_gather_yuv420_pair and the two aug_gather_yuv420 launches differ")
+        us_p = kernel_us(C, L, lambda t: ops.aug_gather_yuv420_pair(hr_pool, lr_pool, t[0], N, S, f, want_f32=want_f32),
+                         tables, "aug_gather_yuv420_pair_kernel")
+        us_h = kernel_us(C, L, lambda t: ops.aug_gather_yuv420(hr_pool, t[1], N, S, want_f32=want_f32), tables,
+                         "aug_gather_yuv420_kernel")
+        us_l = kernel_us(C, L, lambda t: ops.aug_gather_yuv420(lr_pool, t[2], N, s, want_f32=want_f32), tables,
+                         "aug_gather_yuv420_kernel")
+        res["f32" if want_f32 else "u8"] = {"pair_kernel_us": us_p, "hr_kernel_us": us_h, "lr_kernel_us": us_l,
+                                            "two_launches_us": us_h + us_l, "ratio": us_p / (us_h + us_l)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=32)
@@ -135,6 +193,7 @@ def main():
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--yuv-frames", type=int, default=64, help="1920x1080 frames of the YUV leg (0: skip it)")
     ap.add_argument("--only-yuv", action="store_true", help="run the YUV leg alone")
+    ap.add_argument("--only-pair", action="store_true", help="run the pair leg alone (--yuv-frames frame pairs)")
     a = ap.parse_args()
     import torch
     C = importlib.import_module(PKG + "._C")
@@ -148,6 +207,10 @@ def main():
     N, S = 16, 256
     out = {"N": N, "S": S, "copy_TBps": COPY_TBPS, "files": a.files, "entries": max(a.entries, a.files),
            "file_hw": [a.height, a.width]}
+    if a.only_pair:
+        out["yuv420_pair"] = pair_leg(C, L, ops, aug, dev, N, S, max(a.yuv_frames, 1), a.reps)
+        print(json.dumps(out), flush=True)
+        return
     if a.yuv_frames > 0:
         out["yuv420"] = yuv_leg(C, L, ops, aug, dev, N, S, a.yuv_frames, a.reps)
     if a.only_yuv:

@@ -9,7 +9,8 @@ the same `args` attribute names, reference :21-132), one process per GPU:
 Differences from the reference script: hyper-parameters that it edits in source are flags here
 (--net s4|x4, --teacher-path, --path, --mix-prec); with --synthetic the synthetic provider stands in for a missing
 DIV2K directory (otherwise a missing dataset is an error); --video PATH trains on the frames of raw 8-bit YUV 4:2:0
-video instead (data_providers/video_frames.py); multi-GPU is RCCL data parallelism (one flat all-reduce per step)."""
+video instead (data_providers/video_frames.py), and --video-lr PATH pairs each video with its decoded low-resolution
+stream, which then is the network input at its scale; multi-GPU is RCCL data parallelism (one flat all-reduce per step)."""
 import argparse
 import importlib
 import os
@@ -40,6 +41,7 @@ def main():
     vf.add_video_args(ap)
     args = ap.parse_args()
     video_kw = vf.take_video_args(args)     # None without --video: `args` is then what it always was
+    vf.refuse_pair_for_hr_input(video_kw, "image" if args.net == "x4" else None, "--net x4")
 
     import numpy as np
     import torch
