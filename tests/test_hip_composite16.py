@@ -9,8 +9,6 @@ its result, rounded once, is compared with what the GPU stage WROTE, element by 
 DESIGN.md section 4 (rtol 1e-2 bf16 / 2e-3 f16).  Reference call sites restated by the oracle:
 dynamic_layers.py:70-84, dynamic_op.py:46-84,104-112,148-167, proxyless_nets.py:44-51.  The launch counters of the
 library (include/ofasr.h, Diagnostics) assert that the kernel variants of the timed path served the call."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -97,15 +95,36 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "N%d_%dx%d_e%d_k%d_%s_%s" % (
-    c[0], c[1], c[2], c[3], c[4], "train" if c[5] else "eval", "bf16" if c[6] == torch.bfloat16 else "f16"))
+# The switches that change which kernel serves a stage of the block, or what the backward scratch holds (csrc/mbconv.hip,
+# INTEGRATION.md "Environment switches, read once"), as the library reads them in this process.  The default profile is the
+# timed path; tests/test_hip_switches.py runs check_block in fresh processes under the other profiles.
+DEFAULT_PROFILE = dict(fanout_slabs=True, fanin_fast=True, epilogue_stats=True, bn_fold=True, coef_fold=True,
+                       dw_wgrad_mfma=True, dw_wgrad_bx=True, wg1_bx=False, bn_onepass=False)
+CASE_ID = lambda c: "N%d_%dx%d_e%d_k%d_%s_%s" % (c[0], c[1], c[2], c[3], c[4], "train" if c[5] else "eval",
+                                                  "bf16" if c[6] == torch.bfloat16 else "f16")
+
+
+def bstat_applies(case):
+    N, Hh, Ww, e, K, train, dtype = case
+    return train and (Hh * Ww) % 128 == 0 and 64 * e in (256, 384)
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_ID)
 @pytest.mark.parametrize("bstat", [False, True], ids=["", "bn2sums_in_dgrad"])
 def test_composite_block_16bit_vs_oracle(ora, case, bstat):
+    if bstat and not bstat_applies(case):
+        pytest.skip("the BN2-sums-in-the-project-dgrad variant (off by default) only exists for the slab-walk kernel")
+    check_block(ora, case, bstat, DEFAULT_PROFILE)
+
+
+def check_block(ora, case, bstat, profile):
+    """one composite forward + backward of `case`, every stage against the oracle; `profile` says which side of each
+    routing switch this process runs (the switches are read once per process).  Returns the launch table of the call."""
     from oracle import composite16 as c16
     N, Hh, Ww, e, K, train, dtype = case
     ops, C = amd("ops"), amd("_C")
-    if bstat and not (train and (Hh * Ww) % 128 == 0 and 64 * e in (256, 384)):
-        pytest.skip("the BN2-sums-in-the-project-dgrad variant (off by default) only exists for the slab-walk kernel")
+    pf = dict(DEFAULT_PROFILE, **profile)
+    assert not bstat or bstat_applies(case), case
     was_bstat = C.lib().ofasr_debug_mbconv_bn_bwd_stat(1 if bstat else 0)
     block, layer = _make_block(100 * K + e)
     block.to(DEV).train(train)
@@ -139,54 +158,87 @@ def test_composite_block_16bit_vs_oracle(ora, case, bstat):
         ops._TMP_CACHE.clear()
         C.lib().ofasr_debug_mbconv_bn_bwd_stat(was_bstat)
 
-    # ---- routing: the kernel variants bench.py's timed step runs (profiles/r02_*_steps.txt) served this call
+    # ---- routing: the kernel variants bench.py's timed step runs (profiles/r02_*_steps.txt) served this call -- or, under
+    # another profile, the variant that switch selects and not the default one
     T = TNAME[dtype]
 
     def ran(table, *parts):
         return sum(n for name, n in table.items() if all(p in name for p in parts))
 
     aligned = (Hh * Ww) % 128 == 0
+    # BN1 / BN2 backward folded into their consumers: needs the switch and the fast fan-in kernel (pwconv_dgrad_bx_supported)
+    folded = pf["bn_fold"] and pf["fanin_fast"]
+    st2 = bstat and folded
+    fast = "true" if pf["fanin_fast"] else "false"
+    generic_fanout = "pw_fanout_kernel<%s, true, true, false>" % T
     if train and aligned:
         if mid in (256, 384):
-            assert ran(fwd_table, "pw_fanout_slabs_kernel<%s, %d, 1>" % (T, mid // 128)) == 1, fwd_table   # + BN1 stats
-            if bstat:   # project dgrad + the BN2-backward sums of what it writes (BwdStatOut): no reduction pass for BN2
+            if pf["fanout_slabs"]:   # + BN1 statistics in the epilogue unless OFASR_PW_EPILOGUE_STATS=0
+                assert ran(fwd_table, "pw_fanout_slabs_kernel<%s, %d, %d>" % (T, mid // 128, 1 if pf["epilogue_stats"] else 0)) == 1, fwd_table
+            else:
+                assert ran(fwd_table, "pw_fanout_slabs_kernel") == 0 and ran(fwd_table, generic_fanout) == 1, fwd_table
+            if st2:   # project dgrad + the BN2-backward sums of what it writes (BwdStatOut): no reduction pass for BN2
                 assert ran(bwd_table, "pw_fanout_slabs_kernel<%s, %d, 2>" % (T, mid // 128)) == 1, bwd_table
                 assert ran(bwd_table, "bn_bwd_coef_cp_kernel") == 1, bwd_table
-            else:
+            elif pf["fanout_slabs"]:
                 assert ran(bwd_table, "pw_fanout_slabs_kernel<%s, %d, 0>" % (T, mid // 128)) == 1, bwd_table
                 assert ran(bwd_table, "bn_bwd_coef_cp_kernel") == 0, bwd_table
-        assert ran(fwd_table, "pw_fanin_pipe_kernel<%s, true, true, false>" % T) == 1, fwd_table      # project: XF + fold
-        # backward: BN1 / BN2 have no apply pass -- their consumers read (da, y) through the BN backward (BwdXf variants)
-        assert ran(bwd_table, "pw_fanin_pipe_kernel<%s, false, true, true>" % T) == 1, bwd_table   # expand dgrad (+dout)
+            else:
+                assert ran(bwd_table, "pw_fanout_slabs_kernel") == 0 and ran(bwd_table, generic_fanout) == 1, bwd_table
+                assert ran(bwd_table, "bn_bwd_coef_cp_kernel") == 0, bwd_table
+        assert ran(fwd_table, "pw_fanin_pipe_kernel<%s, true, %s, false>" % (T, fast)) == 1, fwd_table      # project: XF + fold
+        assert ran(fwd_table, "pw_fanin_pipe_kernel") == 1, fwd_table
+        if folded:
+            # backward: BN1 / BN2 have no apply pass -- their consumers read (da, y) through the BN backward (BwdXf variants)
+            assert ran(bwd_table, "pw_fanin_pipe_kernel<%s, false, true, true>" % T) == 1, bwd_table   # expand dgrad (+dout)
+        else:   # the plain expand dgrad (+dout) reads the dy1 an apply pass stored
+            assert ran(bwd_table, "pw_fanin_pipe_kernel<%s, false, %s, false>" % (T, fast)) == 1, bwd_table
+        assert ran(bwd_table, "pw_fanin_pipe_kernel") == 1, bwd_table
         assert ran(bwd_table, "pw_wgrad_direct_kernel<%s, 1>" % T) + ran(bwd_table, "pw_wgrad_direct_kernel<%s, 2>" % T) == 1
         # the expand weight gradient: from the dy1 the expand dgrad stored (<T, 0>, default) or, with OFASR_MBCONV_WG1_BX=1,
         # formed from (da1, y1) as it reads them (BwdXf, <T, 3>; the expand dgrad then stores no dy1)
-        want3 = 1 if os.environ.get("OFASR_MBCONV_WG1_BX", "0") == "1" else 0
+        want3 = 1 if (pf["wg1_bx"] and folded) else 0
         assert ran(bwd_table, "pw_wgrad_direct_kernel<%s, 3>" % T) == want3 and \
             ran(bwd_table, "pw_wgrad_direct_kernel<%s, 0>" % T) == 1 - want3, bwd_table
-        if Ww in (32, 64) and Hh % 16 == 0 and Hh <= 64:   # depthwise weight gradient on the matrix cores, no reduce launch
-            assert ran(bwd_table, "dw_wgrad_mfma_kernel<%s, %d, %d, true, true>" % (T, K, Ww // 32)) == 1, bwd_table
+        mfma_shape = Ww in (32, 64) and Hh % 16 == 0 and Hh <= 64
+        if mfma_shape and pf["dw_wgrad_mfma"]:   # depthwise weight gradient on the matrix cores, no reduce launch
+            # <..., true, true>: dy2 formed from (da2, y2) on read; <..., true, false> (OFASR_DW_WGRAD_BX=0, or after an apply
+            # pass): the stored dy2
+            bx = "true" if (folded and pf["dw_wgrad_bx"]) else "false"
+            assert ran(bwd_table, "dw_wgrad_mfma_kernel<%s, %d, %d, true, %s>" % (T, K, Ww // 32, bx)) == 1, bwd_table
+            assert ran(bwd_table, "dw_wgrad_mfma_kernel") == 1, bwd_table
             assert ran(bwd_table, "dw_wgrad_vec") == 0, bwd_table
         else:
             assert ran(bwd_table, "dw_wgrad_vec_kernel<%s, %d, true>" % (T, K)) == 1, bwd_table
+            assert ran(bwd_table, "dw_wgrad_mfma_kernel") == 0, bwd_table
         nstat = ran(bwd_table, "bn_bwd_coef_cp_kernel")
         # BN3 (64 channels, no activation): the reduction + apply pair; with OFASR_BN_BWD_ONEPASS=1 (opt-in, measured slower in
         # the step) a one-pass backward from registers when a channel fits a workgroup (N * HW <= 65536)
         one3 = ran(bwd_table, "bn_bwd_onepass_kernel")
-        assert one3 == (1 if (N * Hh * Ww <= 65536 and os.environ.get("OFASR_BN_BWD_ONEPASS", "0") == "1") else 0), bwd_table
-        assert ran(bwd_table, "bn_bwd_reduce_kernel") == 3 - one3 - nstat and ran(bwd_table, "bn_bwd_apply_kernel") == 1 - one3
-        # ... and no coefficient launch either: the consumers fold the reduction's partial slabs themselves (BwdXf::fold_*)
-        assert ran(bwd_table, "bn_bwd_coef_kernel") == 0
+        assert one3 == (1 if (N * Hh * Ww <= 65536 and pf["bn_onepass"]) else 0), bwd_table
+        if folded:
+            assert ran(bwd_table, "bn_bwd_reduce_kernel") == 3 - one3 - nstat and ran(bwd_table, "bn_bwd_apply_kernel") == 1 - one3
+            # ... and no coefficient launch either: the consumers fold the reduction's partial slabs themselves
+            # (BwdXf::fold_*); OFASR_MBCONV_BN_COEF_FOLD=0 puts the coefficient kernel between each reduction and its consumer
+            assert ran(bwd_table, "bn_bwd_coef_kernel") == (0 if pf["coef_fold"] else 2 - nstat), bwd_table
+        else:   # the reduction + apply pair for all three BNs, no BwdXf consumer
+            assert nstat == 0 and ran(bwd_table, "bn_bwd_reduce_kernel") == 3 - one3, bwd_table
+            assert ran(bwd_table, "bn_bwd_apply_kernel") == 3 - one3 and ran(bwd_table, "bn_bwd_coef_kernel") == 0, bwd_table
         if K in (5, 7) and Ww in (32, 64):
             assert ran(fwd_table, "dw_mfma_kernel<%s, %d, false, true, true, false>" % (T, K)) == 1, fwd_table
-            assert ran(bwd_table, "dw_mfma_kernel<%s, %d, true, false, false, true>" % (T, K)) == 1, bwd_table
+            assert ran(bwd_table, "dw_mfma_kernel<%s, %d, true, false, false, true>" % (T, K)) == (1 if folded else 0), bwd_table
         else:
             assert ran(fwd_table, "dw_vec_kernel<%s, %d, false, true, true, false>" % (T, K)) == 1, fwd_table
-            assert ran(bwd_table, "dw_vec_kernel<%s, %d, true, false, false, true>" % (T, K)) == 1, bwd_table
+            assert ran(bwd_table, "dw_vec_kernel<%s, %d, true, false, false, true>" % (T, K)) == (1 if folded else 0), bwd_table
     # only BN3 has an apply pass (or its one-pass form): BN1 / BN2 are folded into their consumers
     folded_bwd = ran(bwd_table, "bn_bwd_apply_kernel") + ran(bwd_table, "bn_bwd_onepass_kernel") == 1
     dw_mma = ran(fwd_table, "dw_mfma_kernel") > 0
-    assert ran(fwd_table, "bn_stats_kernel") == 0 and ran(fwd_table, "bn_finalize") == 0 or not (train and aligned)
+    if pf["epilogue_stats"]:
+        assert ran(fwd_table, "bn_stats_kernel") == 0 and ran(fwd_table, "bn_finalize") == 0 or not (train and aligned)
+    elif train and aligned:   # BN1 / BN3 statistics by a pass over the tensor + the classic finalize (BN2's stay in the depthwise)
+        assert ran(fwd_table, "bn_stats_kernel") == 2 and ran(fwd_table, "bn_finalize_kernel") == 2, fwd_table
+    if train and aligned:
+        assert folded_bwd == folded, bwd_table
 
     # ---- the call's own buffers (layout: csrc/mbconv.hip)
     P = N * Hh * Ww
@@ -201,7 +253,13 @@ def test_composite_block_16bit_vs_oracle(ora, case, bstat):
     st1, st2, st3 = st[0:4 * mid].reshape(4, mid), st[4 * mid:8 * mid].reshape(4, mid), st[8 * mid:8 * mid + 256].reshape(4, 64)
     f_gpu = st[8 * mid + 256:].reshape(mid, 1, K, K)
     t = tmp.float().cpu().numpy()
-    # folded BN backward: tA = dy1 (over the dead da2), tB = da1, tC = dy2;  apply pass: tA = dy2, tB = dy1 (in place)
+    # apply pass (bn_fold or fanin_fast off): tA = dy2, tB = dy1 (both in place), tC unused.
+    # folded BN backward: tB = da1 and, by who forms dy2 / dy1 on read (wg_bx: the depthwise weight gradient, wg1: the
+    # expand weight gradient):      tA                      tC
+    #   neither                     dy1 (over the dead da2) dy2
+    #   wg_bx                       da2 (kept)              dy1
+    #   wg1                         da2 (never overwritten) dy2
+    #   wg_bx and wg1               da2 (kept)              unused -- dy2 and dy1 are stored nowhere
     tA = t[0:P * mid].reshape(N, mid, Hh, Ww)
     tB = t[P * mid:2 * P * mid].reshape(N, mid, Hh, Ww)
     dy3 = t[2 * P * mid:2 * P * mid + P * 64].reshape(N, 64, Hh, Ww)
@@ -269,9 +327,14 @@ def test_composite_block_16bit_vs_oracle(ora, case, bstat):
     # where the depthwise weight gradient runs on the matrix cores with both operands formed on read (dw_wgrad_mfma_kernel
     # <..., true, true>) dy2 is stored nowhere: tA keeps da2 for that kernel, dy1 goes to tC
     wg_bx = any("dw_wgrad_mfma_kernel" in k and k.rstrip().endswith("true, true>") for k in bwd_table)
+    wg1 = ran(bwd_table, "pw_wgrad_direct_kernel<%s, 3>" % T) > 0
+    if train and aligned:
+        assert wg_bx == (folded and pf["dw_wgrad_mfma"] and pf["dw_wgrad_bx"] and mfma_shape), bwd_table
+    if wg_bx or (folded_bwd and wg1):
+        # nothing overwrites tA: the depthwise weight gradient still reads da2 there (wg_bx), or no dy1 is stored at all (wg1)
+        close16(tA, c16.r16(da2, dtype), dtype, "da2 (project dgrad, kept in tA)")
     if wg_bx:
-        close16(tA, c16.r16(da2, dtype), dtype, "da2 (project dgrad, kept for the depthwise weight gradient)")
-        d2g, _, _ = c16.bn_bwd(tA, y2, m2, i2, bnp[1]["weight"], pre2, True, train)
+        d2g, _, _ =c16.bn_bwd(tA, y2, m2, i2, bnp[1]["weight"], pre2, True, train)
         dy2_gpu = c16.r16(d2g, dtype)          # dy2 as both depthwise kernels form it from the stored (da2, y2)
     else:
         dy2_gpu = tC if folded_bwd else tA
@@ -323,6 +386,7 @@ def test_composite_block_16bit_vs_oracle(ora, case, bstat):
     close16(H(xg.grad), c16.r16(dxe.astype(np.float64) + dout, dtype), dtype, "dx (expand dgrad + shortcut)")
     for i, nm in enumerate(("inverted_bottleneck.bn.bn.", "depth_conv.bn.bn.")):
         assert np.all(grads[pfx + nm + "weight"][mid:] == 0) and np.all(grads[pfx + nm + "bias"][mid:] == 0)
+    return {k: fwd_table.get(k, 0) + bwd_table.get(k, 0) for k in set(fwd_table) | set(bwd_table)}
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -153,10 +153,16 @@ def test_static_conv_weight_gradients_on_the_side_stream():
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, None])
 def test_mb_stack_call_equals_block_by_block(dtype):
+    check_stack_equals_blocks(dtype)
+
+
+def check_stack_equals_blocks(dtype):
     """ops.FusedMBStackFn (one autograd node / foreign call for all active MB blocks, ofasr_mbstack_fwd / _bwd) against
     the block-by-block path (ops.FusedMBConvFn per block): same kernels in the same order, so outputs, every gradient and
-    its None-ness, and the BN buffers are bit-identical; sampled sub-networks with skipped blocks, bf16 and fp32."""
+    its None-ness, and the BN buffers are bit-identical; sampled sub-networks with skipped blocks, bf16 and fp32.
+    Returns the launch tables of the last sub-step, {True: of the stack call, False: block by block}."""
     ops, C = amd("ops"), amd("_C")
+    tables = {}
     net = _net()
     state = {k: v.clone() for k, v in net.state_dict().items()}
     lr = torch.rand(2, 3, 32, 32, device=DEV)
@@ -182,6 +188,7 @@ def test_mb_stack_call_equals_block_by_block(dtype):
                 ops.flush_deferred()
                 outs.append(out.detach().float().clone())
             torch.cuda.synchronize()
+            tables[stack] = C.launch_table()
             grads = {n: (None if p.grad is None else p.grad.detach().clone()) for n, p in net.named_parameters()}
             bufs = {k: v.clone() for k, v in net.state_dict().items() if "running_" in k or "num_batches" in k}
             return outs, grads, bufs
@@ -199,3 +206,4 @@ def test_mb_stack_call_equals_block_by_block(dtype):
     for k in b0:
         assert torch.equal(b0[k], b1[k]), k
     assert sum(g is None for g in g0.values()) > 0 and sum(g is not None for g in g0.values()) > 100
+    return tables

@@ -25,7 +25,7 @@ from placed import check, place, workspace
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BF16, F16 = torch.bfloat16, torch.float16
-CODE = {F16: 1, BF16: 2}
+CODE = {torch.float32: 0, F16: 1, BF16: 2}   # fp32: the rows of tests/test_hip_switches.py that call run() on fp32 operands
 TNAME = {F16: "ofasr::f16_t", BF16: "ofasr::bf16_t"}
 
 SHAPES = [
