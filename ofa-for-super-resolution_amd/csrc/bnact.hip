@@ -141,38 +141,23 @@ __global__ void __launch_bounds__(64) bn_finalize_kernel(const double* __restric
                                                          float* __restrict__ invstd_out, float* __restrict__ scale,
                                                          float* __restrict__ shift, int64_t* k0 = nullptr,
                                                          int64_t* k1 = nullptr, int64_t* k2 = nullptr) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {   // num_batches_tracked of the composite block's BNs ride along
-        if (k0) *k0 += 1;
-        if (k1) *k1 += 1;
-        if (k2) *k2 += 1;
-    }
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C) return;
-    double mean, var;
+    BnMoments m;
     if (training) {
         double s = 0.0, ss = 0.0;
         for (int p = 0; p < P; ++p) {
             s += partial[((long long)p * C + c) * 2];
             ss += partial[((long long)p * C + c) * 2 + 1];
         }
-        mean = s / M;
-        var = ss / M - mean * mean;
-        if (var < 0.0) var = 0.0;
-        if (running_mean) {
-            const double unb = M > 1.0 ? var * M / (M - 1.0) : var;
-            running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-            running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
-        }
+        m = bn_moments(s, ss, M);
     } else {
-        mean = (double)running_mean[c];
-        var = (double)running_var[c];
+        m = BnMoments{(double)running_mean[c], (double)running_var[c]};
     }
-    const double invstd = 1.0 / sqrt(var + eps);
-    const double g = gamma ? (double)gamma[c] : 1.0, b = beta ? (double)beta[c] : 0.0;
-    mean_out[c] = (float)mean;
-    invstd_out[c] = (float)invstd;
-    scale[c] = (float)(g * invstd);
-    shift[c] = (float)(b - mean * g * invstd);
+    int64_t* const k[3] = {k0, k1, k2};   // num_batches_tracked of the composite block's BNs ride along
+    bn_publish(BnStatsOut{mean_out, invstd_out, scale, shift, running_mean, running_var, momentum}, c, m,
+               bn_coef(m, eps, bn_affine(gamma, c, 1.0), bn_affine(beta, c, 0.0)), M, training && running_mean,
+               c == 0, k);
 }
 
 // --------------------------------------------------------------------------------- bn_act_fwd
@@ -204,10 +189,10 @@ __global__ void __launch_bounds__(BN_THREADS) bn_act_fwd_kernel(const T* __restr
     if (src.mode == 0) {
         sc = src.scale[c];
         mu = src.mean[c];
-        sh = fmaf(mu, sc, src.shift[c]);
+        sh = bn_beta(mu, sc, src.shift[c]);
     } else {
         // every block folds the (tiny) finalize into itself: no separate launch between the passes
-        double mean, var;
+        BnMoments m;
         if (src.mode == 3) {
             // up to ~1000 partials per channel: the block sums them cooperatively (fixed order), then broadcasts
             __shared__ double bc[2];
@@ -223,9 +208,7 @@ __global__ void __launch_bounds__(BN_THREADS) bn_act_fwd_kernel(const T* __restr
                 bc[1] = ss;
             }
             __syncthreads();
-            mean = bc[0] / src.M;
-            var = bc[1] / src.M - mean * mean;
-            if (var < 0.0) var = 0.0;
+            m = bn_moments(bc[0], bc[1], src.M);
         } else if (src.mode == 1) {
             double s = 0.0, ss = 0.0;
             __shared__ double ps[2][BN_THREADS];   // one request per thread, in-order sum from LDS (see bn_bwd_apply_kernel)
@@ -245,29 +228,16 @@ __global__ void __launch_bounds__(BN_THREADS) bn_act_fwd_kernel(const T* __restr
                     ss += src.partial[((long long)q * C + c) * 2 + 1];
                 }
             }
-            mean = s / src.M;
-            var = ss / src.M - mean * mean;
-            if (var < 0.0) var = 0.0;
+            m = bn_moments(s, ss, src.M);
         } else {
-            mean = (double)src.running_mean[c];
-            var = (double)src.running_var[c];
+            m = BnMoments{(double)src.running_mean[c], (double)src.running_var[c]};
         }
-        const double invstd = 1.0 / sqrt(var + src.eps);
-        const double g = src.gamma ? (double)src.gamma[c] : 1.0, b = src.beta ? (double)src.beta[c] : 0.0;
-        sc = (float)(g * invstd);
-        mu = (float)mean;
-        sh = (float)b;
-        if (p == 0 && threadIdx.x == 0) {
-            src.mean[c] = (float)mean;
-            src.invstd[c] = (float)invstd;
-            src.scale[c] = sc;
-            src.shift[c] = (float)(b - mean * g * invstd);
-            if ((src.mode == 1 || src.mode == 3) && src.running_mean) {
-                const double unb = src.M > 1.0 ? var * src.M / (src.M - 1.0) : var;
-                src.running_mean[c] = (float)((1.0 - src.momentum) * (double)src.running_mean[c] + src.momentum * mean);
-                src.running_var[c] = (float)((1.0 - src.momentum) * (double)src.running_var[c] + src.momentum * unb);
-            }
-        }
+        const BnCoef k = bn_coef(m, src.eps, bn_affine(src.gamma, c, 1.0), bn_affine(src.beta, c, 0.0));
+        sc = k.scale;
+        mu = (float)m.mean;
+        sh = k.beta;
+        if (p == 0 && threadIdx.x == 0)
+            bn_publish(src, c, m, k, src.M, (src.mode == 1 || src.mode == 3) && src.running_mean, false, {nullptr, nullptr, nullptr});
     }
     for (int n = p; n < N; n += P) {
         const long long off = ((long long)n * C + c) * HW;
@@ -282,18 +252,18 @@ __global__ void __launch_bounds__(BN_THREADS) bn_act_fwd_kernel(const T* __restr
                 if (RES) unpack16<T>(rv[i], r);
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
-                    float v = fmaf(f[j] - mu, sc, sh);
+                    float v = bn_pre(f[j], mu, sc, sh);
                     if (RES) v += r[j];
-                    if (ACT == 1) v = fminf(fmaxf(v, 0.f), 6.f);
+                    if (ACT == 1) v = relu6(v);
                     f[j] = v;
                 }
                 yv[i] = pack16<T>(f);
             }
         } else {
             for (int i = threadIdx.x; i < HW; i += BN_THREADS) {
-                float v = fmaf(to_float(x[off + i]) - mu, sc, sh);
+                float v = bn_pre(to_float(x[off + i]), mu, sc, sh);
                 if (RES) v += to_float(res[off + i]);
-                if (ACT == 1) v = fminf(fmaxf(v, 0.f), 6.f);
+                if (ACT == 1) v = relu6(v);
                 y[off + i] = from_float<T>(v);
             }
         }
@@ -313,7 +283,7 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_reduce_kernel(const T* __re
                                                                    double* __restrict__ partial, int N, int C, int HW,
                                                                    int P) {
     const int c = blockIdx.x, p = blockIdx.y;
-    const float sc = scale[c], mu = mean[c], is = invstd[c], sh = fmaf(mu, sc, shift[c]);
+    const float sc = scale[c], mu = mean[c], is = invstd[c], sh = bn_beta(mu, sc, shift[c]);
     double s = 0.0, sx = 0.0;
     for (int n = p; n < N; n += P) {
         const long long off = ((long long)n * C + c) * HW;
@@ -332,9 +302,9 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_reduce_kernel(const T* __re
                 for (int j = 0; j < V; ++j) {
                     float dz = g[j];
                     if (ACT == 1) {
-                        float pre = fmaf(f[j] - mu, sc, sh);
+                        float pre = bn_pre(f[j], mu, sc, sh);
                         if (RES) pre += r[j];
-                        dz = (pre > 0.f && pre < 6.f) ? dz : 0.f;
+                        dz = relu6_gate(pre, dz);
                     }
                     s8 += dz;
                     q8 = fmaf(dz, (f[j] - mu) * is, q8);
@@ -347,9 +317,9 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_reduce_kernel(const T* __re
                 const float xf = to_float(x[off + i]);
                 float dz = to_float(dy[off + i]);
                 if (ACT == 1) {
-                    float pre = fmaf(xf - mu, sc, sh);
+                    float pre = bn_pre(xf, mu, sc, sh);
                     if (RES) pre += to_float(res[off + i]);
-                    dz = (pre > 0.f && pre < 6.f) ? dz : 0.f;
+                    dz = relu6_gate(pre, dz);
                 }
                 s += (double)dz;
                 sx += (double)dz * (double)((xf - mu) * is);
@@ -377,7 +347,7 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_apply_kernel(const T* __res
                                                                   float* __restrict__ dbeta, int N, int C, int HW,
                                                                   int P) {
     const int c = blockIdx.x, p = blockIdx.y;
-    const float sc = scale[c], mu = mean[c], is = invstd[c], sh = fmaf(mu, sc, shift[c]);
+    const float sc = scale[c], mu = mean[c], is = invstd[c], sh = bn_beta(mu, sc, shift[c]);
     double s = 0.0, sx = 0.0;
     // the channel's Pred partial pairs: one request per thread and an in-order sum from LDS (same order, same result as
     // the serial loop, which costs Pred dependent L2 round trips before the block's first tensor request)
@@ -402,7 +372,8 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_apply_kernel(const T* __res
         if (dgamma) dgamma[c] = (float)sx;
         if (dbeta) dbeta[c] = (float)s;
     }
-    const float k1 = sc, ka = training ? (float)(s / M) : 0.f, kb = training ? (float)(sx / M) : 0.f;
+    float ka, kb;
+    bn_bwd_means(s, sx, M, training, ka, kb);
     for (int n = p; n < N; n += P) {
         const long long off = ((long long)n * C + c) * HW;
         if (VEC) {
@@ -421,12 +392,12 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_apply_kernel(const T* __res
                 for (int j = 0; j < V; ++j) {
                     float dz = g[j];
                     if (ACT == 1) {
-                        float pre = fmaf(f[j] - mu, sc, sh);
+                        float pre = bn_pre(f[j], mu, sc, sh);
                         if (RES) pre += r[j];
-                        dz = (pre > 0.f && pre < 6.f) ? dz : 0.f;
+                        dz = relu6_gate(pre, dz);
                     }
                     g[j] = dz;
-                    o[j] = k1 * (dz - ka - (f[j] - mu) * is * kb);
+                    o[j] = bn_bwd_dx(f[j] - mu, dz, sc, is, ka, kb);
                 }
                 ov[i] = pack16<T>(o);
                 if (orv) orv[i] = pack16<T>(g);
@@ -436,11 +407,11 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_apply_kernel(const T* __res
                 const float xf = to_float(x[off + i]);
                 float dz = to_float(dy[off + i]);
                 if (ACT == 1) {
-                    float pre = fmaf(xf - mu, sc, sh);
+                    float pre = bn_pre(xf, mu, sc, sh);
                     if (RES) pre += to_float(res[off + i]);
-                    dz = (pre > 0.f && pre < 6.f) ? dz : 0.f;
+                    dz = relu6_gate(pre, dz);
                 }
-                dx[off + i] = from_float<T>(k1 * (dz - ka - (xf - mu) * is * kb));
+                dx[off + i] = from_float<T>(bn_bwd_dx(xf - mu, dz, sc, is, ka, kb));
                 if (RES && dres) dres[off + i] = from_float<T>(dz);
             }
         }
@@ -513,7 +484,8 @@ __global__ void __launch_bounds__(BN1P_THREADS) bn_bwd_onepass_kernel(const T* _
         if (dgamma) dgamma[c] = (float)tsx;
         if (dbeta) dbeta[c] = (float)ts;
     }
-    const float ka = training ? (float)(ts / M) : 0.f, kb = training ? (float)(tsx / M) : 0.f;
+    float ka, kb;
+    bn_bwd_means(ts, tsx, M, training, ka, kb);
 #pragma unroll
     for (int j = 0; j < BN1P_MAXCH; ++j) {
         if (tid + j * BN1P_THREADS < total) {
@@ -521,7 +493,7 @@ __global__ void __launch_bounds__(BN1P_THREADS) bn_bwd_onepass_kernel(const T* _
             unpack16<T>(xv[j], f);
             unpack16<T>(dv[j], g);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = k1 * (g[e] - ka - (f[e] - mu) * is * kb);
+            for (int e = 0; e < 8; ++e) o[e] = bn_bwd_dx(f[e] - mu, g[e], k1, is, ka, kb);
             *reinterpret_cast<uint4*>(dx + off[j]) = pack16<T>(o);
         }
     }
@@ -536,26 +508,11 @@ __global__ void __launch_bounds__(64) bn_bwd_coef_kernel(const double* __restric
                                                          float* __restrict__ kbi) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C) return;
-    double s = 0.0, sx = 0.0;
-    for (int q0 = 0; q0 < Pred; q0 += 8) {
-        double a[8], b[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int q = q0 + j < Pred ? q0 + j : Pred - 1;
-            a[j] = partial[((long long)q * C + c) * 2];
-            b[j] = partial[((long long)q * C + c) * 2 + 1];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            s += q0 + j < Pred ? a[j] : 0.0;
-            sx += q0 + j < Pred ? b[j] : 0.0;
-        }
-    }
+    double s, sx;
+    bn_fold_pc2(partial, Pred, C, c, s, sx);
     if (dgamma) dgamma[c] = (float)sx;
     if (dbeta) dbeta[c] = (float)s;
-    const double sc = (double)scale[c];
-    ka[c] = training ? (float)(sc * (s / M)) : 0.f;
-    kbi[c] = training ? (float)(sc * (double)invstd[c] * (sx / M)) : 0.f;
+    bn_bwd_coef(s, sx, (double)scale[c], (double)invstd[c], M, training, ka[c], kbi[c]);
 }
 
 // the same from the [C][P] (sum dz, sum dz * (y - mean)) partials a producer kernel left (BwdStatOut): one wave per
@@ -566,33 +523,14 @@ __global__ void __launch_bounds__(64) bn_bwd_coef_cp_kernel(const float2* __rest
                                                             float* __restrict__ dbeta, float* __restrict__ ka,
                                                             float* __restrict__ kbi) {
     const int c = blockIdx.x;
-    const float2* pc = partial + (long long)c * P;
-    double s = 0.0, st = 0.0;
-    for (int q0 = threadIdx.x; q0 < P; q0 += 64 * 8) {
-        float2 v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int q = q0 + 64 * j;
-            v[j] = q < P ? pc[q] : make_float2(0.f, 0.f);
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            s += (double)v[j].x;
-            st += (double)v[j].y;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s += __shfl_xor(s, off, 64);
-        st += __shfl_xor(st, off, 64);
-    }
+    double s, st;
+    bn_fold_cp_wave(partial + (long long)c * P, P, (int)threadIdx.x, s, st);
     if (threadIdx.x == 0) {
-        const double is = (double)invstd[c], sc = (double)scale[c];
-        const double sx = st * is;          // sum dz * xhat
+        const double is = (double)invstd[c];
+        const double sx = st * is;          // the producer's convention: sum dz * (y - mean) -> sum dz * xhat
         if (dgamma) dgamma[c] = (float)sx;
         if (dbeta) dbeta[c] = (float)s;
-        ka[c] = training ? (float)(sc * (s / M)) : 0.f;
-        kbi[c] = training ? (float)(sc * is * (sx / M)) : 0.f;
+        bn_bwd_coef(s, sx, (double)scale[c], is, M, training, ka[c], kbi[c]);
     }
 }
 
@@ -695,8 +633,7 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_apply_ps_kernel(const uint4
         k1[j] = scale[c];
         mu[j] = mean[c];
         is[j] = invstd[c];
-        ka[j] = training ? (float)(s / M) : 0.f;
-        kb[j] = training ? (float)(sx / M) : 0.f;
+        bn_bwd_means(s, sx, M, training, ka[j], kb[j]);
     }
     const int items = H * Wq;
     const long long plane = (long long)H * Wq;
@@ -715,7 +652,7 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_apply_ps_kernel(const uint4
                 unpack16<T>(xv[j], f);
                 unpack16<T>(dz[j], gd);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = k1[j] * (gd[e] - ka[j] - (f[e] - mu[j]) * is[j] * kb[j]);
+                for (int e = 0; e < 8; ++e) o[e] = bn_bwd_dx(f[e] - mu[j], gd[e], k1[j], is[j], ka[j], kb[j]);
                 dx[off] = pack16<T>(o);
             }
         }
@@ -840,43 +777,19 @@ __global__ void __launch_bounds__(64) bn_finalize_cp_kernel(const float2* __rest
                                                             float* __restrict__ shift, int64_t* k0, int64_t* k1,
                                                             int64_t* k2) {
     const int c = blockIdx.x, lane = threadIdx.x;
-    if (c == 0 && lane == 0) {
-        if (k0) *k0 += 1;
-        if (k1) *k1 += 1;
-        if (k2) *k2 += 1;
-    }
-    double mean, var;
+    BnMoments m;
     if (training) {
-        double s = 0.0, ss = 0.0;
-        for (int p = lane; p < P; p += 64) {
-            const float2 v = partial[(long long)c * P + p];
-            s += (double)v.x;
-            ss += (double)v.y;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s += __shfl_xor(s, o, 64);
-            ss += __shfl_xor(ss, o, 64);
-        }
-        mean = s / M;
-        var = ss / M - mean * mean;
-        if (var < 0.0) var = 0.0;
+        double s, ss;
+        bn_fold_cp_wave(partial + (long long)c * P, P, lane, s, ss);
+        m = bn_moments(s, ss, M);
     } else {
-        mean = (double)running_mean[c];
-        var = (double)running_var[c];
+        m = BnMoments{(double)running_mean[c], (double)running_var[c]};
     }
     if (lane != 0) return;
-    if (training && running_mean) {
-        const double unb = M > 1.0 ? var * M / (M - 1.0) : var;
-        running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-        running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
-    }
-    const double invstd = 1.0 / sqrt(var + eps);
-    const double g = gamma ? (double)gamma[c] : 1.0, b = beta ? (double)beta[c] : 0.0;
-    mean_out[c] = (float)mean;
-    invstd_out[c] = (float)invstd;
-    scale[c] = (float)(g * invstd);
-    shift[c] = (float)(b - mean * g * invstd);
+    int64_t* const k[3] = {k0, k1, k2};
+    bn_publish(BnStatsOut{mean_out, invstd_out, scale, shift, running_mean, running_var, momentum}, c, m,
+               bn_coef(m, eps, bn_affine(gamma, c, 1.0), bn_affine(beta, c, 0.0)), M, training && running_mean,
+               c == 0, k);
 }
 
 int bn_finalize_cp(const float2* partial, int64_t P, int64_t C, double count, const float* gamma, const float* beta,

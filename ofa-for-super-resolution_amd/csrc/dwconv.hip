@@ -375,56 +375,11 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_mfma_kernel(const T* __restr
     float xsc = 1.f, xmu = 0.f, xb = 0.f;   // fused BN + ReLU6 of the input plane (wave-uniform)
     if constexpr (XF) {
         if (fold.cp) {
-            double s = 0.0, ss = 0.0;
-            // 8 partials per lane and request round (clamped index: the loads are in flight together), same order
-            for (int q0 = lane; q0 < fold.P; q0 += 8 * 64) {
-                float2 v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int q = q0 + 64 * j < fold.P ? q0 + 64 * j : fold.P - 1;
-                    v[j] = fold.cp[(long long)c * fold.P + q];
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const bool live = q0 + 64 * j < fold.P;
-                    s += live ? (double)v[j].x : 0.0;
-                    ss += live ? (double)v[j].y : 0.0;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                s += __shfl_xor(s, o, 64);
-                ss += __shfl_xor(ss, o, 64);
-            }
-            const double mean = s / fold.M;
-            double var = ss / fold.M - mean * mean;
-            var = var < 0.0 ? 0.0 : var;
-            const double invstd = 1.0 / sqrt(var + fold.eps);
-            const double gm = fold.gamma ? (double)fold.gamma[c] : 1.0, bt = fold.beta ? (double)fold.beta[c] : 0.0;
-            xsc = (float)(gm * invstd);
-            xmu = (float)mean;
-            xb = (float)bt;
-            if (n0 == 0 && lane == 0) {   // image group 0's wave of channel c keeps the statistics
-                fold.mean[c] = (float)mean;
-                fold.invstd[c] = (float)invstd;
-                fold.scale[c] = xsc;
-                fold.shift[c] = (float)(bt - mean * gm * invstd);
-                if (fold.running_mean) {
-                    const double unb = fold.M > 1.0 ? var * fold.M / (fold.M - 1.0) : var;
-                    fold.running_mean[c] =
-                        (float)((1.0 - fold.momentum) * (double)fold.running_mean[c] + fold.momentum * mean);
-                    fold.running_var[c] = (float)((1.0 - fold.momentum) * (double)fold.running_var[c] + fold.momentum * unb);
-                }
-                if (c == 0) {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        if (fold.counters[i]) *fold.counters[i] += 1;
-                }
-            }
+            bn_fold_wave(fold, c, lane, n0 == 0 && lane == 0, xsc, xmu, xb);   // image group 0's wave keeps the statistics
         } else {
             xsc = xf.scale[c];
             xmu = xf.mean[c];
-            xb = fmaf(xmu, xsc, xf.shift[c]);
+            xb = bn_beta(xmu, xsc, xf.shift[c]);
         }
     }
 
@@ -432,7 +387,7 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_mfma_kernel(const T* __restr
     if constexpr (BX) {
         bmu = bx.mean[c];
         bsc = bx.scale[c];
-        bxb = fmaf(bmu, bsc, bx.shift[c]);
+        bxb = bn_beta(bmu, bsc, bx.shift[c]);
         if (bx.fold_partial) bwdxf_fold(bx, c, bsc, n0 == 0 && lane == 0, bka, bkbi);   // wave-uniform; image group 0 publishes
         else {
             bka = bx.ka[c];
@@ -480,36 +435,9 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_mfma_kernel(const T* __restr
             const int idx = lane + 64 * it;
             if (idx < nchunks) {
                 uint4 v = nxt[it];
-                if constexpr (XF) {
-                    uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        T lo, hi;
-                        lo.v = (uint16_t)(wv[i] & 0xffffu);
-                        hi.v = (uint16_t)(wv[i] >> 16);
-                        const float a = fminf(fmaxf(fmaf(to_float(lo) - xmu, xsc, xb), 0.f), 6.f);
-                        const float b = fminf(fmaxf(fmaf(to_float(hi) - xmu, xsc, xb), 0.f), 6.f);
-                        wv[i] = pack2<T>(a, b);
-                    }
-                    v = make_uint4(wv[0], wv[1], wv[2], wv[3]);
-                }
-                if constexpr (BX) {   // dy = scale*dz - ka - (y - mean)*kbi, dz = da inside the ReLU6 window of BN(y)
-                    uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-                    const uint32_t yv[4] = {nxt2[it].x, nxt2[it].y, nxt2[it].z, nxt2[it].w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        T lo, hi, ylo, yhi;
-                        lo.v = (uint16_t)(wv[i] & 0xffffu);
-                        hi.v = (uint16_t)(wv[i] >> 16);
-                        ylo.v = (uint16_t)(yv[i] & 0xffffu);
-                        yhi.v = (uint16_t)(yv[i] >> 16);
-                        const float t0 = to_float(ylo) - bmu, t1 = to_float(yhi) - bmu;
-                        const float p0 = fmaf(t0, bsc, bxb), p1 = fmaf(t1, bsc, bxb);
-                        const float z0 = (p0 > 0.f && p0 < 6.f) ? to_float(lo) : 0.f;
-                        const float z1 = (p1 > 0.f && p1 < 6.f) ? to_float(hi) : 0.f;
-                        wv[i] = pack2<T>(fmaf(-t0, bkbi, fmaf(bsc, z0, -bka)), fmaf(-t1, bkbi, fmaf(bsc, z1, -bka)));
-                    }
-                    v = make_uint4(wv[0], wv[1], wv[2], wv[3]);
+                if constexpr (XF) v = xf_apply8_core<T>(v, xsc, xmu, xb);
+                if constexpr (BX) {   // dy from (da, y): the fused-read form of the BN(+ReLU6) backward
+                    v = bx_apply8<T>(v, nxt2[it], bmu, bsc, bxb, bka, bkbi);
                     if (bx.dy_out)   // wave-uniform: the plane's dy, once, for the weight-gradient kernel
                         reinterpret_cast<uint4*>(reinterpret_cast<T*>(bx.dy_out) + plane * (long long)H * W)[idx] = v;
                 }
@@ -619,7 +547,7 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_vec_kernel(const T* __restri
     if constexpr (BX) {
         bmu = bx.mean[c];
         bsc = bx.scale[c];
-        bxb = fmaf(bmu, bsc, bx.shift[c]);
+        bxb = bn_beta(bmu, bsc, bx.shift[c]);
         if (bx.fold_partial) bwdxf_fold(bx, c, bsc, plane < C && slab == 0 && lane == 0, bka, bkbi);   // wave-uniform
         else {
             bka = bx.ka[c];
@@ -629,57 +557,12 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_vec_kernel(const T* __restri
     float xsc = 1.f, xmu = 0.f, xb = 0.f;            // fused BN + ReLU6 of the input plane (wave-uniform)
     if constexpr (XF) {
         if (fold.cp) {
-            // the input BN's finalize, per wave: channel c from its P partials (lanes stride, fp64 butterfly: fixed order)
-            double s = 0.0, ss = 0.0;
-            // 8 partials per lane and request round (clamped index: the loads are in flight together), same order
-            for (int q0 = lane; q0 < fold.P; q0 += 8 * 64) {
-                float2 v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int q = q0 + 64 * j < fold.P ? q0 + 64 * j : fold.P - 1;
-                    v[j] = fold.cp[(long long)c * fold.P + q];
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const bool live = q0 + 64 * j < fold.P;
-                    s += live ? (double)v[j].x : 0.0;
-                    ss += live ? (double)v[j].y : 0.0;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                s += __shfl_xor(s, o, 64);
-                ss += __shfl_xor(ss, o, 64);
-            }
-            const double mean = s / fold.M;
-            double var = ss / fold.M - mean * mean;
-            var = var < 0.0 ? 0.0 : var;
-            const double invstd = 1.0 / sqrt(var + fold.eps);
-            const double gm = fold.gamma ? (double)fold.gamma[c] : 1.0, bt = fold.beta ? (double)fold.beta[c] : 0.0;
-            xsc = (float)(gm * invstd);
-            xmu = (float)mean;
-            xb = (float)bt;
-            if (plane < C && slab == 0 && lane == 0) {   // image 0's wave of channel c keeps the statistics
-                fold.mean[c] = (float)mean;
-                fold.invstd[c] = (float)invstd;
-                fold.scale[c] = xsc;
-                fold.shift[c] = (float)(bt - mean * gm * invstd);
-                if (fold.running_mean) {
-                    const double unb = fold.M > 1.0 ? var * fold.M / (fold.M - 1.0) : var;
-                    fold.running_mean[c] =
-                        (float)((1.0 - fold.momentum) * (double)fold.running_mean[c] + fold.momentum * mean);
-                    fold.running_var[c] = (float)((1.0 - fold.momentum) * (double)fold.running_var[c] + fold.momentum * unb);
-                }
-                if (c == 0) {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        if (fold.counters[i]) *fold.counters[i] += 1;
-                }
-            }
+            // the input BN's finalize, per wave; image 0's wave of channel c keeps the statistics
+            bn_fold_wave(fold, c, lane, plane < C && slab == 0 && lane == 0, xsc, xmu, xb);
         } else {
             xsc = xf.scale[c];
             xmu = xf.mean[c];
-            xb = fmaf(xmu, xsc, xf.shift[c]);
+            xb = bn_beta(xmu, xsc, xf.shift[c]);
         }
     }
 
@@ -728,7 +611,7 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_vec_kernel(const T* __restri
             if constexpr (XF) {   // rows outside the image are the convolution's zero padding, not relu6(beta)
                 const bool rv = live && t < niter && hin >= 0 && hin < H;
 #pragma unroll
-                for (int p = 0; p < PXL; ++p) v[p] = rv ? fminf(fmaxf(fmaf(v[p] - xmu, xsc, xb), 0.f), 6.f) : 0.f;
+                for (int p = 0; p < PXL; ++p) v[p] = rv ? relu6(bn_pre(v[p], xmu, xsc, xb)) : 0.f;
             }
             if constexpr (BX) {   // dy = scale*dz - ka - (y - mean)*kbi; rows outside the image are zero padding
                 float yv[PXL];
@@ -736,9 +619,8 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_vec_kernel(const T* __restri
                 const bool rv = live && t < niter && hin >= 0 && hin < H;
 #pragma unroll
                 for (int p = 0; p < PXL; ++p) {
-                    const float tt = yv[p] - bmu, pre = fmaf(tt, bsc, bxb);
-                    const float dz = (pre > 0.f && pre < 6.f) ? v[p] : 0.f;
-                    v[p] = rv ? fmaf(-tt, bkbi, fmaf(bsc, dz, -bka)) : 0.f;
+                    const float dz = relu6_gate(bn_pre(yv[p], bmu, bsc, bxb), v[p]);
+                    v[p] = rv ? bn_bwd_dy(yv[p] - bmu, dz, bsc, bka, bkbi) : 0.f;
                 }
                 raw2[u] = load_row2(t + K);
                 // rows [h0, h1) belong to this lane group (halo rows are some other group's): each dy row is stored once
@@ -825,13 +707,13 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_wgrad_vec_kernel(const T* __
         const int c = (int)(plane % C);
         xsc = xf.scale[c];
         xmu = xf.mean[c];
-        xb = fmaf(xmu, xsc, xf.shift[c]);
+        xb = bn_beta(xmu, xsc, xf.shift[c]);
     }
     auto xform = [&](float* v, int r) {   // r = image row of the values; rows outside the image are zero
         const bool rv = x_ok(r);
         if constexpr (XF) {
 #pragma unroll
-            for (int p = 0; p < PXL; ++p) v[p] = rv ? fminf(fmaxf(fmaf(v[p] - xmu, xsc, xb), 0.f), 6.f) : 0.f;
+            for (int p = 0; p < PXL; ++p) v[p] = rv ? relu6(bn_pre(v[p], xmu, xsc, xb)) : 0.f;
         } else {
 #pragma unroll
             for (int p = 0; p < PXL; ++p) v[p] = rv ? v[p] : 0.f;
@@ -1077,13 +959,13 @@ __global__ void __launch_bounds__(DWG_THREADS) dw_wgrad_mfma_kernel(const T* __r
     if constexpr (XF) {
         mu = xf.mean[c];
         sc = xf.scale[c];
-        be = fmaf(mu, sc, xf.shift[c]);
+        be = bn_beta(mu, sc, xf.shift[c]);
     }
     float bmu = 0.f, bsc = 1.f, bxb = 0.f, bka = 0.f, bkbi = 0.f;
     if constexpr (GBX) {
         bmu = bx.mean[c];
         bsc = bx.scale[c];
-        bxb = fmaf(bmu, bsc, bx.shift[c]);
+        bxb = bn_beta(bmu, bsc, bx.shift[c]);
         bka = bx.ka[c];
         bkbi = bx.kbi[c];
     }
@@ -1109,34 +991,10 @@ __global__ void __launch_bounds__(DWG_THREADS) dw_wgrad_mfma_kernel(const T* __r
     auto store = [&](int b) {
         if (mine) {
             uint4 a = ga;
-            if constexpr (XF) {   // the activated operand relu6(BN(y)) as the matrix cores see it (16-bit)
-                const uint32_t w[4] = {ga.x, ga.y, ga.z, ga.w};
-                uint32_t o[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float lo, hi;
-                    unpack2<T>(w[i], lo, hi);
-                    o[i] = pack2<T>(fminf(fmaxf(fmaf(lo - mu, sc, be), 0.f), 6.f), fminf(fmaxf(fmaf(hi - mu, sc, be), 0.f), 6.f));
-                }
-                a = make_uint4(o[0], o[1], o[2], o[3]);
-            }
+            if constexpr (XF) a = xf_apply8_core<T>(a, sc, mu, be);   // the activated operand as the matrix cores see it (16-bit)
             uint4 g = gg;
-            if constexpr (GBX) {   // dy = scale*dz - ka - (y - mean)*kbi, dz = da inside the ReLU6 window of BN(y): the arithmetic
-                                   // of dw_mfma_kernel's BX staging, so the weight gradient sees the dy the input gradient saw
-                const uint32_t wv[4] = {gg.x, gg.y, gg.z, gg.w}, yv[4] = {gy.x, gy.y, gy.z, gy.w};
-                uint32_t o[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float d0, d1, y0, y1;
-                    unpack2<T>(wv[i], d0, d1);
-                    unpack2<T>(yv[i], y0, y1);
-                    const float t0 = y0 - bmu, t1 = y1 - bmu;
-                    const float p0 = fmaf(t0, bsc, bxb), p1 = fmaf(t1, bsc, bxb);
-                    const float z0 = (p0 > 0.f && p0 < 6.f) ? d0 : 0.f, z1 = (p1 > 0.f && p1 < 6.f) ? d1 : 0.f;
-                    o[i] = pack2<T>(fmaf(-t0, bkbi, fmaf(bsc, z0, -bka)), fmaf(-t1, bkbi, fmaf(bsc, z1, -bka)));
-                }
-                g = make_uint4(o[0], o[1], o[2], o[3]);
-            }
+            // the arithmetic of dw_mfma_kernel's BX staging, so the weight gradient sees the dy the input gradient saw
+            if constexpr (GBX) g = bx_apply8<T>(gg, gy, bmu, bsc, bxb, bka, bkbi);
             *reinterpret_cast<uint4*>(lds[b] + (row + P) * (DWG_PITCH * 2) + col8 * 16) = a;
             *reinterpret_cast<uint4*>(lds[b] + A_BYTES + row * (DWG_PITCH * 2) + col8 * 16) = g;
         }

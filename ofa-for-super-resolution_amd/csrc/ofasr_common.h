@@ -175,86 +175,11 @@ template <> struct uint_of<8> { using type = uint64_t; };
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Optional BatchNorm + ReLU6 applied to an operand as a kernel reads it (the composite MB block never materialises
-// the activated tensor): v -> min(max((v - mean[c]) * scale[c] + beta[c], 0), 6) with beta = shift + mean*scale.
-// Zero padding / out-of-range elements stay exactly zero.  All pointers null = plain read.
-struct InputXf {
-    const float* scale;
-    const float* shift;
-    const float* mean;
-};
+}  // namespace ofasr
+// the BatchNorm rules of the training path and the operand transforms (InputXf, BwdXf, BwdStatOut, BnFold, StatOut)
+#include "bn_math.h"
+namespace ofasr {
 
-// BatchNorm(+ReLU6) BACKWARD applied to an operand as a kernel reads it: the gradient dy of the pre-BN tensor y is
-//     t = y - mean;  pre = t*scale + beta;  dz = (0 < pre < 6) ? da : 0;  dy = scale*dz - ka - t*kbi
-// (ka = scale * mean(dz), kbi = scale * invstd * mean(dz * xhat); both 0 for eval-mode BN) formed from the incoming
-// gradient da and y on the fly, so the "apply" pass of the BN backward -- read da, read y, write dy -- never runs and dy
-// is a pass of its own no more.  The per-channel sums behind ka / kbi come from bn_bwd_reduce_coef.  The kernel that
-// consumes dy on the input-gradient chain also stores it once (dy_out, may be null) for the weight-gradient kernel on the
-// side stream: compared with the separate pass the chain moves one tensor less (no second read of da) and loses a
-// launch, and the side stream reads what it read before.  y == nullptr: plain read.
-struct BwdXf {
-    const void* y;        // the pre-BN tensor, same shape and element type as the gradient operand
-    const float* mean;
-    const float* scale;   // gamma * invstd
-    const float* shift;   // beta - mean * scale
-    const float* ka;
-    const float* kbi;
-    void* dy_out;         // where the consumer leaves dy (same shape / element type), or nullptr
-    // Optional: the consumer folds the reduction pass's partial slabs itself (no coefficient launch between the two).
-    // fold_partial[(q * C + c) * 2 + {0, 1}] = (sum dz, sum dz * xhat) of part q < fold_P (bn_bwd_reduce_kernel's layout),
-    // folded in fp64 in the order q = 0 .. fold_P-1 exactly as bn_bwd_coef_kernel does; ka / kbi above are then ignored.
-    // ONE designated unit per channel also writes dgamma / dbeta and (coef_ka, coef_kbi) -- the latter for a later kernel
-    // that takes finished coefficients (the side stream's weight gradient).
-    const double* fold_partial;
-    int fold_P, fold_C, fold_training;
-    double fold_M;
-    const float* fold_invstd;
-    float* fold_dgamma;
-    float* fold_dbeta;
-    float* coef_ka;
-    float* coef_kbi;
-};
-#if defined(__HIPCC__)
-// (ka, kbi) of channel c from the partial slabs; `writer`: this unit also publishes dgamma / dbeta / the coefficients
-__device__ __forceinline__ void bwdxf_fold(const BwdXf& bx, int c, float sc, bool writer, float& ka, float& kbi) {
-    double s = 0.0, sx = 0.0;
-    for (int q0 = 0; q0 < bx.fold_P; q0 += 8) {      // the loads of a round requested together, summed in order
-        double a[8], b[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int q = q0 + j < bx.fold_P ? q0 + j : bx.fold_P - 1;
-            a[j] = bx.fold_partial[((long long)q * bx.fold_C + c) * 2];
-            b[j] = bx.fold_partial[((long long)q * bx.fold_C + c) * 2 + 1];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            s += q0 + j < bx.fold_P ? a[j] : 0.0;
-            sx += q0 + j < bx.fold_P ? b[j] : 0.0;
-        }
-    }
-    ka = bx.fold_training ? (float)((double)sc * (s / bx.fold_M)) : 0.f;
-    kbi = bx.fold_training ? (float)((double)sc * (double)bx.fold_invstd[c] * (sx / bx.fold_M)) : 0.f;
-    if (writer) {
-        if (bx.fold_dgamma) bx.fold_dgamma[c] = (float)sx;
-        if (bx.fold_dbeta) bx.fold_dbeta[c] = (float)s;
-        if (bx.coef_ka) bx.coef_ka[c] = ka;
-        if (bx.coef_kbi) bx.coef_kbi[c] = kbi;
-    }
-}
-#endif
-// The REDUCTION pass of the same backward folded into the kernel that produces da (the gradient of the activated
-// tensor): the producer reads y at the positions it writes and leaves, per channel c and producer unit p (a pixel tile,
-// a plane slab), partial[c * P + p] = (sum dz, sum dz * (y - mean)) with dz as above and da as stored; bn_bwd_coef_cp
-// folds the P partials of a channel in fp64 in a fixed order into dgamma, dbeta, ka, kbi.  The chain loses the pass
-// "read da, read y" and its launch; the producer reads y (one tensor) more.
-struct BwdStatOut {
-    const void* y;
-    const float* mean;
-    const float* scale;
-    const float* shift;
-    float2* partial;
-    int P;
-};
 int bn_bwd_coef_cp(const float2* partial, int64_t P, int64_t C, double count, int training, const float* scale,
                    const float* invstd, float* dgamma, float* dbeta, float* ka, float* kbi, void* stream);
 bool pwconv_dgrad_bstat_supported(const void* dy, const void* y, const void* dx, const float* w, int64_t ldw, int64_t Cin,
@@ -272,25 +197,6 @@ int bn_bwd_reduce_coef(const void* dy, const void* x, const float* scale, const 
 int bn_bwd_reduce_only(const void* dy, const void* x, const float* scale, const float* shift, const float* mean,
                        const float* invstd, int64_t N, int64_t C, int64_t HW, int act, int dtype, void* workspace,
                        size_t workspace_bytes, int* P_out, void* stream);
-
-// A consumer kernel can fold the producer's epilogue partials itself (no finalize launch between the two): every
-// block derives scale / mean / beta of the channels it reads from partial[c * P + 0..P) in fp64 in a fixed order, and
-// one designated block also writes mean | invstd | scale | shift (kept for the backward) and the running statistics.
-// cp == nullptr: not used (the InputXf pointers hold finalized values).
-struct BnFold {
-    const float2* cp;
-    int P;
-    double M, momentum, eps;
-    const float* gamma;
-    const float* beta;
-    float* running_mean;
-    float* running_var;
-    float* mean;
-    float* invstd;
-    float* scale;
-    float* shift;
-    int64_t* counters[3];   // num_batches_tracked of the block's BNs, bumped once by the designated writer (may be null)
-};
 
 #if defined(__HIPCC__)
 // BatchNorm statistics epilogue: v[reg] is this lane's partial sum for accumulator register reg (row (reg & 3) + 8 * (reg >> 2) + 4 * h).
@@ -333,13 +239,6 @@ __device__ __forceinline__ int half_wave_row_reg(int c) { return ((c >> 4) & 1) 
 
 #endif
 
-// Optional BatchNorm statistics of the tensor a conv kernel writes: every producer unit p (a pixel tile, a plane slab)
-// leaves its per-channel (sum, sum of squares) at partial[c * P + p] -- fp32 over <= a few thousand values -- and
-// bn_finalize_cp folds the P partials of a channel in fp64 in a fixed order.  partial == nullptr: no statistics.
-struct StatOut {
-    float2* partial;
-    int P;
-};
 // number of producer units per channel of the kernels that take a StatOut
 int dwconv_stat_units(int64_t N, int64_t H, int64_t W, int K, int dtype);
 int pwconv_stat_units(int64_t N, int64_t Cin, int64_t HW);

@@ -242,50 +242,6 @@ __device__ __forceinline__ int pos16(int q) {
     return PX == 4 ? (32 * (q & 3) + (q >> 2)) : (64 * (q >> 6) + 32 * (q & 1) + ((q & 63) >> 1));
 }
 
-// fused BN + ReLU6 of 8 packed 16-bit values of channel ch (InputXf, ofasr_common.h)
-template <typename T>
-__device__ __forceinline__ uint4 xf_apply8_core(uint4 v, float sc, float mu, float b);
-template <typename T>
-__device__ __forceinline__ uint4 xf_apply8(uint4 v, const InputXf& xf, int ch) {
-    const float sc = xf.scale[ch], mu = xf.mean[ch];
-    return xf_apply8_core<T>(v, sc, mu, fmaf(mu, sc, xf.shift[ch]));
-}
-template <typename T>
-__device__ __forceinline__ uint4 xf_apply8_core(uint4 v, float sc, float mu, float b) {
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        T lo, hi;
-        lo.v = (uint16_t)(w[i] & 0xffffu);
-        hi.v = (uint16_t)(w[i] >> 16);
-        const float a = fminf(fmaxf(fmaf(to_float(lo) - mu, sc, b), 0.f), 6.f);
-        const float c = fminf(fmaxf(fmaf(to_float(hi) - mu, sc, b), 0.f), 6.f);
-        w[i] = pack2<T>(a, c);
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// BN(+ReLU6) backward of 8 packed gradient values `g` of one channel given the 8 pre-BN values `yv` (BwdXf)
-template <typename T>
-__device__ __forceinline__ uint4 bx_apply8(uint4 g, uint4 yv, float mu, float sc, float xb, float ka, float kbi) {
-    uint32_t w[4] = {g.x, g.y, g.z, g.w};
-    const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        T lo, hi, ylo, yhi;
-        lo.v = (uint16_t)(w[i] & 0xffffu);
-        hi.v = (uint16_t)(w[i] >> 16);
-        ylo.v = (uint16_t)(yw[i] & 0xffffu);
-        yhi.v = (uint16_t)(yw[i] >> 16);
-        const float t0 = to_float(ylo) - mu, t1 = to_float(yhi) - mu;
-        const float p0 = fmaf(t0, sc, xb), p1 = fmaf(t1, sc, xb);
-        const float z0 = (p0 > 0.f && p0 < 6.f) ? to_float(lo) : 0.f;
-        const float z1 = (p1 > 0.f && p1 < 6.f) ? to_float(hi) : 0.f;
-        w[i] = pack2<T>(fmaf(-t0, kbi, fmaf(sc, z0, -ka)), fmaf(-t1, kbi, fmaf(sc, z1, -ka)));
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // A [64 channels x 128 pixels] X chunk in registers (aligned tensors: 16-byte vectors wholly inside or outside): request
 // = all vectors issued branch-free (a vector outside the tensor reads the image's first one), deposit = fused BN + ReLU6
 // where asked for, zero the outside ones, write the staging layout of stage_x_tile.
@@ -710,7 +666,7 @@ pw_fanout_slabs_kernel(const T* __restrict__ x, WView wv, T* __restrict__ y, int
     if constexpr (STAT == 2) {
         for (int i = threadIdx.x; i < NSLAB * FO_ROWS; i += PW_THREADS) {
             const float mu = bs.mean[i], sc = bs.scale[i];
-            btab[i] = make_float4(mu, sc, fmaf(mu, sc, bs.shift[i]), 0.f);
+            btab[i] = make_float4(mu, sc, bn_beta(mu, sc, bs.shift[i]), 0.f);
         }
     }
     const int lane = lane_id();
@@ -786,8 +742,7 @@ pw_fanout_slabs_kernel(const T* __restrict__ x, WView wv, T* __restrict__ y, int
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const float tt = yv[t] - cst.x;
-                    const float pre = fmaf(tt, cst.y, cst.z);
-                    const float dz = (pre > 0.f && pre < 6.f) ? da[t] : 0.f;
+                    const float dz = relu6_gate(bn_pre(yv[t], cst.x, cst.y, cst.z), da[t]);
                     ss += dz;
                     qq = fmaf(dz, tt, qq);
                 }
@@ -988,7 +943,7 @@ __global__ void __launch_bounds__(PW_THREADS) pw_fanin_pipe_kernel(const T* __re
             const float mu = bx.mean[ch], sc = bx.scale[ch];
             bxt[ch] = mu;
             bxt[FOLD_KMAX + ch] = sc;
-            bxt[2 * FOLD_KMAX + ch] = fmaf(mu, sc, bx.shift[ch]);
+            bxt[2 * FOLD_KMAX + ch] = bn_beta(mu, sc, bx.shift[ch]);
             if (bx.fold_partial) {   // workgroup-uniform: fold the reduction pass's partial slabs here; block (0, 0) publishes
                 float ka, kbi;
                 bwdxf_fold(bx, ch, sc, blockIdx.x == 0 && blockIdx.y == 0, ka, kbi);
@@ -1006,44 +961,9 @@ __global__ void __launch_bounds__(PW_THREADS) pw_fanin_pipe_kernel(const T* __re
         if (folded) {   // the input BN's finalize, per block: channel ch from its P partials, fixed order, fp64
             const bool writer = blockIdx.x == 0 && blockIdx.y == 0;
             for (int ch = tid; ch < wv.K; ch += PW_THREADS) {
-                double s = 0.0, ss = 0.0;
-                // 8 partials per request round (clamped index, so the 8 loads are in flight together), summed in order:
-                // the same result as one load per iteration, which is P dependent L2 round trips per channel
-                for (int q0 = 0; q0 < fold.P; q0 += 8) {
-                    float2 v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int q = q0 + j < fold.P ? q0 + j : fold.P - 1;
-                        v[j] = fold.cp[(long long)ch * fold.P + q];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const bool live = q0 + j < fold.P;
-                        s += live ? (double)v[j].x : 0.0;
-                        ss += live ? (double)v[j].y : 0.0;
-                    }
-                }
-                const double mean = s / fold.M;
-                double var = ss / fold.M - mean * mean;
-                var = var < 0.0 ? 0.0 : var;
-                const double invstd = 1.0 / sqrt(var + fold.eps);
-                const double g = fold.gamma ? (double)fold.gamma[ch] : 1.0, b = fold.beta ? (double)fold.beta[ch] : 0.0;
-                fsc[ch] = (float)(g * invstd);
-                fmu[ch] = (float)mean;
-                fb[ch] = (float)b;
-                if (writer) {
-                    fold.mean[ch] = (float)mean;
-                    fold.invstd[ch] = (float)invstd;
-                    fold.scale[ch] = (float)(g * invstd);
-                    fold.shift[ch] = (float)(b - mean * g * invstd);
-                    if (fold.running_mean) {
-                        const double unb = fold.M > 1.0 ? var * fold.M / (fold.M - 1.0) : var;
-                        fold.running_mean[ch] =
-                            (float)((1.0 - fold.momentum) * (double)fold.running_mean[ch] + fold.momentum * mean);
-                        fold.running_var[ch] =
-                            (float)((1.0 - fold.momentum) * (double)fold.running_var[ch] + fold.momentum * unb);
-                    }
-                }
+                double s, ss;
+                bn_fold_cp(fold.cp + (long long)ch * fold.P, fold.P, s, ss);
+                bn_fold_finish(fold, ch, s, ss, writer, fsc[ch], fmu[ch], fb[ch]);
             }
             __syncthreads();
         }
@@ -1557,7 +1477,7 @@ __device__ __forceinline__ void wd_stream_body(const T* __restrict__ R, const T*
         const int rc = rs ? wrow0 + c : MR - 1;
         xsc = xf.scale[rc];
         xmu = xf.mean[rc];
-        xb = fmaf(xmu, xsc, xf.shift[rc]);
+        xb = bn_beta(xmu, xsc, xf.shift[rc]);
         asm volatile("" : "+v"(xsc), "+v"(xmu), "+v"(xb));
     }
     if constexpr (XF == 2) {
@@ -1566,7 +1486,7 @@ __device__ __forceinline__ void wd_stream_body(const T* __restrict__ R, const T*
             const int colc = cs[cb] ? 32 * cb + c : NS - 1;
             csc[cb] = xf.scale[colc];
             cmu[cb] = xf.mean[colc];
-            cbb[cb] = fmaf(cmu[cb], csc[cb], xf.shift[colc]);
+            cbb[cb] = bn_beta(cmu[cb], csc[cb], xf.shift[colc]);
             asm volatile("" : "+v"(csc[cb]), "+v"(cmu[cb]), "+v"(cbb[cb]));
         }
     }
@@ -1712,13 +1632,13 @@ __global__ void __launch_bounds__(512) pw_wgrad_direct_kernel(const T* __restric
         for (int rb = 0; rb < WD_RB; ++rb) {
             xsc[rb] = xf.scale[rowc[rb]];
             xmu[rb] = xf.mean[rowc[rb]];
-            xb[rb] = fmaf(xmu[rb], xsc[rb], xf.shift[rowc[rb]]);
+            xb[rb] = bn_beta(xmu[rb], xsc[rb], xf.shift[rowc[rb]]);
         }
     }
     if constexpr (XF == 2) {
         csc = xf.scale[colc];
         cmu = xf.mean[colc];
-        cbb = fmaf(cmu, csc, xf.shift[colc]);
+        cbb = bn_beta(cmu, csc, xf.shift[colc]);
     }
     float bka[WD_RB], bkbi[WD_RB];
     if constexpr (XF == 3) {
@@ -1726,7 +1646,7 @@ __global__ void __launch_bounds__(512) pw_wgrad_direct_kernel(const T* __restric
         for (int rb = 0; rb < WD_RB; ++rb) {
             xsc[rb] = bx.scale[rowc[rb]];
             xmu[rb] = bx.mean[rowc[rb]];
-            xb[rb] = fmaf(xmu[rb], xsc[rb], bx.shift[rowc[rb]]);
+            xb[rb] = bn_beta(xmu[rb], xsc[rb], bx.shift[rowc[rb]]);
             bka[rb] = bx.ka[rowc[rb]];
             bkbi[rb] = bx.kbi[rowc[rb]];
         }

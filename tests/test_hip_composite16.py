@@ -92,6 +92,9 @@ CASES = [
     (2, 64, 64, 3, 3, True, torch.float16), (2, 64, 64, 6, 5, False, torch.float16),
     (3, 32, 32, 6, 7, True, torch.float16),
     (2, 48, 48, 6, 3, True, torch.bfloat16),          # BASELINE config 2's LR size
+    # P = N * ceil(HW / 128) = 544 BN1 partials per channel: the depthwise kernel's wave fold (csrc/bn_math.h) takes a
+    # second request round (P > 8 * 64) with a clamped tail, in dw_vec_kernel (K = 3) and in dw_mfma_kernel (K >= 5)
+    (17, 64, 64, 3, 3, True, torch.bfloat16), (17, 64, 64, 3, 5, True, torch.bfloat16),
 ]
 
 
