@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 311 /* + ofasr_mode_unpack_u8, ofasr_mode_pack_u8 */
+#define OFASR_VERSION 312 /* + ofasr_rgb_hist_slabs, ofasr_rgb_hist_yuv420, ofasr_rgb_hist_yuv420p16, ofasr_hist_fold_distance */
 
 typedef enum {
     OFASR_OK = 0,
@@ -645,6 +645,39 @@ int ofasr_window_activity_plane(const void* plane, int64_t H, int64_t W, int dep
 int ofasr_window_route(const int64_t* partial, int64_t slabs, int64_t limit, const int32_t* changed, int64_t changed_slabs,
                        const int64_t* origins, const int64_t* table, int64_t n, int64_t batch, int64_t* out_origins,
                        int64_t* out_table, int64_t* out_index, int64_t* count, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Scene cuts of a planar YUV 4:2:0 video (csrc/scene.hip; host statement: scenes.py rgb_histogram_host /
+ * frame_distance_host) -- for scenes.SceneDetector and scenes_ofa_net_sr.py: the per-channel colour histogram of a frame
+ * with the decode fused in, and the squared distance between the histograms of consecutive frames.
+ *   With RGB the decode of the WHOLE frame as ofasr_yuv420_to_rgb_u8 defines it (depth 10: the same on samples read as
+ *   min(s, 1023), channels 0 .. 1023) and P = H * W:
+ *     hist[c][b] = the number of pixels whose channel c falls into bin b, b = the value at depth 8, value >> 2 at depth
+ *     10; c = 0, 1, 2 for R, G, B; every channel sums to P.
+ *   ofasr_rgb_hist_slabs(H, W): a host-only query, the number S of row slabs the frame is cut into, 1 <= S <= 1024 (one
+ *     workgroup each); 0 for a frame the entry points below refuse.
+ *   ofasr_rgb_hist_yuv420: y [H][W], u, v [H/2][W/2] uint8 planes, coeffs the six decode coefficients (yo, cy, rv, gu, gv,
+ *     bu) as ofasr_yuv420_to_rgb_u8 takes them.  partial is a device uint32 table [S][3][256]: partial[s] = the histogram
+ *     of slab s; hist = the sum of the S partials.  Every word is written by every call, each by one workgroup.
+ *   ofasr_rgb_hist_yuv420p16: the same on uint16 planes (2-byte aligned pointers; `depth` must be 10).
+ *   ofasr_hist_fold_distance: ONE workgroup.  hist_out[c][b] = sum_s partial[s][c][b] (device uint32 [3][256]);
+ *     *dist_out (device int64) = sum_c sum_b (hist_out[c][b] - hist_prev[c][b])^2 with hist_prev a table written by an
+ *     earlier call, or 0 with hist_prev null.  The distance is exact: at most 6 P^2 (three channels, all mass moved from
+ *     one bin to another), below 2^63 for P <= 2^28 -- the cap of these entry points.  The call does not synchronise.
+ * LDS integer atomics inside a workgroup, plain stores to memory, no global atomics, integer sums only: two calls give
+ * identical bytes.  No load leaves the planes whatever their base alignment (wide loads only where the address is aligned
+ * for them); a block of 4 columns cut by the right edge (W % 4 == 2) counts its 2 valid columns.  64-bit addressing.
+ * OFASR_ERR_INVALID_ARG: a null pointer, odd or too small sides, a coefficient outside the tables' range, a table not
+ * aligned for its element type, an odd 16-bit plane pointer, a depth other than 10, slabs < 1 or > 1024, hist_out ==
+ * hist_prev.  OFASR_ERR_UNSUPPORTED: more than 2^28 pixels.
+ * ------------------------------------------------------------------------------------------- */
+int64_t ofasr_rgb_hist_slabs(int64_t H, int64_t W);
+int ofasr_rgb_hist_yuv420(const void* y, const void* u, const void* v, int64_t H, int64_t W, const int32_t* coeffs,
+                          uint32_t* partial, void* stream);
+int ofasr_rgb_hist_yuv420p16(const void* y, const void* u, const void* v, int64_t H, int64_t W, int depth,
+                             const int32_t* coeffs, uint32_t* partial, void* stream);
+int ofasr_hist_fold_distance(const uint32_t* partial, int64_t slabs, uint32_t* hist_out, const uint32_t* hist_prev,
+                             int64_t* dist_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Geometric self-ensemble: the 8 flips / transposes (the dihedral group D4) of an NCHW batch and the fp32 merge of the

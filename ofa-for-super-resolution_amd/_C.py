@@ -153,6 +153,10 @@ SIGNATURES = {
     "ofasr_window_activity_plane": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
     "ofasr_window_route": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp,
                                     _c_vp, _c_vp]),
+    "ofasr_rgb_hist_slabs": (_c_i64, [_c_i64, _c_i64]),
+    "ofasr_rgb_hist_yuv420": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "ofasr_rgb_hist_yuv420p16": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp]),
+    "ofasr_hist_fold_distance": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ofasr_d4_apply": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp]),
     "ofasr_d4_accumulate": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, ctypes.c_float,
                                      _c_vp]),

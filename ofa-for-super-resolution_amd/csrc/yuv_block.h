@@ -55,6 +55,53 @@ __device__ __forceinline__ void yuv_decode_px(const YuvDec& D, int Y, const int 
     rgb[2] = yuv_clampv<P>((l + D.bu * u) >> 14);
 }
 
+// RGB of the 2 x 4 block whose corner is the even frame position (by, bx): rgb[row][col][c].  Columns at or past W
+// repeat column W - 1 (the caller masks them); by + 1 < H since H is even.
+template <typename P>
+__device__ __forceinline__ void yuv_decode_block(const P* __restrict__ yp, const P* __restrict__ up, const P* __restrict__ vp,
+                                                 long long H, long long W, long long by, long long bx, const YuvDec& D,
+                                                 int (&rgb)[2][4][3]) {
+    typedef yuv_px<P> px;
+    const long long CH = H >> 1, CW = W >> 1;
+    const long long cy = by >> 1, cx = bx >> 1;
+    long long rows[3], cols[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) rows[i] = clampll(cy - 1 + i, 0, CH - 1) * CW;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cols[j] = clampll(cx - 1 + j, 0, CW - 1);
+    int cu[3][4], cv[3][4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cu[i][j] = px::sample(up[rows[i] + cols[j]]);
+            cv[i][j] = px::sample(vp[rows[i] + cols[j]]);
+        }
+    int Y[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const P* p = yp + (by + r) * W + bx;
+        if ((reinterpret_cast<uintptr_t>(p) & (4 * sizeof(P) - 1)) == 0 && bx + 4 <= W) {
+            px::load4(p, Y[r]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) Y[r][k] = px::sample(p[bx + k < W ? k : (int)(W - 1 - bx)]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int nr = r == 0 ? 0 : 2;                   // the other chroma row: above for the even row, below for the odd
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c0 = 1 + (k >> 1);
+            const int nc = (k & 1) ? c0 + 1 : c0 - 1;    // left for the even column, right for the odd
+            const int tu[4] = {cu[1][c0], cu[1][nc], cu[nr][c0], cu[nr][nc]};
+            const int tv[4] = {cv[1][c0], cv[1][nc], cv[nr][c0], cv[nr][nc]};
+            yuv_decode_px<P>(D, Y[r][k], tu, tv, rgb[r][k]);
+        }
+    }
+}
+
 // luma of the 2 x 4 block rgb (columns < valid, valid = 2 or 4) and its one or two chroma pairs
 template <typename P>
 __device__ __forceinline__ void yuv_encode_block(const int (&rgb)[2][4][3], const YuvEnc& E, int (&Y)[2][4], int (&U)[2],

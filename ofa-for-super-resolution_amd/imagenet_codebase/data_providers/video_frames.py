@@ -20,6 +20,7 @@ import argparse
 
 VIDEO_FLAGS = ("video", "video_size", "video_frames", "video_valid_every", "matrix", "range")
 PAIR_FLAGS = ("video_lr", "video_lr_size", "video_no_rotate")
+SCENE_FLAGS = ("video_scene",)
 
 
 # ---------------------------------------------------------------------------------------------- command line
@@ -68,6 +69,9 @@ def add_video_args(ap):
     g.add_argument("--video-no-rotate", action="store_true",
                    help="paired training without the random rotation (the angle is drawn and set to 0): LR and HR crops "
                         "then cover exactly the same area; needs --video-lr")
+    g.add_argument("--video-scene", default=None, metavar="FILE:K",
+                   help="--video-frames = the range of scene K of the scene map FILE (scenes_ofa_net_sr.py); needs exactly "
+                        "one --video and excludes --video-frames")
     return ap
 
 
@@ -77,6 +81,17 @@ def take_video_args(a):
     given without --video is an error)."""
     vals = {k: a.__dict__.pop(k) for k in VIDEO_FLAGS}
     pair = {k: a.__dict__.pop(k) for k in PAIR_FLAGS}
+    scene = {k: a.__dict__.pop(k) for k in SCENE_FLAGS}["video_scene"]
+    if scene is not None:     # without --video-scene everything below is what it was before the flag existed
+        if not vals["video"] or len(vals["video"]) != 1:
+            raise SystemExit("--video-scene needs exactly one --video")
+        if vals["video_frames"] is not None:
+            raise SystemExit("--video-scene and --video-frames exclude each other: the scene is the frame range")
+        from ... import scenes
+        try:
+            vals["video_frames"] = parse_video_frames(scenes.video_scene_range(scene))
+        except (ValueError, OSError) as e:
+            raise SystemExit("--video-scene: %s" % e)
     if not pair["video_lr"] and (pair["video_lr_size"] is not None or pair["video_no_rotate"]):
         raise SystemExit("--video-lr-size / --video-no-rotate need --video-lr")
     if not vals["video"]:

@@ -414,6 +414,62 @@ def rgb_to_yuv420_u8(rgb, matrix="bt601", full_range=False, out=None):
     return y, u, v
 
 
+# ------------------------------------------------------------------------------ scene cuts (colour histograms)
+HIST_MAX_PIXELS = 1 << 28     # 6 P^2 < 2^63: the frame-to-frame distance stays an exact int64 (scenes.py)
+
+
+def rgb_hist_slabs(H, W):
+    """row slabs of rgb_hist_yuv420's partial table for an H x W frame (ofasr_rgb_hist_slabs; host only)"""
+    return int(_C.lib().ofasr_rgb_hist_slabs(H, W))
+
+
+def rgb_hist_yuv420(y, u, v, matrix="bt601", full_range=False, out=None):
+    """planar YUV 4:2:0 (uint8 GPU planes, or uint16 at depth 10) -> the int32 table partial [S, 3, 256], S =
+    rgb_hist_slabs(H, W): the per-slab colour histograms of the decoded frame, which is never written
+    (ofasr_rgb_hist_yuv420 / ofasr_rgb_hist_yuv420p16, csrc/scene.hip; the definition is scenes.rgb_histogram_host).
+    The counts are below 2^31, so the library's uint32 words are held in an int32 tensor.  `out`: the table to write."""
+    H, W = yuv420_planes(y, u, v, "rgb_hist_yuv420")
+    if H * W > HIST_MAX_PIXELS:
+        raise ValueError("rgb_hist_yuv420: a %dx%d frame has more than 2^28 pixels: the distance's bound 6 P^2 would "
+                         "leave int64" % (W, H))
+    S = rgb_hist_slabs(H, W)
+    if out is None:
+        out = torch.empty(S, 3, 256, dtype=torch.int32, device=y.device)
+    _gpu(out)
+    if out.dtype != torch.int32 or tuple(out.shape) != (S, 3, 256) or not out.is_contiguous() or out.device != y.device:
+        raise ValueError("rgb_hist_yuv420: the partial table must be a contiguous int32 [%d, 3, 256] tensor on the planes' "
+                         "device" % S)
+    depth = YUV_DEPTHS[y.dtype]
+    table = yuv_table(matrix, full_range, False, depth)
+    if depth == 8:
+        _C.check(_C.lib().ofasr_rgb_hist_yuv420(_p(y), _p(u), _p(v), H, W, table, _p(out), _stream()),
+                 "ofasr_rgb_hist_yuv420")
+    else:
+        _C.check(_C.lib().ofasr_rgb_hist_yuv420p16(_p(y), _p(u), _p(v), H, W, depth, table, _p(out), _stream()),
+                 "ofasr_rgb_hist_yuv420p16")
+    return out
+
+
+def hist_fold_distance(partial, hist_out, hist_prev, dist_out):
+    """hist_out [3, 256] (int32) = the sum of partial [S, 3, 256] over S; dist_out (one int64 element) = the sum of
+    (hist_out - hist_prev)^2, or 0 with hist_prev None (ofasr_hist_fold_distance; the definition is
+    scenes.frame_distance_host).  No host synchronisation."""
+    _gpu(partial, hist_out, hist_prev, dist_out)
+    if partial.dtype != torch.int32 or partial.dim() != 3 or tuple(partial.shape[1:]) != (3, 256) or partial.size(0) < 1 \
+            or not partial.is_contiguous():
+        raise ValueError("hist_fold_distance: partial must be a contiguous int32 [S, 3, 256] tensor")
+    for h in (hist_out, hist_prev):
+        if h is not None and (h.dtype != torch.int32 or tuple(h.shape) != (3, 256) or not h.is_contiguous()
+                              or h.device != partial.device):
+            raise ValueError("hist_fold_distance: a histogram must be a contiguous int32 [3, 256] tensor on partial's device")
+    if dist_out.dtype != torch.int64 or dist_out.numel() != 1 or dist_out.device != partial.device:
+        raise ValueError("hist_fold_distance: dist_out must be one int64 element on partial's device")
+    _C.check(_C.lib().ofasr_hist_fold_distance(_p(partial), partial.size(0), _p(hist_out),
+                                               None if hist_prev is None else _p(hist_prev), _p(dist_out), _stream()),
+             "ofasr_hist_fold_distance")
+    return hist_out
+
+
 # ------------------------------------------------------------------------------ image modes (alpha, greyscale)
 MODE_MAX_TAPS = 7     # taps per axis of ofasr_mode_pack_u8: lanczos enlarging (modes.MAX_TAPS)
 

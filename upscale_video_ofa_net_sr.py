@@ -34,6 +34,13 @@ reproducible, and with --reuse-static an unchanged window keeps its class and it
 the two networks: neighbouring cores can differ at the seam.  --route-report prints per frame how many windows were easy,
 hard and reused and the min / median / max of the per-window measure, which is what to look at when choosing T.  Both
 flags work with --reuse-static, --self-ensemble, --out-size, --out-depth, --frames and --reference.
+--scene-map FILE serves one export per scene of the map that scenes_ofa_net_sr.py wrote: a scene whose entry carries
+"static": DIR runs that export, every other scene the --static one.  Each distinct export gets its own tiled upscaler,
+built when its first scene comes and kept, so every graph is captured once; all exports need the --static network's
+upscale factor, which also decides the output size and the header.  A frame outside the map's ranges is an error.  The
+output is byte-identical to the per-scene runs (--static DIR --frames A:B) joined together; with --reuse-static the
+first frame of a scene runs every window.  It works with --frames, --out-depth, --out-size, --self-ensemble,
+--reuse-static, --reference and --dump-png, and not with --easy-static.  The summary then also counts the switches.
 Prints frames per second and output megapixels per second at the end."""
 import argparse
 import concurrent.futures
@@ -128,11 +135,16 @@ def parse_args(argv=None):
     ap.add_argument("--easy-threshold", default=None, metavar="T",
                     help="a window is easy when its mean absolute luma difference, in 8-bit levels, is at most T")
     ap.add_argument("--route-report", action="store_true", help="per frame: easy / hard / reused windows and the activity")
+    ap.add_argument("--scene-map", default=None, metavar="FILE",
+                    help="serve one export per scene of this scene map (scenes_ofa_net_sr.py): \"static\" of a scene's "
+                         "entry, --static where it has none")
     ap.add_argument("--dump-png", default=None, metavar="DIR", help="also write every output frame as a PNG")
     ap.add_argument("--reference", default=None, metavar="REF", help="ground-truth video of the output's size: PSNR")
     ap.add_argument("input", metavar="INPUT", help="*.y4m, or a headerless yuv420p file (then --size is required)")
     a = ap.parse_args(argv)
     check_route_args(ap, a)
+    if a.scene_map is not None and a.easy_static is not None:
+        ap.error("--scene-map with --easy-static is not supported: route inside one export, or switch exports per scene")
     if a.dump_png is not None and 10 in (a.out_depth, a.depth if a.out_depth is None else None):
         ap.error("--dump-png needs an 8-bit output (there is no 16-bit PNG writer): leave it out or use --out-depth 8")
     return a
@@ -180,6 +192,15 @@ def main(argv=None):
     if a.dump_png is not None and out_depth != 8:      # a C420p10 input without --out-depth 8: known only now
         raise SystemExit("--dump-png needs an 8-bit output (there is no 16-bit PNG writer): use --out-depth 8")
     full = a.range == "pc"
+    smap = None
+    if a.scene_map is not None:
+        try:
+            smap = importlib.import_module(PKG + ".scenes").SceneMap.load(a.scene_map)
+        except (ValueError, OSError) as e:
+            raise SystemExit("--scene-map: %s" % e)
+        if (smap.width, smap.height, smap.depth) != (W, H, depth):
+            raise SystemExit("--scene-map: %s describes %dx%d frames of %d bits, %s has %dx%d of %d bits"
+                             % (a.scene_map, smap.width, smap.height, smap.depth, a.input, W, H, depth))
     net = evals.load_static(a.static).cuda()
     easy = None if a.easy_static is None else evals.load_static(a.easy_static).cuda()
     try:
@@ -208,6 +229,34 @@ def main(argv=None):
         print("routing: windows of mean luma activity <= %s run %s (receptive radius %d px)"
               % (a.easy_threshold, easy.name(), upscale.receptive_radius(easy.config)))
     routed = [0, 0, 0]                                     # easy, hard, reused windows of all frames
+    # --scene-map: one (upscaler, stream) per distinct export, built at its first scene and kept
+    runners = {os.path.normpath(a.static): (up, stream)}
+    switches, served = 0, None
+    if smap is not None:
+        for k, sc in enumerate(smap.scenes):               # the factor stands in the export's config: refuse before frame 0
+            if "static" in sc and os.path.normpath(sc["static"]) not in runners:
+                try:
+                    with open(os.path.join(sc["static"], "net_config.json")) as fh:
+                        factor = json.load(fh).get("upscale", s)
+                except (OSError, ValueError) as e:
+                    raise SystemExit("--scene-map: scenes[%d]: %s" % (k, e))
+                if factor != s:
+                    raise SystemExit("--scene-map: scenes[%d]: %s upscales x%s, --static %s x%d: all exports need one factor"
+                                     % (k, sc["static"], factor, a.static, s))
+        print("scene map %s: %d scenes, %d exports" % (a.scene_map, len(smap.scenes), len(
+            set(os.path.normpath(sc.get("static", a.static)) for sc in smap.scenes) | set(runners))))
+
+    def runner(path):
+        key = os.path.normpath(path)
+        if key not in runners:
+            other = upscale.TiledUpscaler(evals.load_static(path).cuda(), core=a.core, batch=a.batch, mix_prec=a.mix_prec,
+                                          self_ensemble=a.self_ensemble)
+            if other.scale != s:
+                raise SystemExit("--scene-map: %s upscales x%d, --static %s x%d: all exports need one factor"
+                                 % (path, other.scale, a.static, s))
+            runners[key] = (other, other.yuv420_stream(matrix=a.matrix, full_range=full, out_depth=out_depth,
+                                                       out_size=out_size, resample=a.resample) if a.reuse_static else None)
+        return key, runners[key]
     writer = open_writer(video, reader, a.out, OW, OH, depth, out_depth)
     ref = None
     if a.reference is not None:
@@ -265,6 +314,17 @@ def main(argv=None):
             torch.cuda.current_stream().synchronize()     # the pinned slot is free again once the upload has finished
             nxt = rd.submit(read, (done + 1) % SLOTS) if want is None or done + 1 < want else None
             y, u, v = video.split_frame(dev_in, W, H, depth)
+            if smap is not None:
+                try:
+                    scene = smap.scenes[smap.scene_of(first + done)]
+                except ValueError as e:
+                    raise SystemExit("--scene-map: %s" % e)
+                key, (up, stream) = runner(scene.get("static", a.static))
+                if key != served:
+                    switches += served is not None
+                    served = key
+                    if stream is not None:
+                        stream.reset()                     # another network wrote the frames in between
             if stream is not None:
                 Y, U, V = stream.upscale(y, u, v)          # the stream's own planes: copied out before the next frame
             else:
@@ -325,12 +385,12 @@ def main(argv=None):
                                 "hard": routed[1], "reused": routed[2]}
             json.dump(rec, fh, indent=1)
     mp = done * OW * OH / 1e6
-    print("%d frames, %.2f output MP in %.3f s: %.2f frames/s, %.2f MP/s" % (done, mp, dt, done / dt, mp / dt))
+    print("%d frames, %.2f output MP in %.3f s: %.2f frames/s, %.2f MP/s%s" % (
+        done, mp, dt, done / dt, mp / dt, "" if smap is None else ", %d export switches" % switches))
     if easy is not None:
         print("routed %d windows: %d easy (%.1f %%), %d hard, %d reused" % (
             sum(routed), routed[0], 100.0 * routed[0] / max(sum(routed), 1), routed[1], routed[2]))
-    if stream is not None:
-        st = stream.stats
+    for st in [r[1].stats for r in runners.values() if r[1] is not None]:
         print("windows run %d of %d (%.1f %%), %d frames unchanged" % (
             st.total_run, st.total_windows, 100.0 * st.total_run / max(st.total_windows, 1), st.frames_unchanged))
 
