@@ -227,7 +227,7 @@ def check_block(ora, case, bstat, profile):
         else:   # the reduction + apply pair for all three BNs, no BwdXf consumer
             assert nstat == 0 and ran(bwd_table, "bn_bwd_reduce_kernel") == 3 - one3, bwd_table
             assert ran(bwd_table, "bn_bwd_apply_kernel") == 3 - one3 and ran(bwd_table, "bn_bwd_coef_kernel") == 0, bwd_table
-        if K in (5, 7) and Ww in (32, 64):
+        if K in (5, 7) and Ww in (32, 64) and Hh in (32, 64):   # mfma_geom_ok (csrc/dwconv.hip)
             assert ran(fwd_table, "dw_mfma_kernel<%s, %d, false, true, true, false>" % (T, K)) == 1, fwd_table
             assert ran(bwd_table, "dw_mfma_kernel<%s, %d, true, false, false, true>" % (T, K)) == (1 if folded else 0), bwd_table
         else:

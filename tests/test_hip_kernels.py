@@ -171,6 +171,17 @@ DW_SHAPES = [
     (1, 4, 6, 4),       # 1 lane per row
     (2, 3, 5, 16),
     (1, 2, 40, 24),
+    # several slabs per plane, one row group per wave, idle lanes, the upper edges of the vector path: the geometries
+    # of test_hip_dw_geometry.py::GEOMETRY (exact data there; here the data rounds on store)
+    (1, 2, 70, 256),
+    (2, 3, 130, 128),
+    (1, 2, 37, 132),
+    (1, 3, 9, 84),
+    (1, 2, 20, 72),
+    (1, 2, 33, 512),
+    (1, 1, 40, 264),
+    (2, 2, 200, 64),
+    (1, 2, 72, 128),
 ]
 
 

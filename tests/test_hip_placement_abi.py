@@ -224,6 +224,8 @@ DW_SHAPES = [
     (2, 6, 12, 8),
     (1, 3, 70, 65),
     (1, 6, 40, 150),
+    (1, 2, 37, 132),    # vector kernels, two slabs per plane, rows of 33 lanes: clamped halo-row loads of both slabs
+    (1, 2, 70, 256),    # three slabs (two at 8 pixels per lane): the weight gradient's workspace holds a partial per slab
 ]
 
 
