@@ -120,13 +120,13 @@ def test_composite_block_16bit_vs_oracle(ora, case, bstat):
     check_block(ora, case, bstat, DEFAULT_PROFILE)
 
 
-def check_block(ora, case, bstat, profile):
-    """one composite forward + backward of `case`, every stage against the oracle; `profile` says which side of each
-    routing switch this process runs (the switches are read once per process).  Returns the launch table of the call."""
-    from oracle import composite16 as c16
+def run_block(case, bstat, before_backward=None):
+    """one composite forward + backward of `case` (deferred weight gradients, shared scratch -- the trainer's mode), up
+    to and including flush_deferred() / synchronize().  `before_backward(main_stream)`, if given, is called immediately
+    before y.backward(); if it returns a callable, that is called with the same stream right after backward() returns
+    (before the flush).  Returns the raw tensors and the two launch tables."""
     N, Hh, Ww, e, K, train, dtype = case
     ops, C = amd("ops"), amd("_C")
-    pf = dict(DEFAULT_PROFILE, **profile)
     assert not bstat or bstat_applies(case), case
     was_bstat = C.lib().ofasr_debug_mbconv_bn_bwd_stat(1 if bstat else 0)
     block, layer = _make_block(100 * K + e)
@@ -150,7 +150,11 @@ def check_block(ora, case, bstat, profile):
         act, stat = saved[1], saved[2]
         fwd_table = C.launch_table()
         C.reset_launch_counts()
-        y.backward(do16.to(DEV))
+        dog = do16.to(DEV)
+        after_backward = before_backward(torch.cuda.current_stream()) if before_backward is not None else None
+        y.backward(dog)
+        if callable(after_backward):
+            after_backward(torch.cuda.current_stream())
         amd("ops").flush_deferred()   # deferred weight gradients -> .grad (ops.py)
         torch.cuda.synchronize()
         bwd_table = C.launch_table()
@@ -160,6 +164,21 @@ def check_block(ora, case, bstat, profile):
         ops.deferred_weight_grads(was_defer)
         ops._TMP_CACHE.clear()
         C.lib().ofasr_debug_mbconv_bn_bwd_stat(was_bstat)
+    grads = {n: (None if p.grad is None else p.grad.detach()) for n, p in block.named_parameters()}
+    return dict(y=y.detach(), dx=xg.grad.detach(), grads=grads, act=act, stat=stat, tmp=tmp, fwd_table=fwd_table,
+                bwd_table=bwd_table, block=block, mid=mid, sd0=sd0, x16=x16, do16=do16)
+
+
+def check_block(ora, case, bstat, profile, before_backward=None):
+    """one composite forward + backward of `case` (run_block), every stage against the oracle; `profile` says which side
+    of each routing switch this process runs (the switches are read once per process).  Returns the launch table of the
+    call."""
+    from oracle import composite16 as c16
+    N, Hh, Ww, e, K, train, dtype = case
+    pf = dict(DEFAULT_PROFILE, **profile)
+    r = run_block(case, bstat, before_backward)
+    y, act, stat, tmp, fwd_table, bwd_table = r["y"], r["act"], r["stat"], r["tmp"], r["fwd_table"], r["bwd_table"]
+    block, mid, sd0, x16, do16 = r["block"], r["mid"], r["sd0"], r["x16"], r["do16"]
 
     # ---- routing: the kernel variants bench.py's timed step runs (profiles/r02_*_steps.txt) served this call -- or, under
     # another profile, the variant that switch selects and not the default one
@@ -279,7 +298,7 @@ def check_block(ora, case, bstat, profile):
     x = x16.float().numpy()
     dout = do16.float().numpy()
     sd1 = {k: v.detach().cpu() for k, v in block.state_dict().items()}
-    grads = {n: (None if p.grad is None else p.grad.detach().cpu().numpy()) for n, p in block.named_parameters()}
+    grads = {n: (None if gr is None else gr.cpu().numpy()) for n, gr in r["grads"].items()}
 
     def check_stats(i, ytens, stg, name):
         b = bnp[i]
@@ -386,7 +405,7 @@ def check_block(ora, case, bstat, profile):
     dxe, dw1 = ora.pwconv_bwd(dy1_gpu, x, c16.r16(w1, dtype))
     close32(grads[pfx + "inverted_bottleneck.conv.conv.weight"], dw1, "dw1")
     assert np.all(grads[pfx + "inverted_bottleneck.conv.conv.weight"][mid:] == 0)
-    close16(H(xg.grad), c16.r16(dxe.astype(np.float64) + dout, dtype), dtype, "dx (expand dgrad + shortcut)")
+    close16(H(r["dx"]), c16.r16(dxe.astype(np.float64) + dout, dtype), dtype, "dx (expand dgrad + shortcut)")
     for i, nm in enumerate(("inverted_bottleneck.bn.bn.", "depth_conv.bn.bn.")):
         assert np.all(grads[pfx + nm + "weight"][mid:] == 0) and np.all(grads[pfx + nm + "bias"][mid:] == 0)
     return {k: fwd_table.get(k, 0) + bwd_table.get(k, 0) for k in set(fwd_table) | set(bwd_table)}

@@ -24,37 +24,68 @@ def _net():
                                pixelshuffle_depth_list=[1, 2]).to(DEV).train()
 
 
-def _two_pass_grads(net, lr, hr, hooks=None):
+def _two_pass_grads(net, lr, hr, hooks=None, before_backward=None):
+    """`before_backward(sub, main_stream)`, if given, is called immediately before each backward(); a callable it returns
+    is called with the stream right after backward() has returned, before the flush (tests/stream_hold.py)"""
     net.zero_grad(set_to_none=True)
     for sub in range(2):
         random.seed(100 + sub)
         net.sample_active_subnet()
         with torch.autocast("cuda", dtype=torch.bfloat16):
             out = net(lr)
-        F.mse_loss(out.float(), hr).backward()
+        loss = F.mse_loss(out.float(), hr)
+        after = before_backward(sub, torch.cuda.current_stream()) if before_backward is not None else None
+        loss.backward()
+        if callable(after):
+            after(torch.cuda.current_stream())
         amd("ops").flush_deferred()   # deferred weight gradients -> .grad (ops.py)
     torch.cuda.synchronize()
     return {n: (None if p.grad is None else p.grad.detach().clone()) for n, p in net.named_parameters()}
 
 
+@pytest.mark.parametrize("stack", [True, False], ids=["mbstack", "per_block"])
+@pytest.mark.parametrize("schedule", ["natural", "held"])
 @pytest.mark.parametrize("shared_tmp", [False, True])
-def test_deferred_equals_immediate_with_accumulation(shared_tmp):
+def test_deferred_equals_immediate_with_accumulation(shared_tmp, schedule, stack):
+    """`held`: the library's side stream is held once before each backward() until the whole input-gradient chain of the
+    pass has run (tests/stream_hold.py; sized from a timed unheld pass of the same call).  With a scratch buffer of its
+    own per block (shared_tmp False) nothing on the chain waits for the side stream, and assert_held demands that the
+    schedule was the held one.  With the shared buffer every later block's chain reaches scratch that an unjoined earlier
+    call still uses: the PendingSide waits (csrc/mbconv.hip) then hold the chain back behind the spin on every block, so
+    the chain legitimately does not finish first.  `stack`: ofasr_mbstack_bwd (batched kernel transform at the end) or
+    one ofasr_mbconv_bwd per block."""
+    import stream_hold
     ops = amd("ops")
     net = _net()
     state = {k: v.clone() for k, v in net.state_dict().items()}
     lr = torch.rand(4, 3, 32, 32, device=DEV)
     hr = torch.rand(4, 3, 128, 128, device=DEV)
-    was, was_tmp = ops.deferred_weight_grads(False), ops.SHARED_TMP
+    was, was_tmp, was_stack = ops.deferred_weight_grads(False), ops.SHARED_TMP, ops.FUSED_STACK
+    ops.FUSED_STACK = stack
     try:
         ref = _two_pass_grads(net, lr, hr)
         net.load_state_dict(state)
         ops.deferred_weight_grads(True)
         ops.SHARED_TMP = shared_tmp
-        got = _two_pass_grads(net, lr, hr)
+        if schedule == "held":
+            timed = [stream_hold.Timed(), stream_hold.Timed()]
+            _two_pass_grads(net, lr, hr, before_backward=lambda sub, st: timed[sub](st))
+            net.load_state_dict(state)
+            holds = [stream_hold.Held(t.hold_ms()) for t in timed]
+            print("shared_tmp=%s stack=%s: chain %s ms, host %s ms -> holds %s ms at %.0f cycles/ms" % (
+                shared_tmp, stack, ["%.3f" % t.chain_ms for t in timed], ["%.3f" % t.host_ms for t in timed],
+                ["%.1f" % h.ms for h in holds], stream_hold.cycles_per_ms()))
+            got = _two_pass_grads(net, lr, hr, before_backward=lambda sub, st: holds[sub](st))
+            if not shared_tmp:
+                for h in holds:
+                    h.check()
+        else:
+            got = _two_pass_grads(net, lr, hr)
         assert not ops._Deferred.keep and not ops._Deferred.grads and not ops._Deferred.queued
     finally:
         ops.deferred_weight_grads(was)
         ops.SHARED_TMP = was_tmp
+        ops.FUSED_STACK = was_stack
     assert set(ref) == set(got)
     n_def = 0
     for n in ref:

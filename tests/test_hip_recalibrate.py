@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import placed
 from conftest import amd, assert_close
 
 pytestmark = pytest.mark.gpu
@@ -66,22 +67,11 @@ def _bn_state(net):
 
 
 # ------------------------------------------------------------------------------------------------ 1. the block
-_KEEP = []
-
-
-def _tail(t):
-    """a copy of t that ends exactly where its own device allocation ends (the allocator's segment)"""
-    nbytes = t.numel() * t.element_size()
-    seg = max(12 << 20, (nbytes + (2 << 20) - 1) // (2 << 20) * (2 << 20) + (2 << 20))
-    torch.cuda.empty_cache()
-    buf = torch.empty(seg, dtype=torch.uint8, device=DEV)
-    out = buf[seg - nbytes:].view(t.dtype).view(t.shape)
-    out.copy_(t.to(DEV))
-    end = out.data_ptr() + nbytes
-    segs = [s for s in torch.cuda.memory_snapshot() if s["address"] <= out.data_ptr() < s["address"] + s["total_size"]]
-    assert len(segs) == 1 and segs[0]["address"] + segs[0]["total_size"] == end, "tensor is not at its allocation's end"
-    _KEEP.append(buf)
-    return out
+def _placed(t, name):
+    """a 16-byte aligned copy of t inside a buffer of its own, NaN guard bands on both sides (tests/placed.py, role "in"):
+    a read before t[0] or past t[-1] poisons the statistics and the output, and placed.check() demands afterwards that
+    guards and payload are unchanged.  Independent of the caching allocator's state."""
+    return placed.place(t.to(DEV), 0, "in", name)
 
 
 def _double_recal_block(x, w1, wdw, w2, bns, K, residual):
@@ -123,8 +113,8 @@ def test_recal_block_vs_double(case, residual):
     w2 = torch.randn((64, mid, 1, 1), generator=g) * (1.0 / mid ** 0.5)
     bns = [[torch.rand(c, generator=g) * 0.6 + 0.7, torch.rand(c, generator=g) * 0.2 - 0.1] for c in (mid, mid, 64)]
     x = torch.randn((N, 64, Hh, Ww), generator=g) + 0.5     # an offset mean: the statistics must not cancel
-    xt, w1t, wdwt, w2t = _tail(x), _tail(w1), _tail(wdw), _tail(w2)
-    bt = [[_tail(t) for t in b] for b in bns]
+    xt, w1t, wdwt, w2t = _placed(x, "x"), _placed(w1, "w1"), _placed(wdw, "wdw"), _placed(w2, "w2")
+    bt = [[_placed(t, "%s%d" % (nm, i + 1)) for t, nm in zip(b, ("gamma", "beta"))] for i, b in enumerate(bns)]
     buffers = [(bn.running_mean.clone(), bn.running_var.clone(), bn.num_batches_tracked.clone()) for bn in cfg["bns"]]
     acc = tuple(torch.zeros((2, c), dtype=torch.float64, device=DEV) for c in (mid, mid, 64))
     C.reset_launch_counts()
@@ -148,7 +138,10 @@ def test_recal_block_vs_double(case, residual):
     for bn, (rm, rv, nb) in zip(cfg["bns"], buffers):   # running statistics are neither read nor written
         assert torch.equal(bn.running_mean, rm) and torch.equal(bn.running_var, rv)
         assert torch.equal(bn.num_batches_tracked, nb)
-    _KEEP.clear()
+    views = [xt, w1t, wdwt, w2t] + [t for b in bt for t in b]
+    placed.check_all(*views)   # guards and payloads byte for byte
+    for v in views:   # a placed view and its bookkeeping refer to each other: part them, so that the buffers (16 MB for x)
+        v.placement.t = None   # go back to the allocator when this test returns and not at some later collection
 
 
 def test_recal_block_scope():

@@ -51,6 +51,10 @@ def _tail(t):
     nbytes = t.numel() * t.element_size()
     seg = max(12 << 20, (nbytes + (2 << 20) - 1) // (2 << 20) * (2 << 20) + (2 << 20))
     torch.cuda.empty_cache()
+    # larger than every free block inside a segment that live tensors of earlier tests still pin: the allocator then has
+    # to make a new segment of exactly `seg` bytes, whatever ran before
+    free = max([b["size"] for s in torch.cuda.memory_snapshot() for b in s["blocks"] if b["state"] == "inactive"] or [0])
+    seg = max(seg, (free + (2 << 20) - 1) // (2 << 20) * (2 << 20) + (2 << 20))
     buf = torch.empty(seg, dtype=torch.uint8, device=DEV)
     out = buf[seg - nbytes:].view(t.dtype).view(t.shape)
     out.copy_(t.to(DEV))
