@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 312 /* + ofasr_rgb_hist_slabs, ofasr_rgb_hist_yuv420, ofasr_rgb_hist_yuv420p16, ofasr_hist_fold_distance */
+#define OFASR_VERSION 313 /* + ofasr_aug_select */
 
 typedef enum {
     OFASR_OK = 0,
@@ -767,6 +767,39 @@ int ofasr_aug_gather_yuv420(const void* pool, int64_t pool_bytes, const int64_t*
 int ofasr_aug_gather_yuv420_pair(const void* hr_pool, int64_t hr_bytes, const void* lr_pool, int64_t lr_bytes,
                                  const int64_t* table, int64_t n, int64_t S, int64_t f, const int32_t* coeffs,
                                  void* hr_u8, void* hr_f32, void* lr_u8, void* lr_f32, void* stream);
+
+/* Best of K candidate crops: K rows per sample go in, the row whose S x S crop rectangle holds the most luma detail comes
+ * out, ready for the three gathers above unchanged (host statement: augment.select_candidates_np; on the pool's bytes
+ * with the clamps below: augment.aug_select_np).  Two launches, no host synchronisation.
+ *   pool:     as ofasr_aug_gather_u8's (layout OFASR_AUG_RGB_HWC) or ofasr_aug_gather_yuv420's (OFASR_AUG_YUV420); for a
+ *             paired set the HR pool.
+ *   cand:     device int64 [blocks][n * K][12], rows as above, sample-major: candidates 0 .. K-1 of sample 0, then those of
+ *             sample 1.  blocks = 1, or 2 for ofasr_aug_gather_yuv420_pair's table (block 0 the HR rows, block 1 the LR
+ *             rows of the same draws).  The activity is always measured from block 0's row, on `pool`, at side S.
+ *   activity: A of candidate q = the sum of |L[r][c+1] - L[r][c]| over r < S, c < S-1 plus the sum of |L[r+1][c] - L[r][c]|
+ *             over r < S-1, c < S, with L[r][c] the luma sample at row i + r, column j + c of the image the row names --
+ *             the crop rectangle in the source frame, before flip and rotation; L = (77 R + 150 G + 29 B + 128) >> 8 of an
+ *             RGB pixel, the Y plane's byte of a 4:2:0 frame (ofasr_window_activity_*'s measure).  A <= 510 S^2: device
+ *             int64 [n * K], all written.
+ *   choice:   device int32 [n]: the candidate with the largest A, the lowest index among equals.
+ *   out_table: device int64 [blocks][n][12]: the winners' rows, every block's, copied word for word (unclamped).
+ *   stats:    NULL, or device int64 [3] to which the call ADDS (sum of the chosen A, sum of candidate 0's A, n).
+ *   workspace: n * K * strips int64 words, 8-byte aligned, strips = min(max(ceil(S * S / 16384), 1), 64, S) row strips
+ *             per candidate (one workgroup each; augment.aug_select_strips is the same function).
+ * The row is clamped as the gathers clamp it: H, W to [S, 2^24] (OFASR_AUG_YUV420: [Se, 2^24] & ~1, Se = S rounded up to
+ * even), 0 <= i <= H-S, 0 <= j <= W-S, 0 <= offset <= pool_bytes, and the address of every byte read --
+ * offset + ((i + r) * W + j + c) * bps + b, bps = 3 or 1 -- to [0, pool_bytes-1]: no table content makes an access leave
+ * pool.  Integer arithmetic only, one plain store per word; the only atomics are the three 64-bit integer adds into
+ * `stats`, so two calls give identical bytes in every output.
+ * OFASR_ERR_UNSUPPORTED: K outside 1 .. 16, S > 4096, n * K > 65535, a pool too small for one image of side S (as the
+ * gathers).  OFASR_ERR_INVALID_ARG: a null pointer (stats excepted), a non-positive size, blocks not 1 or 2, an unknown
+ * layout, a table not aligned for its element type.  OFASR_ERR_WORKSPACE: workspace null, misaligned or too small.
+ * Nothing is launched in any of these cases. */
+#define OFASR_AUG_RGB_HWC 0 /* layouts of ofasr_aug_select's pool */
+#define OFASR_AUG_YUV420 1
+int ofasr_aug_select(const void* pool, int64_t pool_bytes, const int64_t* cand, int64_t blocks, int64_t n, int64_t K,
+                     int64_t S, int layout, int64_t* out_table, int32_t* choice, int64_t* activity, int64_t* stats,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Y-channel quality metrics: exact SSE (for Y-PSNR) and mean SSIM of two image batches, per image  -- replaces the host

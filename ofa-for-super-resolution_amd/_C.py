@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("OFASR_LIB_PATH") or os.path.join(_HERE, "csrc", "libo
 
 F32, F16, BF16 = 0, 1, 2
 U8_HWC = 3   # operand format of ofasr_quality_y: one interleaved uint8 RGB image
+AUG_RGB_HWC, AUG_YUV420 = 0, 1   # pool layouts of ofasr_aug_select
 
 _lib = None
 
@@ -165,6 +166,8 @@ SIGNATURES = {
     "ofasr_aug_gather_yuv420": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ofasr_aug_gather_yuv420_pair": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp,
                                               _c_vp, _c_vp, _c_vp]),
+    "ofasr_aug_select": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
+                                  _c_vp, _c_sz, _c_vp]),
     "ofasr_quality_y_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "ofasr_quality_y": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_sz,
                                  _c_vp]),

@@ -1,6 +1,7 @@
 // augment.hip -- the training augmentation on GPU-resident images (ofasr_aug_gather_u8) and on GPU-resident planar
 // YUV 4:2:0 video frames with the colour decode fused in (ofasr_aug_gather_yuv420, stated before its kernel below; the
-// HR / LR pair of one draw in one launch: ofasr_aug_gather_yuv420_pair, stated before its kernel).
+// HR / LR pair of one draw in one launch: ofasr_aug_gather_yuv420_pair, stated before its kernel), and the choice of the
+// most detailed of K candidate crops per sample in front of any of the three (ofasr_aug_select, stated before its kernels).
 //
 // The DIV2K training sample is RandomCrop(S) -> RandomHorizontalFlip -> RandomRotation((-90, 90)) of a decoded RGB image
 // (data_providers/div2k_setxx.py).  With the decoded images resident in one uint8 pool, the three transforms are one
@@ -304,6 +305,184 @@ static void aug_gather(const void* pool, int64_t pool_bytes, const int64_t* tabl
     }
 }
 
+// ---- best of K candidate crops (ofasr_aug_select) ------------------------------------------------------------------------
+// K candidate rows per sample stand in the table [blocks][n * K][12], sample-major; the candidate whose S x S crop
+// rectangle holds the largest luma activity wins, ties to the lowest index, and its row (both blocks' rows of a paired
+// set) goes into the [blocks][n][12] table the gathers above take unchanged.  The host statement is augment.py
+// (crop_activity_np / select_candidates_np; on the pool's bytes with the clamps: aug_select_np), the measure routing.py's:
+//   L   the luma sample: the Y plane's byte of a 4:2:0 frame, or (77 R + 150 G + 29 B + 128) >> 8 of an RGB pixel
+//   A   over rows i .. i + S - 1, columns j .. j + S - 1 of the frame (before flip and rotation):
+//       sum of |L[r][c + 1] - L[r][c]| (r < S, c < S - 1) + sum of |L[r + 1][c] - L[r][c]| (r < S - 1, c < S)
+// always from block 0's row (clamped by aug_row as the gathers clamp it) on `pool`.  A <= 510 S^2: int64.
+// activity: grid (x: row strip, y: candidate), strips = aug_select_strips(S) (include/ofasr.h).  A strip owns the horizontal
+//          terms of its rows and the vertical terms whose upper row it owns.  The 256 threads are LPR lanes along a row
+//          (LPR = the power of two >= ceil(S / 4), at most 256) times 256 / LPR row lanes; a row lane walks a contiguous
+//          run of the strip's rows downwards and keeps the previous row's lumas in registers.  A thread owns 4 adjacent
+//          columns and reads a fifth, its right neighbour.  Wide path: the dwords that cover its 5 samples, read from
+//          4-byte aligned addresses (2 for a Y plane, 5 for RGB) and shifted by the row's misalignment, whatever the
+//          corner; it is taken when the pool's base is 4-byte aligned and the rectangle ends at least AUG_SELECT_SLACK
+//          bytes before the pool does, both uniform over the workgroup.  Byte path otherwise: 5 / 15 byte loads, each
+//          address clamped to [0, pool_bytes - 1].  Either way every load is issued from a clamped address by every
+//          lane, every trip, and rows, columns and lanes that do not count are masked afterwards: no load stands under a
+//          lane-dependent branch.  The workgroup reduces through the waves (shuffles), then 4 words of LDS, and thread 0
+//          stores ONE int64, partial[q * strips + s], with a plain store.
+// choose:  ONE wave per sample.  Lane c < K folds candidate c's partials in strip order; every lane then scans the K sums
+//          in index order and keeps the first largest; lanes copy the winner's 12 words per block, `choice` and the K
+//          activities.  With `stats`: three 64-bit integer atomic adds (sum of the chosen, sum of the first candidates,
+//          1 per sample) -- integer, so two calls still give identical bytes everywhere.
+static const int AUG_SELECT_THREADS = 256;
+static const long long AUG_SELECT_STRIP_SAMPLES = 16384;
+static const int AUG_SELECT_MAX_STRIPS = 64;
+static const int AUG_SELECT_MAX_K = 16;
+static const long long AUG_SELECT_SLACK = 20;           // bytes a wide read may pass the rectangle's last byte by, at most
+
+// the strip count, as include/ofasr.h states it (augment.aug_select_strips mirrors it)
+inline int64_t aug_select_strips(int64_t S) {
+    int64_t s = cdiv(S * S, AUG_SELECT_STRIP_SAMPLES);
+    s = s < AUG_SELECT_MAX_STRIPS ? s : AUG_SELECT_MAX_STRIPS;
+    s = s < S ? s : S;
+    return s < 1 ? 1 : s;
+}
+
+__device__ __forceinline__ int aug_luma(int r, int g, int b) { return (77 * r + 150 * g + 29 * b + 128) >> 8; }
+
+// BPS: bytes per sample, 1 (the Y plane of a 4:2:0 frame) or 3 (interleaved RGB)
+template <int BPS>
+__global__ void __launch_bounds__(AUG_SELECT_THREADS) aug_select_activity_kernel(const uint8_t* __restrict__ pool,
+                                                                                 long long pool_bytes,
+                                                                                 const long long* __restrict__ table, int S,
+                                                                                 long long* __restrict__ partial) {
+    __shared__ long long red[AUG_SELECT_THREADS / 64];
+    constexpr int NW = BPS == 1 ? 2 : 5;                 // aligned dwords that cover 5 samples at any misalignment
+    const long long q = blockIdx.y;
+    const AugRow R = aug_row(table, q, S, pool_bytes, BPS == 1);
+    long long lo, hi;
+    slab_rows(S, blockIdx.x, gridDim.x, lo, hi);
+    const int G = (S + 3) >> 2;
+    int lpr = 1;
+    while (lpr < G && lpr < AUG_SELECT_THREADS) lpr <<= 1;
+    const int RL = AUG_SELECT_THREADS / lpr;
+    const int cl = (int)threadIdx.x & (lpr - 1), rl = (int)threadIdx.x / lpr;
+    // the run of rows of this row lane: [r0, r1) owned; row r1 is read as well, for the vertical terms below r1 - 1
+    const long long per = (hi - lo + RL - 1) / RL;
+    const long long r0 = lo + rl * per < hi ? lo + rl * per : hi;
+    const long long r1 = r0 + per < hi ? r0 + per : hi;
+    const long long base = R.off + (R.ci * R.W + R.cj) * BPS;            // the rectangle's first byte
+    const long long rect_last = base + ((long long)(S - 1) * R.W + (S - 1)) * BPS + (BPS - 1);
+    const long long last = pool_bytes - 1;
+    const bool wide = (reinterpret_cast<uintptr_t>(pool) & 3) == 0 && rect_last + AUG_SELECT_SLACK < pool_bytes;
+    long long acc = 0;
+    for (int g0 = 0; g0 < G; g0 += lpr) {                                // the trip counts are the workgroup's
+        const int g = g0 + cl;
+        const int c0 = (g < G ? g : G - 1) * 4;                          // lanes past the row repeat its last group, masked
+        bool cv[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) cv[k] = g < G && c0 + k < S;
+        int P[4] = {0, 0, 0, 0};
+        for (long long t = 0; t <= per; ++t) {
+            const long long r = r0 + t;
+            const long long rc = r < S - 1 ? r : S - 1;
+            const bool own = r < r1;                                     // its horizontal terms count
+            const bool below = t > 0 && r <= r1 && r < S;                // its vertical terms to the row above count
+            int L[5];
+            const long long rb = base + rc * R.W * BPS;                  // the row's first byte in the rectangle
+            if (wide) {
+                const long long a = rb + (long long)c0 * BPS;
+                const int sh = 8 * (int)((reinterpret_cast<uintptr_t>(pool) + (uintptr_t)a) & 3);
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(pool + (a - (sh >> 3)));
+                uint32_t d[NW + 1];
+#pragma unroll
+                for (int k = 0; k < NW; ++k) d[k] = p[k];
+                d[NW] = 0u;
+                uint32_t w[NW];                                          // the bytes from `a` on
+#pragma unroll
+                for (int k = 0; k < NW; ++k) w[k] = (uint32_t)((((uint64_t)d[k + 1] << 32) | d[k]) >> sh);
+#pragma unroll
+                for (int k = 0; k < 5; ++k) {
+                    if constexpr (BPS == 1) {
+                        L[k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 0xffu);
+                    } else {
+                        int c[3];
+#pragma unroll
+                        for (int m = 0; m < 3; ++m) {
+                            const int b = 3 * k + m;
+                            c[m] = (int)((w[b >> 2] >> (8 * (b & 3))) & 0xffu);
+                        }
+                        L[k] = aug_luma(c[0], c[1], c[2]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) {
+                    const int col = c0 + k < S ? c0 + k : S - 1;
+                    const long long a = rb + (long long)col * BPS;
+                    if constexpr (BPS == 1) {
+                        L[k] = pool[a > last ? last : a];
+                    } else {
+                        const long long a1 = a + 1, a2 = a + 2;
+                        L[k] = aug_luma(pool[a > last ? last : a], pool[a1 > last ? last : a1], pool[a2 > last ? last : a2]);
+                    }
+                }
+            }
+            int sum = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                sum += own && cv[k + 1] ? abs(L[k + 1] - L[k]) : 0;
+                sum += below && cv[k] ? abs(L[k] - P[k]) : 0;
+                P[k] = L[k];
+            }
+            acc += sum;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if (lane_id() == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long s = 0;
+#pragma unroll
+        for (int w = 0; w < AUG_SELECT_THREADS / 64; ++w) s += red[w];
+        partial[q * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// grid: (x: sample), one wave
+__global__ void __launch_bounds__(64) aug_select_choose_kernel(const long long* __restrict__ partial, int strips,
+                                                               const long long* __restrict__ cand, int blocks, long long n,
+                                                               int K, long long* __restrict__ out_table,
+                                                               int* __restrict__ choice, long long* __restrict__ activity,
+                                                               unsigned long long* __restrict__ stats) {
+    __shared__ long long act[AUG_SELECT_MAX_K];
+    const long long s = blockIdx.x;
+    const int t = (int)threadIdx.x;
+    const int c = t < K ? t : K - 1;                     // lanes past K fold the last candidate again, and store nothing
+    long long A = 0;
+    for (int k = 0; k < strips; ++k) A += partial[(s * K + c) * strips + k];
+    if (t < K) {
+        act[t] = A;
+        activity[s * K + t] = A;
+    }
+    __syncthreads();
+    int best = 0;
+    long long bestA = act[0];
+    for (int k = 1; k < K; ++k) {
+        const long long v = act[k];
+        if (v > bestA) bestA = v, best = k;               // strictly larger: a tie stays with the lower index
+    }
+    if (t < 12 * blocks) {
+        const int b = t / 12, w = t - 12 * b;
+        out_table[((long long)b * n + s) * 12 + w] = cand[(((long long)b * n + s) * K + best) * 12 + w];
+    }
+    if (t == 0) {
+        choice[s] = best;
+        if (stats) {
+            atomicAdd(stats, (unsigned long long)bestA);
+            atomicAdd(stats + 1, (unsigned long long)act[0]);
+            atomicAdd(stats + 2, 1ull);
+        }
+    }
+}
+
 }  // namespace ofasr
 
 using namespace ofasr;
@@ -370,5 +549,48 @@ OFASR_EXPORT int ofasr_aug_gather_u8(const void* pool, int64_t pool_bytes, const
                   "%s: a pool of %lld bytes holds no image of at least %lldx%lld (H, W >= S)", name, (long long)pool_bytes,
                   (long long)S, (long long)S);
     aug_gather<false>(pool, pool_bytes, table, n, S, YuvDec{}, out_u8, out_f32, as_stream(stream));
+    return check_launch(name);
+}
+
+OFASR_EXPORT int ofasr_aug_select(const void* pool, int64_t pool_bytes, const int64_t* cand, int64_t blocks, int64_t n,
+                                  int64_t K, int64_t S, int layout, int64_t* out_table, int32_t* choice, int64_t* activity,
+                                  int64_t* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* name = "ofasr_aug_select";
+    OFASR_REQUIRE(pool && cand && out_table && choice && activity, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
+    OFASR_REQUIRE(K >= 1 && K <= AUG_SELECT_MAX_K, OFASR_ERR_UNSUPPORTED, "%s: %lld candidates per sample (1 .. %d)", name,
+                  (long long)K, AUG_SELECT_MAX_K);
+    OFASR_REQUIRE(layout == OFASR_AUG_RGB_HWC || layout == OFASR_AUG_YUV420, OFASR_ERR_INVALID_ARG,
+                  "%s: layout %d is neither OFASR_AUG_RGB_HWC nor OFASR_AUG_YUV420", name, layout);
+    OFASR_REQUIRE(blocks == 1 || blocks == 2, OFASR_ERR_INVALID_ARG, "%s: %lld table blocks (1, or 2 for a paired set)", name,
+                  (long long)blocks);
+    AUG_REQUIRE_SIZES(n, S, pool_bytes);
+    OFASR_REQUIRE(n * K <= 65535, OFASR_ERR_UNSUPPORTED, "%s: %lld candidates in one launch (at most 65535)", name,
+                  (long long)(n * K));
+    // as the gathers: the smallest pool that can hold one image (one even-sided frame) with H, W >= S
+    const int64_t Se = (S + 1) & ~(int64_t)1;
+    const int64_t least = layout == OFASR_AUG_YUV420 ? Se * Se * 3 / 2 : 3 * S * S;
+    OFASR_REQUIRE(pool_bytes >= least, OFASR_ERR_UNSUPPORTED, "%s: a pool of %lld bytes holds no image of at least %lldx%lld",
+                  name, (long long)pool_bytes, (long long)S, (long long)S);
+    OFASR_REQUIRE(((reinterpret_cast<uintptr_t>(cand) | reinterpret_cast<uintptr_t>(out_table) |
+                    reinterpret_cast<uintptr_t>(activity) | reinterpret_cast<uintptr_t>(stats)) & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(choice) & 3) == 0,
+                  OFASR_ERR_INVALID_ARG, "%s: a table is not aligned for its element type", name);
+    const int64_t strips = aug_select_strips(S);
+    OFASR_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 &&
+                      workspace_bytes >= (size_t)(n * K * strips) * sizeof(int64_t),
+                  OFASR_ERR_WORKSPACE, "%s: the workspace holds n * K * strips = %lld int64 words, 8-byte aligned", name,
+                  (long long)(n * K * strips));
+    const dim3 grid((unsigned)strips, (unsigned)(n * K));
+    prof_note((double)(n * K) * (double)(S * S) * (layout == OFASR_AUG_YUV420 ? 1.0 : 3.0), 0.0);
+    if (layout == OFASR_AUG_YUV420)
+        OFASR_LAUNCH(aug_select_activity_kernel<1>, grid, dim3(AUG_SELECT_THREADS), 0, as_stream(stream), (const uint8_t*)pool,
+                     (long long)pool_bytes, (const long long*)cand, (int)S, (long long*)workspace);
+    else
+        OFASR_LAUNCH(aug_select_activity_kernel<3>, grid, dim3(AUG_SELECT_THREADS), 0, as_stream(stream), (const uint8_t*)pool,
+                     (long long)pool_bytes, (const long long*)cand, (int)S, (long long*)workspace);
+    prof_note((double)n * (double)K * (8.0 * (double)strips + 8.0) + (double)n * (double)blocks * 192.0, 0.0);
+    OFASR_LAUNCH(aug_select_choose_kernel, dim3((unsigned)n), dim3(64), 0, as_stream(stream), (const long long*)workspace,
+                 (int)strips, (const long long*)cand, (int)blocks, (long long)n, (int)K, (long long*)out_table, (int*)choice,
+                 (long long*)activity, (unsigned long long*)stats);
     return check_launch(name);
 }

@@ -149,6 +149,7 @@ def train_one_epoch(run_manager, args, epoch, warmup_epochs=0, warmup_lr=0):
     losses.update(float(loss_sum) / max(n_seen, 1), n_seen)     # the only host syncs of the epoch
     psnr_meter.update(float(psnr_sum) / max(n_seen, 1), n_seen)
     run_manager._last_train_log = log
+    run_manager.log_crop_selection(epoch)      # a line only with best-of-K training crops
     return losses.avg, psnr_meter.avg
 
 

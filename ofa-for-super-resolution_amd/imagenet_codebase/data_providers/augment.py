@@ -20,6 +20,11 @@ Paired video.  A source video and its decoded low-resolution stream give the HR 
 (ofasr_aug_gather_yuv420_pair, ops.aug_gather_yuv420_pair, ResidentVideoPairSet); the definition -- the pair, the draw,
 the sample, registration -- stands before draw_pair_params below (tests/test_video_pair.py on the host,
 tests/test_hip_video_pair.py on the GPU).
+
+Best of K.  ResidentTrainLoader(candidates=K) draws K parameter sets per sample and the GPU keeps the one whose crop
+rectangle holds the most luma detail (ofasr_aug_select, ops.aug_select) before the unchanged gather runs; the definition
+stands before aug_select_strips below, aug_select_np restates the kernel on the pool's bytes (tests/test_crop_select.py
+on the host, tests/test_hip_crop_select.py on the GPU).
 """
 import math
 import os
@@ -291,6 +296,102 @@ def gather_yuv420_pair_np(hr_pool, lr_pool, table, S, f, coeffs):
     return gather_yuv420_np(hr_pool, table[0], S, coeffs), gather_yuv420_np(lr_pool, table[1], s, coeffs)
 
 
+# ------------------------------------------------------------------------------------- best of K candidate crops
+# Candidates.  For each sample of a batch, in batch order, K parameter sets (i, j, flip, angle) are drawn one after
+# another with the draw the sample would have had anyway (draw_train_params; draw_pair_params of a paired set, on its LR
+# grid): all K of sample 0, then all K of sample 1.  With K = 1 that is the RNG sequence of a loader without candidates.
+#
+# Measure.  Candidate c scores the routing.py activity A of its S x S crop rectangle in the source frame, rows
+# i .. i + S - 1, columns j .. j + S - 1, BEFORE flip and rotation: the sum of absolute luma differences of horizontally
+# and vertically neighbouring samples with both samples inside the rectangle (crop_activity_np; it equals
+# routing.window_activity_host(src, [(i, j)], S, S)[0]).  Luma of an RGB image: (77 R + 150 G + 29 B + 128) >> 8; of a
+# 4:2:0 frame: the Y plane as stored; of a paired sample: the Y plane of the HR frame at (f i, f j), side S.
+# A <= 510 S^2, above 2^32 at S = 4096: int64.
+#
+# Choice.  The largest A wins, ties go to the lowest candidate index (a flat image keeps its first draw), and the
+# winner's whole parameter set, flip and angle included, is what the gather receives (select_candidates_np).
+#
+# aug_select_np restates the kernel (ofasr_aug_select) on the pool's bytes, the clamps of a device table included.
+MAX_CANDIDATES = 16                 # ofasr_aug_select's limit on K
+SELECT_STRIP_SAMPLES = 16384        # samples of a crop rectangle per workgroup of its first launch, about
+SELECT_MAX_STRIPS = 64
+LAYOUT_RGB, LAYOUT_YUV420 = "rgb", "yuv420"
+
+
+def aug_select_strips(S):
+    """the row strips ofasr_aug_select cuts an S x S rectangle into (include/ofasr.h states the function; the workspace
+    is n * K * strips int64 words)"""
+    S = int(S)
+    return max(1, min(-(-S * S // SELECT_STRIP_SAMPLES), SELECT_MAX_STRIPS, S))
+
+
+def check_candidates(K):
+    K = int(K)
+    if not 1 <= K <= MAX_CANDIDATES:
+        raise ValueError("crop candidates per sample: %d outside 1 .. %d" % (K, MAX_CANDIDATES))
+    return K
+
+
+def draw_candidates(draw, K):
+    """K parameter sets of one sample, drawn one after another by `draw()`"""
+    return [draw() for _ in range(check_candidates(K))]
+
+
+def crop_activity_np(src, params, S):
+    """A of the S x S crop rectangle at params' (i, j) in `src`, an [H, W, 3] uint8 RGB image or a 2-D uint8 luma plane"""
+    from ... import routing
+    L = routing.luma_plane(src)
+    i, j, S = int(params[0]), int(params[1]), int(S)
+    if not (0 <= i <= L.shape[0] - S and 0 <= j <= L.shape[1] - S):
+        raise ValueError("crop corner (%d, %d) of side %d outside the %dx%d image" % (i, j, S, L.shape[0], L.shape[1]))
+    R = L[i:i + S, j:j + S]
+    return int(np.abs(np.diff(R, axis=1)).sum()) + int(np.abs(np.diff(R, axis=0)).sum())
+
+
+def select_candidates_np(srcs, cands, S):
+    """(choice int32 [n], activity int64 [n, K]) of the K candidates cands[s] of each sample's source srcs[s] (an RGB image,
+    a Y plane; for a paired sample the HR Y plane with the HR parameters, pair_hr_params)"""
+    act = np.array([[crop_activity_np(src, p, S) for p in ps] for src, ps in zip(srcs, cands)], dtype=np.int64)
+    act = act.reshape(len(cands), -1)
+    return np.argmax(act, axis=1).astype(np.int32), act          # argmax: the first of equal maxima
+
+
+def aug_select_np(pool_bytes, cand_table, n, K, S, layout):
+    """ofasr_aug_select restated on the pool's bytes (a 1-D uint8 array), clamping rules included: (choice int32 [n],
+    activity int64 [n, K], table int64 [blocks, n, 12]).  `cand_table`: int64 [blocks, n * K, 12], sample-major; `layout`:
+    LAYOUT_RGB (HWC images, 3 bytes a sample) or LAYOUT_YUV420 (the Y plane of a frame, 1 byte a sample).  Per candidate,
+    from block 0's row: H = clamp(H, S, 2^24) and W alike (yuv420: clamp(., Se, 2^24) & ~1, Se = S rounded up to even),
+    (i, j) into [0, H - S] x [0, W - S], offset into [0, pool bytes], and the address of every byte read into
+    [0, pool bytes - 1]."""
+    pool = np.asarray(pool_bytes, dtype=np.uint8).reshape(-1)
+    nb, n, K, S = int(pool.size), int(n), check_candidates(K), int(S)
+    if layout not in (LAYOUT_RGB, LAYOUT_YUV420):
+        raise ValueError("aug_select_np: layout is %r or %r, got %r" % (LAYOUT_RGB, LAYOUT_YUV420, layout))
+    yuv = layout == LAYOUT_YUV420
+    cand = np.asarray(cand_table, dtype=np.int64)
+    cand = cand.reshape(-1, n * K, TABLE_COLS)
+    bps, lim, Se = (1 if yuv else 3), 1 << 24, ((S + 1) & ~1 if yuv else S)
+    r, c = np.mgrid[0:S, 0:S].astype(np.int64)
+    act = np.zeros((n, K), np.int64)
+    for q, row in enumerate(cand[0]):
+        off, H, W, i, j = (int(v) for v in row[:5])
+        H, W = min(max(H, Se), lim), min(max(W, Se), lim)
+        if yuv:
+            H, W = H & ~1, W & ~1
+        i, j = min(max(i, 0), H - S), min(max(j, 0), W - S)
+        off = min(max(off, 0), nb)
+        a = off + ((i + r) * W + j + c) * bps
+
+        def at(b):
+            return pool[np.minimum(b, nb - 1)].astype(np.int64)
+
+        L = at(a) if yuv else (77 * at(a) + 150 * at(a + 1) + 29 * at(a + 2) + 128) >> 8
+        act[q // K, q % K] = int(np.abs(np.diff(L, axis=1)).sum()) + int(np.abs(np.diff(L, axis=0)).sum())
+    choice = np.argmax(act, axis=1).astype(np.int32)
+    pick = np.arange(n) * K + choice
+    return choice, act, np.ascontiguousarray(cand[:, pick])
+
+
 # ------------------------------------------------------------------------------------- the resident training set
 class ResidentTrainSet(object):
     """Every training image decoded once (Image.open(p).convert("RGB"), on at most 16 threads) into ONE uint8 pool on
@@ -346,6 +447,38 @@ class ResidentTrainSet(object):
 
     def image_np(self, k):
         """image k back on the host as [H, W, 3] (tests and debugging)"""
+        off, h, w = self.entries[k]
+        return self.pool[off:off + h * w * 3].cpu().numpy().reshape(h, w, 3)
+
+
+class ResidentArraySet(object):
+    """ResidentTrainSet's pool from images that are decoded already: [H, W, 3] uint8 arrays, packed HWC back to back in
+    ONE uint8 pool on `device`, `entries[k] = (offset, H, W)`, `paths[k]` = `names[k]` (the synthetic stand-in of the
+    DIV2K provider under crop_candidates, and tests)."""
+
+    def __init__(self, images, device, names=None):
+        images = [np.ascontiguousarray(a) for a in images]
+        if not images:
+            raise ValueError("ResidentArraySet: no images")
+        for a in images:
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("ResidentArraySet: an image is an [H, W, 3] uint8 array, got %s %s" % (a.shape, a.dtype))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            from ... import _C
+            raise _C.OfasrError("ResidentArraySet keeps the images on the GPU (got device %s)" % (self.device,))
+        self.paths = ["array#%d" % k for k in range(len(images))] if names is None else list(names)
+        self.entries, total = [], 0
+        for a in images:
+            self.entries.append((total, a.shape[0], a.shape[1]))
+            total += a.size
+        self.nbytes = total
+        self.pool = torch.from_numpy(np.concatenate([a.reshape(-1) for a in images])).to(self.device)
+
+    def __len__(self):
+        return len(self.entries)
+
+    def image_np(self, k):
         off, h, w = self.entries[k]
         return self.pool[off:off + h * w * 3].cpu().numpy().reshape(h, w, 3)
 
@@ -590,11 +723,21 @@ class ResidentTrainLoader(object):
     A paired set (ResidentVideoPairSet) brings hooks of its own, and only such a set has them: `TABLE_BLOCKS` rows of
     pinned table per sample, `check_crop(S)`, `draw_params(k, S)` in place of draw_train_params, `make_table(indices,
     params, S, out)` in place of make_table, and `as_batch(out, want_f32)` for the batch's keys.  For every other set
-    the draws, the table and the batch are what they were."""
+    the draws, the table and the batch are what they were.
 
-    def __init__(self, dataset, batch_size, sampler, size, drop_last=True, want_f32=False, ring=4):
+    `candidates=K` > 1: best of K candidate crops (the definition stands before aug_select_strips above).  K parameter
+    sets are drawn per sample, sample-major, the candidate table -- the same rows, K per sample, built by the same
+    make_table / set hook in a pinned ring of K times the rows -- is uploaded once, ops.aug_select names each sample's
+    winner on the device and its table goes to the unchanged gather: two small launches more and no host read.
+    `last_params` is then the list of K-lists, `last_choice` (int32 [n]) and `last_activity` (int64 [n, K]) are device
+    tensors, `batch(indices, params=...)` takes a list of K parameter sets per sample, and selection_stats() reads what
+    the batches since its last call accumulated.  With K = 1 none of this code runs."""
+
+    def __init__(self, dataset, batch_size, sampler, size, drop_last=True, want_f32=False, ring=4, candidates=1):
         self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
         self.size, self.drop_last, self.want_f32 = int(size), bool(drop_last), bool(want_f32)
+        self.candidates = check_candidates(candidates)
+        self.last_choice, self.last_activity, self._stats = None, None, None
         if not 0 < self.size <= MAX_SIDE:
             raise ValueError("ResidentTrainLoader: crop side %d outside 1 .. %d" % (self.size, MAX_SIDE))
         for (_, h, w), p in zip(dataset.entries, dataset.paths):
@@ -603,7 +746,7 @@ class ResidentTrainLoader(object):
                                  % ((self.size, self.size), (h, w), p))
         if hasattr(dataset, "check_crop"):
             dataset.check_crop(self.size)
-        rows = self.batch_size * getattr(dataset, "TABLE_BLOCKS", 1)
+        rows = self.batch_size * getattr(dataset, "TABLE_BLOCKS", 1) * self.candidates
         self._host = [torch.empty((rows, TABLE_COLS), dtype=torch.int64).pin_memory() for _ in range(ring)]
         self._done = [None] * ring
         self._turn = 0
@@ -614,8 +757,11 @@ class ResidentTrainLoader(object):
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
     def batch(self, indices, params=None):
-        """the batch of images `indices`; `params` (a list of (i, j, flip, angle)) are drawn when not given"""
+        """the batch of images `indices`; `params` (a list of (i, j, flip, angle); with candidates = K > 1 a list of K such
+        sets per sample) are drawn when not given"""
         from ... import ops
+        if self.candidates > 1:
+            return self._batch_best_of(indices, params)
         ds, S = self.dataset, self.size
         draw = getattr(ds, "draw_params", None)       # a paired set draws on its LR grid
         if params is None and draw is not None:
@@ -647,6 +793,64 @@ class ResidentTrainLoader(object):
         if self.want_f32:
             return {"image_u8": out[0], "image": out[1]}
         return {"image_u8": out}
+
+    def _batch_best_of(self, indices, params):
+        """batch() with candidates = K > 1"""
+        from ... import ops
+        ds, S, K, n = self.dataset, self.size, self.candidates, len(indices)
+        draw = getattr(ds, "draw_params", None)       # a paired set draws on its LR grid
+        if params is None and draw is not None:
+            params = [draw_candidates(lambda: draw(k, S), K) for k in indices]
+        if params is None:
+            params = [draw_candidates(lambda: draw_train_params(ds.entries[k][1], ds.entries[k][2], S), K) for k in indices]
+        params = [list(ps) if isinstance(ps, (list, tuple)) else [] for ps in params]
+        if len(params) != n or any(len(ps) != K or any(not isinstance(p, (list, tuple)) or len(p) != 4 for p in ps)
+                                   for ps in params):
+            raise ValueError("ResidentTrainLoader: with candidates=%d, params is a list of %d parameter sets per sample" % (K, K))
+        rep = [k for k in indices for _ in range(K)]          # sample-major: all K of sample 0, then all K of sample 1
+        flat = [p for ps in params for p in ps]
+        slot = self._turn
+        self._turn = (slot + 1) % len(self._host)
+        if self._done[slot] is not None:
+            self._done[slot].synchronize()     # the upload that last read this pinned table
+        if hasattr(ds, "make_table"):                 # a paired set: [2, n * K, 12]
+            host = ds.make_table(rep, flat, S, out=self._host[slot])
+        else:
+            host = make_table([ds.entries[k] + (p,) for k, p in zip(rep, flat)], S, out=self._host[slot],
+                              yuv420=getattr(ds, "yuv420", False)).view(1, n * K, TABLE_COLS)
+        with torch.cuda.device(ds.device):
+            if self._stats is None:
+                self._stats = torch.zeros(3, dtype=torch.int64, device=ds.device)
+            cand = host.to(ds.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._done[slot] = ev
+            table, choice, activity = ops.aug_select(ds.pool, cand, n, K, S, yuv420=getattr(ds, "yuv420", False),
+                                                     blocks=host.size(0), stats=self._stats)
+            gather = getattr(ds, "gather", None)
+            if hasattr(ds, "make_table"):
+                out = gather(table, n, S, want_f32=self.want_f32)
+            elif gather is not None:
+                out = gather(table[0], n, S, want_f32=self.want_f32)
+            else:
+                out = ops.aug_gather_u8(ds.pool, table[0], n, S, want_f32=self.want_f32)
+        self.last_indices, self.last_params = list(indices), params
+        self.last_choice, self.last_activity = choice, activity
+        if hasattr(ds, "as_batch"):
+            return ds.as_batch(out, self.want_f32)
+        if self.want_f32:
+            return {"image_u8": out[0], "image": out[1]}
+        return {"image_u8": out}
+
+    def selection_stats(self):
+        """(sum of the chosen crops' activities, sum of the first candidates' activities, samples) over the batches since
+        the last call, and the counters start again.  It reads the device: once per epoch, not per batch.  (0, 0, 0) with
+        candidates = 1."""
+        if self._stats is None:
+            return 0, 0, 0
+        chosen, first, count = (int(v) for v in self._stats.tolist())
+        self._stats.zero_()
+        return chosen, first, count
 
     def __iter__(self):
         chunk = []

@@ -114,6 +114,21 @@ def take_video_args(a):
     return kw
 
 
+def take_crop_candidates(a, resident):
+    """Remove --crop-candidates from the parsed namespace `a` and return it as the run configs' keyword argument: {} with
+    K = 1 (everything is then what it was before the flag existed), {'crop_candidates': K} otherwise.  `resident`: the
+    run keeps its training set on the GPU (--resident or --video); without it K > 1 is refused."""
+    K = a.__dict__.pop("crop_candidates")
+    if not 1 <= K <= 16:
+        raise SystemExit("--crop-candidates must be 1 .. 16, got %d" % K)
+    if K == 1:
+        return {}
+    if not resident:
+        raise SystemExit("--crop-candidates %d needs --resident or --video: the selection runs on the resident pool "
+                         "(the training set in GPU memory); there is no PIL-side implementation" % K)
+    return {"crop_candidates": K}
+
+
 def refuse_pair_for_hr_input(video_kw, input_key, what):
     """the entry scripts' refusal of --video-lr for a network whose input is the HR image itself (the X4 family)"""
     if video_kw and video_kw.get("videos_lr") and input_key == "image":
@@ -172,12 +187,14 @@ class VideoFramesDataProvider(object):
     `train` is an augment.ResidentTrainLoader over one augment.ResidentVideoSet holding every selected frame (training
     and evaluation frames alike); `valid` is `test`.  With `videos_lr` (one per video; `video_lr_size` for headerless
     files) the set is an augment.ResidentVideoPairSet and every batch and evaluation item carries the decoded LR
-    stream's crop / frame; `rotate=False` trains without the rotation."""
+    stream's crop / frame; `rotate=False` trains without the rotation.  `crop_candidates=K` > 1: every training crop is
+    the most detailed of K drawn candidates (augment.ResidentTrainLoader(candidates=K); a paired set scores on its HR
+    pool); the sub-train and evaluation loaders are untouched."""
     SUB_SEED = 937162211     # DataProvider.SUB_SEED of div2k_setxx.py
 
     def __init__(self, videos, video_size=None, frames=None, valid_every=10, matrix="bt601", full_range=False,
                  train_batch_size=16, test_batch_size=1, image_size=32, num_replicas=None, rank=None,
-                 resident_max_bytes=32 << 30, videos_lr=None, video_lr_size=None, rotate=True):
+                 resident_max_bytes=32 << 30, videos_lr=None, video_lr_size=None, rotate=True, crop_candidates=1):
         import torch
         from ... import video
         from .augment import ResidentTrainLoader, ResidentVideoPairSet, ResidentVideoSet, count_frames
@@ -220,8 +237,10 @@ class VideoFramesDataProvider(object):
             sampler = RankShardSampler(self.train_indices, num_replicas, rank)
         else:
             sampler = torch.utils.data.SubsetRandomSampler(self.train_indices)
+        self.crop_candidates = int(crop_candidates)
         self.train = ResidentTrainLoader(self.resident_set, train_batch_size, sampler, self.active_img_size,
-                                         drop_last=True, want_f32=True)
+                                         drop_last=True, want_f32=True,
+                                         **({} if self.crop_candidates == 1 else dict(candidates=self.crop_candidates)))
         self.test = _EvalFrames(self.resident_set, self.eval_indices)
         self.valid = self.test
 

@@ -46,7 +46,7 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                  opt_param=None, weight_decay=4e-5, label_smoothing=0.1, no_decay_keys=None, mixup_alpha=None,
                  model_init="he_fout", validation_frequency=1, print_frequency=10, n_worker=32,
                  resize_scale=0.08, distort_color=None, image_size=32, allow_synthetic=None, resident=False,
-                 **kwargs):
+                 crop_candidates=1, **kwargs):
         super().__init__(n_epochs, init_lr, lr_schedule_type, lr_schedule_param, dataset, train_batch_size,
                          test_batch_size, valid_size, opt_type, opt_param, weight_decay, label_smoothing,
                          no_decay_keys, mixup_alpha, model_init, validation_frequency, print_frequency,
@@ -56,6 +56,12 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
         self.resize_scale = resize_scale
         self.distort_color = distort_color
         self.resident = bool(resident)
+        if int(crop_candidates) != 1:     # best of K candidate crops (data_providers/augment.py); the key exists only then
+            if not self.resident:
+                raise ValueError("crop_candidates=%d needs resident=True: the selection runs on the resident pool"
+                                 % int(crop_candidates))
+            self.crop_candidates = int(crop_candidates)
+            self._synthetic["crop_candidates"] = self.crop_candidates     # the stand-in selects on a resident pool too
         self.dataset_root = os.environ.get("OFASR_DIV2K_ROOT", "/SSD/div2k_setxx")
         self.allow_synthetic = (os.environ.get("OFASR_ALLOW_SYNTHETIC_DATA", "0") == "1") if allow_synthetic is None \
             else bool(allow_synthetic)
@@ -73,7 +79,8 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                     valid_size=self.valid_size, n_worker=self.n_worker, resize_scale=self.resize_scale,
                     distort_color=self.distort_color, image_size=self.image_size,
                     num_replicas=ws if ws > 1 else None, rank=dd.rank() if ws > 1 else None,
-                    resident=self.resident)
+                    resident=self.resident,
+                    **({} if self.__dict__.get("crop_candidates", 1) == 1 else dict(crop_candidates=self.crop_candidates)))
             elif self.allow_synthetic:
                 from ... import distributed as dd
                 if dd.rank() == 0:
@@ -102,7 +109,7 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
                  train_batch_size=256, test_batch_size=1, valid_size=None, opt_type="sgd", opt_param=None,
                  weight_decay=4e-5, label_smoothing=0.1, no_decay_keys=None, mixup_alpha=None, model_init="he_fout",
                  validation_frequency=1, print_frequency=10, n_worker=0, image_size=32, resident_max_bytes=32 << 30,
-                 videos_lr=None, video_lr_size=None, video_rotate=True, **kwargs):
+                 videos_lr=None, video_lr_size=None, video_rotate=True, crop_candidates=1, **kwargs):
         videos = [videos] if isinstance(videos, str) else list(videos)
         name = "video_frames: " + ", ".join(videos)
         if videos_lr is not None:
@@ -128,6 +135,8 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
             self.videos_lr = videos_lr
             self.video_lr_size = None if video_lr_size is None else tuple(video_lr_size)
             self.video_rotate = bool(video_rotate)
+        if int(crop_candidates) != 1:     # best of K candidate crops; the key exists only then
+            self.crop_candidates = int(crop_candidates)
 
     @property
     def data_provider(self):
@@ -142,5 +151,6 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
                 num_replicas=ws if ws > 1 else None, rank=dd.rank() if ws > 1 else None,
                 resident_max_bytes=self.resident_max_bytes,
                 **({} if self.__dict__.get("videos_lr") is None else dict(
-                    videos_lr=self.videos_lr, video_lr_size=self.video_lr_size, rotate=self.video_rotate)))
+                    videos_lr=self.videos_lr, video_lr_size=self.video_lr_size, rotate=self.video_rotate)),
+                **({} if self.__dict__.get("crop_candidates", 1) == 1 else dict(crop_candidates=self.crop_candidates)))
         return self.__dict__["_data_provider"]

@@ -252,6 +252,8 @@ class SRRunManager(object):
         if model_name is None:
             model_name = "checkpoint.pth.tar"
         checkpoint["dataset"] = self.run_config.dataset
+        if getattr(self.run_config, "crop_candidates", 1) != 1:      # best-of-K training crops (data_providers/augment.py)
+            checkpoint["crop_candidates"] = int(self.run_config.crop_candidates)
         model_path = os.path.join(self.save_path, model_name)
         with open(os.path.join(self.save_path, "latest.txt"), "w") as fout:
             fout.write(model_path + "\n")
@@ -476,7 +478,22 @@ class SRRunManager(object):
             psnrs.update(psnr_y(output, images), images.size(0))
             end = time.time()
         self._last_lr = new_lr
+        self.log_crop_selection(epoch)
         return losses.avg, psnrs.avg
+
+    def log_crop_selection(self, epoch):
+        """with best-of-K training crops (ResidentTrainLoader(candidates=K > 1)): one line per epoch, the mean luma
+        activity per difference in 8-bit levels (routing.mean_activity) of the chosen crops and of the first candidates
+        -- what a loader without candidates would have served.  The epoch's one read of the selection counters."""
+        loader = self.run_config.train_loader
+        if getattr(loader, "candidates", 1) <= 1:
+            return
+        from ... import routing
+        chosen, first, count = loader.selection_stats()
+        S, c = loader.size, max(count, 1)
+        self.write_log("Crop selection [%d]\tK=%d\tcrops %d\tmean activity chosen %.3f\tfirst candidate %.3f" % (
+            epoch + 1, loader.candidates, count, float(routing.mean_activity(chosen, S, S)) / c,
+            float(routing.mean_activity(first, S, S)) / c), prefix="train")
 
     def train(self, args, warmup_epoch=0, warmup_lr=0):
         """reference :516-541"""

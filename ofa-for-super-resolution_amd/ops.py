@@ -293,6 +293,40 @@ def aug_gather_yuv420_pair(hr_pool, lr_pool, table, n, S, f, matrix="bt601", ful
     return (hr, hr32, lr, lr32) if want_f32 else (hr, lr)
 
 
+def aug_select(pool, cand_table, n, K, S, yuv420=False, blocks=1, stats=None):
+    """Best of K candidate crops per sample, on the GPU: (table, choice, activity).  `cand_table`: int64 [blocks, n * K,
+    12] (or [n * K, 12] with blocks = 1) on the pool's device, the gathers' rows, sample-major; `blocks` = 2 for the
+    paired table (block 0 the HR rows, pool the HR pool).  The candidate whose S x S crop rectangle holds the largest
+    luma activity (routing.py's measure, before flip and rotation) wins, ties to the lowest index: `table` int64
+    [blocks, n, 12] holds the winners' rows for aug_gather_u8 / aug_gather_yuv420 (table[0]) / aug_gather_yuv420_pair
+    (table), `choice` int32 [n], `activity` int64 [n, K].  `stats`: None, or an int64 [3] tensor on the device to which the
+    call adds (sum of the chosen activities, sum of the first candidates', n).  No host synchronisation
+    (ofasr_aug_select, csrc/augment.hip; the definition is data_providers/augment.aug_select_np)."""
+    from .imagenet_codebase.data_providers.augment import aug_select_strips
+    name = "aug_select"
+    _gpu(pool, cand_table, stats)
+    n, K, S, blocks = int(n), int(K), int(S), int(blocks)
+    if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
+        raise _C.OfasrError("%s: pool is a contiguous 1-D uint8 tensor, got %s %s" % (name, pool.dtype, tuple(pool.shape)))
+    if cand_table.dtype != torch.int64 or not cand_table.is_contiguous() or cand_table.device != pool.device or \
+            cand_table.numel() != max(blocks * n * K, 0) * 12 or cand_table.size(-1) != 12:
+        raise _C.OfasrError("%s: cand_table is a contiguous int64 [%d, %d, 12] tensor on %s, got %s %s on %s"
+                            % (name, blocks, n * K, pool.device, cand_table.dtype, tuple(cand_table.shape), cand_table.device))
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() != 3 or not stats.is_contiguous() or
+                              stats.device != pool.device):
+        raise _C.OfasrError("%s: stats is a contiguous int64 [3] tensor on %s" % (name, pool.device))
+    table = torch.empty((max(blocks, 0), max(n, 0), 12), dtype=torch.int64, device=pool.device)
+    choice = torch.empty((max(n, 0),), dtype=torch.int32, device=pool.device)
+    activity = torch.empty((max(n, 0), max(K, 0)), dtype=torch.int64, device=pool.device)
+    strips = aug_select_strips(S) if 0 < S <= 4096 else 1
+    wst, wsp, wsn = _ws(max(n * K, 0) * strips * 8, pool.device)
+    with _timed(name, max(n * K, 0) * S * S * (1 if yuv420 else 3)):
+        _C.check(_C.lib().ofasr_aug_select(_p(pool), pool.numel(), _p(cand_table), blocks, n, K, S,
+                                           _C.AUG_YUV420 if yuv420 else _C.AUG_RGB_HWC, _p(table), _p(choice), _p(activity),
+                                           None if stats is None else _p(stats), wsp, wsn, _stream()), name)
+    return table, choice, activity
+
+
 # ------------------------------------------------------------------------------ Y-PSNR / Y-SSIM on the GPU
 def _quality_operand(t, what):
     """(contiguous tensor, format code, N, H, W) of one operand of quality_y"""

@@ -14,10 +14,14 @@
    f=4 on F resident 1920x1080 frames and their 480x270 LR frames against the two separate ops.aug_gather_yuv420
    launches that produce the same bytes (checked), on the same crops: the one launch's time, the two launches' times
    and their sum.
+ * the best-of-K leg (--crop-candidates 1,4,8; --only-candidates runs nothing else): the resident loader's img/s per K
+   (--repeats measurements each) on the PNG pool and on --yuv-frames 1920x1080 4:2:0 frames, and per K > 1 the GPU time
+   of ofasr_aug_select's two launches per batch; K = 1 is the loader without candidates.
 Prints one JSON line.
 usage: python tools/bench_augment.py [--files 32] [--entries 256] [--height 1356] [--width 2040] [--batches 200]
                                      [--warmup 10] [--host-batches 200] [--workers 16] [--skip-host]
-                                     [--yuv-frames 64] [--only-yuv] [--only-pair]"""
+                                     [--yuv-frames 64] [--only-yuv] [--only-pair]
+                                     [--crop-candidates 1,4,8] [--repeats 3] [--only-candidates]"""
 import argparse
 import importlib
 import json
@@ -179,6 +183,52 @@ def pair_leg(C, L, ops, aug, dev, N, S, frames, reps, f=4, h=270, w=480):
     return res
 
 
+class _FramePool(object):
+    """what ResidentTrainLoader needs of a ResidentVideoSet, over a pool that is on the device already"""
+    yuv420 = True
+
+    def __init__(self, pool, fb, frames, H, W):
+        self.pool, self.device = pool, pool.device
+        self.entries = [(k * fb, H, W) for k in range(frames)]
+        self.paths = ["frame#%d" % k for k in range(frames)]
+
+    def __len__(self):
+        return len(self.entries)
+
+    def gather(self, table, n, S, want_f32=False):
+        ops = importlib.import_module(PKG + ".ops")
+        return ops.aug_gather_yuv420(self.pool, table, n, S, want_f32=want_f32)
+
+
+def candidates_leg(C, L, aug, utils, dev, N, S, Ks, sets, batches, warmup, repeats, reps):
+    """best of K candidate crops (--crop-candidates K1,K2,...): per pool and K the resident loader's img/s (`repeats`
+    measurements each; the batch counts when its HR + LR images are on the device, as resident_img_per_s) and, for K > 1,
+    the GPU time of the two launches of ofasr_aug_select per batch.  K = 1 is the loader without candidates."""
+    import torch
+    sync = torch.cuda.synchronize
+
+    def step(b):
+        return utils.device_batch(b, dev)["image"].size(0)
+
+    res = {}
+    for name, ds in sets:
+        r = {"images": len(ds), "pool_bytes": int(ds.pool.numel())}
+        sampler = torch.utils.data.RandomSampler(range(len(ds)))
+        for K in Ks:
+            loader = aug.ResidentTrainLoader(ds, N, sampler, S, want_f32=True, **({} if K == 1 else dict(candidates=K)))
+            entry = {"img_per_s": [loader_rate(loader, batches, warmup, step, sync) for _ in range(repeats)]}
+            if K > 1:
+                idx = [torch.randint(0, len(ds), (N,)).tolist() for _ in range(reps)]
+                run = lambda ix: loader.batch(ix)
+                entry["activity_kernel_us"] = kernel_us(C, L, run, idx, "aug_select_activity_kernel")
+                entry["choose_kernel_us"] = kernel_us(C, L, run, idx, "aug_select_choose_kernel")
+                chosen, first, count = loader.selection_stats()
+                entry["activity_chosen_over_first"] = chosen / max(first, 1)
+            r["K=%d" % K] = entry
+        res[name] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=32)
@@ -194,6 +244,11 @@ def main():
     ap.add_argument("--yuv-frames", type=int, default=64, help="1920x1080 frames of the YUV leg (0: skip it)")
     ap.add_argument("--only-yuv", action="store_true", help="run the YUV leg alone")
     ap.add_argument("--only-pair", action="store_true", help="run the pair leg alone (--yuv-frames frame pairs)")
+    ap.add_argument("--crop-candidates", default=None, metavar="K1,K2,...",
+                    help="the best-of-K leg: the resident loader's img/s per K on the PNG pool and on --yuv-frames "
+                         "1920x1080 4:2:0 frames (1 = the loader without candidates)")
+    ap.add_argument("--repeats", type=int, default=3, help="measurements per K of the best-of-K leg")
+    ap.add_argument("--only-candidates", action="store_true", help="run the best-of-K leg alone")
     a = ap.parse_args()
     import torch
     C = importlib.import_module(PKG + "._C")
@@ -211,7 +266,9 @@ def main():
         out["yuv420_pair"] = pair_leg(C, L, ops, aug, dev, N, S, max(a.yuv_frames, 1), a.reps)
         print(json.dumps(out), flush=True)
         return
-    if a.yuv_frames > 0:
+    if a.only_candidates and not a.crop_candidates:
+        raise SystemExit("--only-candidates needs --crop-candidates K1,K2,...")
+    if a.yuv_frames > 0 and not a.only_candidates:
         out["yuv420"] = yuv_leg(C, L, ops, aug, dev, N, S, a.yuv_frames, a.reps)
     if a.only_yuv:
         print(json.dumps(out), flush=True)
@@ -228,6 +285,16 @@ def main():
         out["resident_decode_upload_s"] = time.perf_counter() - t0
         out["resident_bytes"] = prov.resident_set.nbytes
         loader = prov.train
+        if a.crop_candidates:
+            frames = max(a.yuv_frames, 1)
+            ypool, fb = synthetic_yuv_pool(dev, frames, 1080, 1920, 1)
+            sets = [("rgb", prov.resident_set), ("yuv420_1080p", _FramePool(ypool, fb, frames, 1080, 1920))]
+            out["crop_candidates"] = candidates_leg(C, L, aug, utils, dev, N, S, [int(k) for k in a.crop_candidates.split(",")],
+                                                    sets, a.batches, a.warmup, a.repeats, a.reps)
+            del ypool, sets
+            if a.only_candidates:
+                print(json.dumps(out), flush=True)
+                return
 
         # ---- the kernel: library per-launch events over `reps` launches with freshly drawn tables
         torch.manual_seed(0)

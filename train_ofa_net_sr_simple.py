@@ -37,10 +37,14 @@ def main():
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic images when DIV2K is absent")
     ap.add_argument("--resident", action="store_true",
                     help="keep the decoded training images on the GPU and augment them there")
+    ap.add_argument("--crop-candidates", type=int, default=1, metavar="K",
+                    help="draw K candidate crops per training sample and train on the most detailed one (1: off); "
+                         "needs --resident or --video")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     args = ap.parse_args()
     video_kw = vf.take_video_args(args)     # None without --video: `args` is then what it always was
+    args.__dict__.update(vf.take_crop_candidates(args, args.resident or bool(video_kw)))    # nothing with K = 1
     vf.refuse_pair_for_hr_input(video_kw, "image" if args.net == "x4" else None, "--net x4")
 
     import numpy as np

@@ -27,10 +27,14 @@ def main():
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic images when DIV2K is absent")
     ap.add_argument("--resident", action="store_true",
                     help="keep the decoded training images on the GPU and augment them there")
+    ap.add_argument("--crop-candidates", type=int, default=1, metavar="K",
+                    help="draw K candidate crops per training sample and train on the most detailed one (1: off); "
+                         "needs --resident or --video")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     a = ap.parse_args()
     video_kw = vf.take_video_args(a)
+    crop_kw = vf.take_crop_candidates(a, a.resident or bool(video_kw))
 
     import numpy as np
     import torch
@@ -46,7 +50,8 @@ def main():
     nets = importlib.import_module(PKG + ".elastic_nn.networks")
     args = argparse.Namespace(teacher_model=None, kd_ratio=0, kd_type="ce")
     kw = dict(n_epochs=a.n_epochs, init_lr=1e-3, opt_type="adam", weight_decay=3e-5, no_decay_keys="bn#bias",
-              label_smoothing=0.0, train_batch_size=a.batch, test_batch_size=1, image_size=a.image_size, n_worker=8)
+              label_smoothing=0.0, train_batch_size=a.batch, test_batch_size=1, image_size=a.image_size, n_worker=8,
+              **crop_kw)
     if video_kw:      # --video: the frames of raw YUV 4:2:0 video, resident on the GPU
         cfg = rm.VideoFramesRunConfig(**dict(kw, **video_kw))
     else:
