@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 313 /* + ofasr_aug_select */
+#define OFASR_VERSION 314 /* + ofasr_sr_loss_workspace / _fwd / _bwd */
 
 typedef enum {
     OFASR_OK = 0,
@@ -827,6 +827,46 @@ int ofasr_quality_y(const void* a, int fmt_a, const void* b, int fmt_b, int64_t 
 size_t ofasr_quality_mse_workspace(int64_t N, int64_t elems);
 int ofasr_quality_mse(const void* a, int fmt_a, const void* b, int fmt_b, int64_t N, int64_t elems, double* mse,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The training loss, its gradient and the logged Y-PSNR of one batch (csrc/loss.hip; host statement: losses.py) --
+ * replaces nn.MSELoss, the teacher term, utils.psnr_y_device and their backward, several dozen ATen launches, with
+ * two launches forward and one backward.  o (network output), t (HR batch), s (teacher output, NULL: no teacher term):
+ * planar NCHW [N, 3, H, W], each OFASR_F32 / OFASR_F16 / OFASR_BF16 on its own, each read as fp32.  M = 3 N H W.
+ *   d = o - t, e = o - s in fp32.  rho by `kind`:
+ *     OFASR_LOSS_MSE          rho(x) = x * x                   rho'(x) = x + x
+ *     OFASR_LOSS_L1           rho(x) = |x|                     rho'(x) = 1, -1 or 0 by the sign of x (0 at 0 and at NaN)
+ *     OFASR_LOSS_CHARBONNIER  rho(x) = sqrt(x * x + eps2)      rho'(x) = x / rho(x)
+ *   every step one fp32 operation, sqrt and the division correctly rounded, nothing contracted; eps2 = (float)(eps * eps),
+ *   eps > 0 (read for OFASR_LOSS_CHARBONNIER only).
+ * ofasr_sr_loss_fwd writes result[0 .. 5] (device, 8-byte aligned, 48 bytes):
+ *   [0] sum of rho(d), [1] sum of rho(e) (0 without s): fp64 sums of the fp32 terms in a fixed order (no atomics)
+ *   [2] L = w_main * [0] / M + w_kd * [1] / M, in fp64
+ *   [3] the int64 Y-SSE of the batch: ofasr_quality_y's quantise and luma on o and t, sum of (Yo - Yt)^2 over all pixels
+ *   [4] 20 log10(255 / sqrt([3] / psnr_count)) in fp64; psnr_count > 0 is the caller's pixel count
+ *   [5] (float)L in the low four bytes, zero above: the value a framework hands to its autograd
+ * One streaming kernel (a workgroup leaves one partial in `workspace`) + one folding workgroup on `stream`.
+ * workspace: ofasr_sr_loss_workspace(M) bytes (host-only query; 0 for M <= 0), 16-byte aligned.
+ * ofasr_sr_loss_bwd writes grad [N, 3, H, W] in o's format:
+ *   ga = ca * g, gb = cb * g with ca = (float)(w_main / M), cb = (float)(w_kd / M) and g the incoming gradient, ONE fp32
+ *   word read from device memory; per element fl(ga * rho'(d)), with s fl(fl(ga * rho'(d)) + fl(gb * rho'(e))), then
+ *   rounded to nearest even into o's format.  One kernel, the forward's walk; no workspace.
+ * With every tensor of a call at a 16-byte aligned address and H * W % 8 == 0 the call reads and writes 16-byte requests,
+ * otherwise element by element (any element-aligned address is accepted); 64-bit offsets; M <= 2^40.
+ * OFASR_ERR_INVALID_ARG: a null pointer (s excepted), an unknown format or kind, a non-positive size, eps <= 0 or not
+ * finite with OFASR_LOSS_CHARBONNIER, psnr_count <= 0, a misaligned result.  OFASR_ERR_UNSUPPORTED: M > 2^40.
+ * OFASR_ERR_WORKSPACE: workspace null, misaligned or too small.  Nothing is launched in any of these cases.
+ * ------------------------------------------------------------------------------------------- */
+#define OFASR_LOSS_MSE 0
+#define OFASR_LOSS_L1 1
+#define OFASR_LOSS_CHARBONNIER 2
+size_t ofasr_sr_loss_workspace(int64_t elems);
+int ofasr_sr_loss_fwd(const void* o, int fmt_o, const void* t, int fmt_t, const void* s, int fmt_s, int64_t N, int64_t H,
+                      int64_t W, int kind, double eps, double w_main, double w_kd, double psnr_count, double* result,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int ofasr_sr_loss_bwd(const void* o, int fmt_o, const void* t, int fmt_t, const void* s, int fmt_s, const float* g,
+                      int64_t N, int64_t H, int64_t W, int kind, double eps, double w_main, double w_kd, void* grad,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (tests and bench.py; nothing on the product path calls these).

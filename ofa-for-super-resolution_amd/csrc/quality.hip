@@ -26,7 +26,7 @@
 // needs no ATen kernel at all.
 //
 // Every global read is bounds-checked against the shaved image, offsets are 64-bit.
-#include "ofasr_common.h"
+#include "quality_math.h"   // q_quant, q_luma
 #include <math.h>
 
 #pragma clang fp contract(off)   // the formula's groupings are meant as written (identical operands give exactly 1)
@@ -44,19 +44,6 @@ struct QOperand {
     const void* p;
     int fmt;                      // OFASR_F32 / OFASR_F16 / OFASR_BF16: planar NCHW; OFASR_U8_HWC: interleaved, one image
 };
-
-__device__ __forceinline__ uint32_t q_quant(float v) {
-    const float f = fminf(fmaxf(v, 0.0f), 1.0f);
-    return (uint32_t)rintf(__fmul_rn(f, 255.0f));
-}
-
-__device__ __forceinline__ uint32_t q_luma(uint32_t r, uint32_t g, uint32_t b) {
-    const uint32_t num = 65481u * r + 128553u * g + 24966u * b;   // <= 55 845 000
-    const uint32_t q = num / 255000u, rem = num - q * 255000u;
-    uint32_t y = q + 16u;
-    if (rem > 127500u || (rem == 127500u && (y & 1u))) ++y;
-    return y;
-}
 
 // luma of pixel (y, x) of image n of an operand ([N, 3, H, W] planar or [H, W, 3] interleaved)
 __device__ __forceinline__ uint32_t q_pixel(const QOperand& o, long long n, long long H, long long W, long long y,

@@ -17,11 +17,10 @@ import random
 import time
 
 import torch
-import torch.nn.functional as F
 
 from ... import ops
 from ...imagenet_codebase.run_manager.sr_run_manager import SRRunManager  # noqa: F401
-from ...utils import AverageMeter, device_batch, int2list, list_mean, psnr_y_device, subset_mean
+from ...utils import AverageMeter, device_batch, int2list, list_mean, subset_mean
 
 
 def validate(run_manager, epoch=0, is_test=True, image_size_list=None, width_mult_list=None, ks_list=None,
@@ -128,12 +127,9 @@ def train_one_epoch(run_manager, args, epoch, warmup_epochs=0, warmup_lr=0):
                 lr_img = x2 if settings["pixel_d"][0] == 1 else x4
             with run_manager.autocast():
                 output = run_manager.net(lr_img)
-            output = output.float()
-            loss = run_manager.train_criterion(output, images)
-            if soft_logits is not None:
-                loss = (args.kd_ratio * F.mse_loss(output, soft_logits) + loss) * (2 / (args.kd_ratio + 1))
+            loss, psnr, output = run_manager.train_loss(output, images, soft_logits, args.kd_ratio, shrinking=True)
             sub_losses.append(loss.detach())
-            sub_psnrs.append(psnr_y_device(output, images))
+            sub_psnrs.append(psnr)
             if sub == args.dynamic_batch_size - 1:
                 run_manager.last_backward_next()
             loss.backward()

@@ -22,7 +22,9 @@ import torch.nn as nn
 from ... import distributed as dd
 from ... import ops
 from ...graphed import GraphedEval
-from ...utils import AverageMeter, bucket_by_size, device_batch, psnr_from_sse, psnr_y, psnr_y_per_image
+from ... import losses as sr_losses
+from ...utils import (AverageMeter, bucket_by_size, device_batch, psnr_from_sse, psnr_y, psnr_y_device,
+                      psnr_y_per_image)
 from ..utils import get_net_info
 
 
@@ -127,7 +129,13 @@ class SRRunManager(object):
     train_criterion, test_criterion; plus `reducer` (None on one GPU)."""
 
     def __init__(self, path, net, run_config, init=True, measure_latency=None, no_gpu=False, mix_prec=None,
-                 num_gpus=None, args=None):
+                 num_gpus=None, args=None, loss="reference", loss_eps=sr_losses.DEFAULT_EPS):
+        if loss != "reference" and loss not in sr_losses.KINDS:
+            raise ValueError("loss must be 'reference' or one of %s, got %r" % (", ".join(sr_losses.KINDS), loss))
+        if not (loss_eps > 0 and math.isfinite(loss_eps)):
+            raise ValueError("loss_eps must be positive, got %r" % (loss_eps,))
+        self.loss = loss           # 'reference': nn.MSELoss through ATen, as ever; else the fused HIP loss (train_loss)
+        self.loss_eps = float(loss_eps)
         self.path = path
         self.net = net
         self.run_config = run_config
@@ -159,6 +167,9 @@ class SRRunManager(object):
 
         self.train_criterion = nn.MSELoss()
         self.test_criterion = nn.MSELoss()
+        if self.loss != "reference":
+            self.write_log("Training loss: %s%s (fused HIP loss, ops.sr_loss)" % (
+                self.loss, " eps %g" % self.loss_eps if self.loss == "charbonnier" else ""), prefix="train")
 
         if self.run_config.no_decay_keys:
             keys = self.run_config.no_decay_keys.split("#")
@@ -254,6 +265,10 @@ class SRRunManager(object):
         checkpoint["dataset"] = self.run_config.dataset
         if getattr(self.run_config, "crop_candidates", 1) != 1:      # best-of-K training crops (data_providers/augment.py)
             checkpoint["crop_candidates"] = int(self.run_config.crop_candidates)
+        if self.loss != "reference":
+            checkpoint["loss"] = self.loss
+            if self.loss == "charbonnier":
+                checkpoint["loss_eps"] = self.loss_eps
         model_path = os.path.join(self.save_path, model_name)
         with open(os.path.join(self.save_path, "latest.txt"), "w") as fout:
             fout.write(model_path + "\n")
@@ -437,6 +452,28 @@ class SRRunManager(object):
         return {"loss": mean(mse), "psnr": mean(psnr), "ssim": mean(ssim), "calls": calls, "psnr_per_image": psnr,
                 "ssim_per_image": ssim}
 
+    def train_loss(self, output, images, soft=None, kd_ratio=0, shrinking=False):
+        """The loss section of one training (sub-)step, for both loops: (loss, psnr, output).  `output` is the network's
+        output as the autocast region left it, `soft` the teacher's or None; `shrinking` tells the progressive-shrinking
+        loop, which scales the sum by 2 / (kd_ratio + 1) and takes its PSNR on the device, from the teacher loop.
+        loss='reference': the lines the two loops always ran -- output.float(), nn.MSELoss, F.mse_loss against the
+        teacher, utils.psnr_y_device (psnr is None in the teacher loop, which scores `output` on the host after its
+        step).  Otherwise ops.sr_loss on the output as it is: loss, gradient and PSNR from the HIP kernels, psnr a 0-dim
+        fp64 view of the result buffer."""
+        if self.loss == "reference":
+            output = output.float()
+            loss = self.train_criterion(output, images)
+            if soft is not None:
+                loss = kd_ratio * torch.nn.functional.mse_loss(output, soft) + loss
+                if shrinking:
+                    loss = loss * (2 / (kd_ratio + 1))
+            return loss, (psnr_y_device(output, images) if shrinking else None), output
+        w_main, w_kd = sr_losses.kd_weights(kd_ratio, shrinking) if soft is not None else (1.0, 0.0)
+        n, _, h, w = output.shape
+        loss, res = ops.sr_loss(output, images, soft, kind=self.loss, eps=self.loss_eps, w_main=w_main, w_kd=w_kd,
+                                psnr_count=sr_losses.mosaic_count(n, h, w))
+        return loss, res[ops.SR_LOSS_PSNR], output
+
     def train_one_epoch(self, args, epoch, warmup_epochs=0, warmup_lr=0, input_key="2x_down_image"):
         """fixed-architecture ("teacher") epoch: BatchNorm layers run in eval mode (frozen statistics,
         reference :417-420), MSE loss, one optimizer step per batch.  Returns (mean loss, mean PSNR)."""
@@ -462,20 +499,19 @@ class SRRunManager(object):
             images, lr_img = mini_batch["image"], mini_batch[input_key]
             with self.autocast():
                 output = self.net(lr_img)
-            output = output.float()
-            loss = self.train_criterion(output, images)
             teacher = getattr(args, "teacher_model", None)
+            soft = None
             if teacher is not None:
                 teacher.train()
                 with torch.no_grad():
                     soft = teacher(images).detach()
-                loss = args.kd_ratio * torch.nn.functional.mse_loss(output, soft) + loss
+            loss, psnr, output = self.train_loss(output, images, soft, args.kd_ratio)
             self.zero_grad()
             loss.backward()
             ops.flush_deferred()   # the MB blocks' weight gradients: joined once per backward pass (ops.py)
             self.step()
             losses.update(loss.item(), images.size(0))
-            psnrs.update(psnr_y(output, images), images.size(0))
+            psnrs.update(psnr_y(output, images) if psnr is None else float(psnr), images.size(0))
             end = time.time()
         self._last_lr = new_lr
         self.log_crop_selection(epoch)

@@ -387,6 +387,83 @@ def quality_mse(output, target, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------ the training loss
+# slots of sr_loss's result buffer (fp64 [6]; include/ofasr.h): the two fp64 sums, L in fp64, the bits of the int64 Y-SSE,
+# the Y-PSNR, and fp32(L) in the low half of the last word
+SR_LOSS_SUM_MAIN, SR_LOSS_SUM_KD, SR_LOSS_VALUE, SR_LOSS_Y_SSE, SR_LOSS_PSNR, SR_LOSS_VALUE_F32 = range(6)
+
+
+class _SrLossFn(Function):
+    """forward: ofasr_sr_loss_fwd (stream kernel + fold); backward: ofasr_sr_loss_bwd, which reads the incoming gradient
+    where it is and writes dL/d(output) in output's dtype.  `cfg`: (target, soft, result buffer, kind code, eps, w_main,
+    w_kd, psnr_count) -- the tensors in it are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, output, cfg):
+        t, s, res, kind, eps, w_main, w_kd, count = cfg
+        o = output.contiguous()
+        N, _, H, W = o.shape
+        L = _C.lib()
+        wst, wsp, wsn = _ws(L.ofasr_sr_loss_workspace(o.numel()), o.device)
+        nbytes = sum(x.numel() * x.element_size() for x in (o, t, s) if x is not None)
+        with _timed("sr_loss_fwd", nbytes):
+            _C.check(L.ofasr_sr_loss_fwd(_p(o), _dt(o), _p(t), _dt(t), None if s is None else _p(s),
+                                         0 if s is None else _dt(s), N, H, W, kind, eps, w_main, w_kd, count, _p(res),
+                                         wsp, wsn, _stream()), "sr_loss_fwd")
+        ctx.save_for_backward(o)
+        ctx.cfg = (t, s, kind, eps, w_main, w_kd)
+        return res[SR_LOSS_VALUE_F32:].view(torch.float32)[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        o, = ctx.saved_tensors
+        t, s, kind, eps, w_main, w_kd = ctx.cfg
+        if not g.is_cuda or g.dtype != torch.float32:
+            raise _C.OfasrError("sr_loss: the incoming gradient is a float32 GPU scalar, got %s on %s" % (g.dtype, g.device))
+        g = g.contiguous()
+        N, _, H, W = o.shape
+        grad = torch.empty_like(o)
+        nbytes = sum(x.numel() * x.element_size() for x in (o, o, t, s) if x is not None)
+        with _timed("sr_loss_bwd", nbytes):
+            _C.check(_C.lib().ofasr_sr_loss_bwd(_p(o), _dt(o), _p(t), _dt(t), None if s is None else _p(s),
+                                                0 if s is None else _dt(s), _p(g), N, H, W, kind, eps, w_main, w_kd,
+                                                _p(grad), _stream()), "sr_loss_bwd")
+        return grad, None
+
+
+def sr_loss(output, target, soft=None, kind="l1", eps=1e-3, w_main=1.0, w_kd=0.0, psnr_count=None, out=None):
+    """(loss, result): the training loss w_main * mean rho(output - target) + w_kd * mean rho(output - soft) as a
+    differentiable 0-dim float32 tensor, and the fp64 [6] result buffer it is a view of (slots SR_LOSS_*: the two fp64
+    sums, the loss in fp64, the bits of the exact int64 Y-SSE of output against target, its Y-PSNR over `psnr_count`
+    pixels -- default N * H * W --, fp32(loss)).  `kind`: "mse", "l1" or "charbonnier" (`eps`); the definition is
+    losses.py.  output, target and soft are [N, 3, H, W] GPU batches of f32 / f16 / bf16, each on its own; the gradient
+    reaches `output` alone, in its dtype.  Two launches forward, one backward, no ATen kernel and no host sync
+    (ofasr_sr_loss_fwd / ofasr_sr_loss_bwd, csrc/loss.hip).  `out`: a contiguous fp64 [6] GPU tensor to write into."""
+    from . import losses
+    if kind not in losses.KINDS:
+        raise _C.OfasrError("sr_loss: unknown kind %r (one of %s)" % (kind, ", ".join(losses.KINDS)))
+    if output.dim() != 4 or output.size(1) != 3:
+        raise _C.OfasrError("sr_loss: output is an NCHW RGB batch [N, 3, H, W], got %s" % (tuple(output.shape),))
+    for what, x in (("target", target), ("soft", soft)):
+        if x is not None and (x.shape != output.shape or x.device != output.device):
+            raise _C.OfasrError("sr_loss: %s is %s on %s, output is %s on %s"
+                                % (what, tuple(x.shape), x.device, tuple(output.shape), output.device))
+    _gpu(output, target, soft, out)
+    for x in (output, target, soft):
+        if x is not None:
+            _dt(x)
+    if out is None:
+        out = torch.empty(6, dtype=torch.float64, device=output.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (6,) or not out.is_contiguous() or out.device != output.device:
+        raise _C.OfasrError("sr_loss: out must be a contiguous fp64 [6] tensor on %s" % output.device)
+    N, _, H, W = output.shape
+    count = float(N * H * W if psnr_count is None else psnr_count)
+    cfg = (target.detach().contiguous(), None if soft is None else soft.detach().contiguous(), out,
+           losses.KINDS.index(kind), float(eps), float(w_main), float(w_kd), count)
+    return _SrLossFn.apply(output, cfg), out
+
+
 # ------------------------------------------------------------------------------ YUV 4:2:0 frames
 YUV_DEPTHS = {torch.uint8: 8, torch.uint16: 10}     # the depth a plane's dtype stands for
 YUV_DTYPES = {8: torch.uint8, 10: torch.uint16}

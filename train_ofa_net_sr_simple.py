@@ -40,9 +40,15 @@ def main():
     ap.add_argument("--crop-candidates", type=int, default=1, metavar="K",
                     help="draw K candidate crops per training sample and train on the most detailed one (1: off); "
                          "needs --resident or --video")
+    ap.add_argument("--loss", default="reference", choices=["reference", "mse", "l1", "charbonnier"],
+                    help="training loss: reference = nn.MSELoss through ATen, as ever; the others run the fused HIP "
+                         "loss kernels (ops.sr_loss)")
+    ap.add_argument("--loss-eps", type=float, default=None, metavar="E", help="the Charbonnier eps (default 1e-3)")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     args = ap.parse_args()
+    loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, args.loss, args.__dict__.pop("loss_eps"))
+    loss = args.__dict__.pop("loss")        # `args` goes into the run config: it stays what it always was
     video_kw = vf.take_video_args(args)     # None without --video: `args` is then what it always was
     args.__dict__.update(vf.take_crop_candidates(args, args.resident or bool(video_kw)))    # nothing with K = 1
     vf.refuse_pair_for_hr_input(video_kw, "image" if args.net == "x4" else None, "--net x4")
@@ -129,7 +135,8 @@ def main():
               ks_list=args.ks_list, expand_ratio_list=args.expand_list, depth_list=args.depth_list,
               pixelshuffle_depth_list=args.pixelshuffle_depth_list)
     run_manager = rm.SRRunManager(args.path, net, run_config, mix_prec=args.mix_prec,
-                                  num_gpus=int(os.environ.get("WORLD_SIZE", "1")), args=args)
+                                  num_gpus=int(os.environ.get("WORLD_SIZE", "1")), args=args, loss=loss,
+                                  loss_eps=loss_eps)
     run_manager.save_config()
 
     validate_func_dict = {"image_size_list": None, "width_mult_list": None,

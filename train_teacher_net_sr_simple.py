@@ -30,9 +30,14 @@ def main():
     ap.add_argument("--crop-candidates", type=int, default=1, metavar="K",
                     help="draw K candidate crops per training sample and train on the most detailed one (1: off); "
                          "needs --resident or --video")
+    ap.add_argument("--loss", default="reference", choices=["reference", "mse", "l1", "charbonnier"],
+                    help="training loss: reference = nn.MSELoss through ATen, as ever; the others run the fused HIP "
+                         "loss kernels (ops.sr_loss)")
+    ap.add_argument("--loss-eps", type=float, default=None, metavar="E", help="the Charbonnier eps (default 1e-3)")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     a = ap.parse_args()
+    loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, a.loss, a.loss_eps)
     video_kw = vf.take_video_args(a)
     crop_kw = vf.take_crop_candidates(a, a.resident or bool(video_kw))
 
@@ -59,7 +64,7 @@ def main():
     net = nets.OFAMobileNetS4(ks_list=[a.ks], expand_ratio_list=[a.expand], depth_list=[a.depth],
                               pixelshuffle_depth_list=[a.pixelshuffle_depth])
     mgr = rm.SRRunManager(a.path, net, cfg, mix_prec=a.mix_prec, num_gpus=int(os.environ.get("WORLD_SIZE", "1")),
-                          args=args)
+                          args=args, loss=a.loss, loss_eps=loss_eps)
     mgr.save_config()
     mgr.train(args)
     if dist.is_initialized():
