@@ -7,11 +7,6 @@
 
 namespace ofasr {
 
-template <typename T> struct add_vec4;
-template <> struct add_vec4<float> { typedef float4 type; };
-template <> struct add_vec4<bf16_t> { typedef uint2 type; };
-template <> struct add_vec4<f16_t> { typedef uint2 type; };
-
 __device__ __forceinline__ float4 add4(float4 a, float4 b) {
     return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
 }
@@ -20,8 +15,7 @@ template <typename T> __device__ __forceinline__ uint2 add4(uint2 a, uint2 b) {
     unpack2<T>(a.x, a0, a1), unpack2<T>(a.y, a2, a3), unpack2<T>(b.x, b0, b1), unpack2<T>(b.y, b2, b3);
     return make_uint2(pack2<T>(__fadd_rn(a0, b0), __fadd_rn(a1, b1)), pack2<T>(__fadd_rn(a2, b2), __fadd_rn(a3, b3)));
 }
-template <typename T> __device__ __forceinline__ typename add_vec4<T>::type add_vec(typename add_vec4<T>::type a,
-                                                                                    typename add_vec4<T>::type b);
+template <typename T> __device__ __forceinline__ typename vec4<T>::type add_vec(typename vec4<T>::type a, typename vec4<T>::type b);
 template <> __device__ __forceinline__ float4 add_vec<float>(float4 a, float4 b) { return add4(a, b); }
 template <> __device__ __forceinline__ uint2 add_vec<bf16_t>(uint2 a, uint2 b) { return add4<bf16_t>(a, b); }
 template <> __device__ __forceinline__ uint2 add_vec<f16_t>(uint2 a, uint2 b) { return add4<f16_t>(a, b); }
@@ -29,7 +23,7 @@ template <> __device__ __forceinline__ uint2 add_vec<f16_t>(uint2 a, uint2 b) { 
 // grid: lanes over ceil(n / 4) groups in a grid-stride loop
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) add_kernel(const T* a, const T* b, T* y, long long n) {
-    typedef typename add_vec4<T>::type V;
+    typedef typename vec4<T>::type V;
     const long long groups = (n + 3) >> 2;
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
         const long long i = g * 4;
@@ -56,8 +50,9 @@ template <typename T> static void add_launch(const void* a, const void* b, void*
     const int64_t blocks = cdiv(cdiv(n, 4), 256);
     const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks)));
     prof_note(3.0 * (double)n * sizeof(T), (double)n);
-    if (vec) OFASR_LAUNCH((add_kernel<T, true>), grid, dim3(256), 0, st, (const T*)a, (const T*)b, (T*)y, (long long)n);
-    else OFASR_LAUNCH((add_kernel<T, false>), grid, dim3(256), 0, st, (const T*)a, (const T*)b, (T*)y, (long long)n);
+    dispatch_bool(vec, [&](auto VEC) {
+        OFASR_LAUNCH((add_kernel<T, VEC>), grid, dim3(256), 0, st, (const T*)a, (const T*)b, (T*)y, (long long)n);
+    });
 }
 
 }  // namespace ofasr
@@ -68,12 +63,9 @@ OFASR_EXPORT int ofasr_add(const void* a, const void* b, void* y, int64_t n, int
     const char* name = "ofasr_add";
     OFASR_REQUIRE(a && b && y, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
+    OFASR_REQUIRE_DTYPE(dtype);
     OFASR_REQUIRE(n <= (1LL << 40), OFASR_ERR_UNSUPPORTED, "%s: tensor too large", name);
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F32) add_launch<float>(a, b, y, n, st);
-    else if (dtype == OFASR_BF16) add_launch<bf16_t>(a, b, y, n, st);
-    else add_launch<f16_t>(a, b, y, n, st);
+    dispatch_float(dtype, [&](auto t) { add_launch<typename decltype(t)::type>(a, b, y, n, st); });
     return check_launch(name);
 }

@@ -264,18 +264,15 @@ static void aug_pair_launch(const AugSide& hr, const AugSide& lr, int64_t n, con
 }
 template <bool VEC_HR, bool VEC_LR>
 static void aug_pair_f32(const AugSide& hr, const AugSide& lr, int64_t n, const YuvDec& D, hipStream_t st) {
-    if (hr.out_f32) aug_pair_launch<VEC_HR, VEC_LR, true>(hr, lr, n, D, st);
-    else aug_pair_launch<VEC_HR, VEC_LR, false>(hr, lr, n, D, st);
+    dispatch_bool(hr.out_f32 != nullptr, [&](auto F32) { aug_pair_launch<VEC_HR, VEC_LR, F32>(hr, lr, n, D, st); });
 }
 static bool aug_vec_ok(const AugSide& s) {
-    return s.S % 4 == 0 && reinterpret_cast<uintptr_t>(s.out_u8) % 4 == 0 && reinterpret_cast<uintptr_t>(s.out_f32) % 16 == 0;
+    return s.S % 4 == 0 && reinterpret_cast<uintptr_t>(s.out_u8) % 4 == 0 && aligned16(s.out_f32);
 }
 static void aug_gather_pair(const AugSide& hr, const AugSide& lr, int64_t n, const YuvDec& D, hipStream_t st) {
-    const bool vh = aug_vec_ok(hr), vl = aug_vec_ok(lr);
-    if (vh && vl) aug_pair_f32<true, true>(hr, lr, n, D, st);
-    else if (vh) aug_pair_f32<true, false>(hr, lr, n, D, st);
-    else if (vl) aug_pair_f32<false, true>(hr, lr, n, D, st);
-    else aug_pair_f32<false, false>(hr, lr, n, D, st);
+    dispatch_bool(aug_vec_ok(hr), [&](auto VEC_HR) {
+        dispatch_bool(aug_vec_ok(lr), [&](auto VEC_LR) { aug_pair_f32<VEC_HR, VEC_LR>(hr, lr, n, D, st); });
+    });
 }
 
 // the launch of either kernel (YUV: the 4:2:0 one, which takes D) and the one VEC / F32 ladder
@@ -294,15 +291,12 @@ static void aug_launch(const void* pool, int64_t pool_bytes, const int64_t* tabl
 template <bool YUV>
 static void aug_gather(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t n, int64_t S, const YuvDec& D,
                        void* out_u8, void* out_f32, hipStream_t st) {
-    const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(out_u8) % 4 == 0 &&
-                     reinterpret_cast<uintptr_t>(out_f32) % 16 == 0;
-    if (out_f32) {
-        if (vec) aug_launch<YUV, true, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-        else aug_launch<YUV, false, true>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-    } else {
-        if (vec) aug_launch<YUV, true, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-        else aug_launch<YUV, false, false>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
-    }
+    const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(out_u8) % 4 == 0 && aligned16(out_f32);
+    dispatch_bool(vec, [&](auto VEC) {
+        dispatch_bool(out_f32 != nullptr, [&](auto F32) {
+            aug_launch<YUV, VEC, F32>(pool, pool_bytes, table, n, S, D, out_u8, out_f32, st);
+        });
+    });
 }
 
 // ---- best of K candidate crops (ofasr_aug_select) ------------------------------------------------------------------------
@@ -582,12 +576,10 @@ OFASR_EXPORT int ofasr_aug_select(const void* pool, int64_t pool_bytes, const in
                   (long long)(n * K * strips));
     const dim3 grid((unsigned)strips, (unsigned)(n * K));
     prof_note((double)(n * K) * (double)(S * S) * (layout == OFASR_AUG_YUV420 ? 1.0 : 3.0), 0.0);
-    if (layout == OFASR_AUG_YUV420)
-        OFASR_LAUNCH(aug_select_activity_kernel<1>, grid, dim3(AUG_SELECT_THREADS), 0, as_stream(stream), (const uint8_t*)pool,
+    dispatch_int<1, 3>(layout == OFASR_AUG_YUV420 ? 1 : 3, [&](auto BPP) {      // bytes per pixel of the plane that is measured
+        OFASR_LAUNCH(aug_select_activity_kernel<BPP>, grid, dim3(AUG_SELECT_THREADS), 0, as_stream(stream), (const uint8_t*)pool,
                      (long long)pool_bytes, (const long long*)cand, (int)S, (long long*)workspace);
-    else
-        OFASR_LAUNCH(aug_select_activity_kernel<3>, grid, dim3(AUG_SELECT_THREADS), 0, as_stream(stream), (const uint8_t*)pool,
-                     (long long)pool_bytes, (const long long*)cand, (int)S, (long long*)workspace);
+    });
     prof_note((double)n * (double)K * (8.0 * (double)strips + 8.0) + (double)n * (double)blocks * 192.0, 0.0);
     OFASR_LAUNCH(aug_select_choose_kernel, dim3((unsigned)n), dim3(64), 0, as_stream(stream), (const long long*)workspace,
                  (int)strips, (const long long*)cand, (int)blocks, (long long)n, (int)K, (long long*)out_table, (int*)choice,

@@ -670,29 +670,28 @@ static int bn_parts(int64_t N, int64_t C) {
 static int check_bn(const char* name, int64_t N, int64_t C, int64_t HW, int dtype) {
     OFASR_REQUIRE(N > 0 && C > 0 && HW > 0, OFASR_ERR_INVALID_ARG, "%s: bad shape N=%lld C=%lld HW=%lld", name,
                   (long long)N, (long long)C, (long long)HW);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG,
-                  "%s: bad dtype %d", name, dtype);
+    OFASR_REQUIRE(is_float_dtype(dtype), OFASR_ERR_INVALID_ARG, "%s: bad dtype %d", name, dtype);
     OFASR_REQUIRE(N <= INT32_MAX && C <= 65535 * 32 && HW <= INT32_MAX, OFASR_ERR_UNSUPPORTED, "%s: too large", name);
     return OFASR_OK;
 }
 
 static bool vec_ok(int64_t HW, int dtype, const void* a, const void* b, const void* c, const void* d) {
-    const int V = dtype == OFASR_F32 ? 4 : 8;
-    uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                     reinterpret_cast<uintptr_t>(d);
-    return (HW % V) == 0 && (bits & 15) == 0;
+    const int V = 16 / (int)elem_bytes(dtype);
+    return (HW % V) == 0 && aligned16(a, b, c, d);
+}
+
+// the kernel variant of a BN pass: f(type tag, VEC, ACT, RES) for a checked dtype; act 1 is ReLU6, anything else none
+template <typename F> static void bn_dispatch(int dtype, bool vec, int act, bool res, F&& f) {
+    dispatch_float(dtype, [&](auto t) {
+        dispatch_bool(vec, [&](auto VEC) {
+            dispatch_int<1, 0>(act, [&](auto ACT) { dispatch_bool(res, [&](auto RES) { f(t, VEC, ACT, RES); }); });
+        });
+    });
 }
 
 }  // namespace ofasr
 
 using namespace ofasr;
-
-#define OFASR_BN_DISPATCH_T(dtype, CALL)      \
-    switch (dtype) {                          \
-        case OFASR_F32: { using T = float; CALL; } break;   \
-        case OFASR_F16: { using T = f16_t; CALL; } break;   \
-        default: { using T = bf16_t; CALL; } break;         \
-    }
 
 OFASR_EXPORT size_t ofasr_bn_workspace(int64_t N, int64_t C) {
     if (N <= 0 || C <= 0) return 0;
@@ -710,12 +709,13 @@ OFASR_EXPORT int ofasr_bn_stats(const void* x, int64_t N, int64_t C, int64_t HW,
     dim3 grid((unsigned)C, (unsigned)P);
     hipStream_t st = as_stream(stream);
     const bool v = vec_ok(HW, dtype, x, nullptr, nullptr, nullptr);
-    prof_note((dtype == OFASR_F32 ? 4.0 : 2.0) * (double)N * (double)C * (double)HW, 0.0);
-    OFASR_BN_DISPATCH_T(dtype, {
-        if (v) OFASR_LAUNCH((bn_stats_kernel<T, true>), grid, dim3(BN_THREADS), 0, st, (const T*)x,
-                                  (double*)workspace, (int)N, (int)C, (int)HW, P);
-        else OFASR_LAUNCH((bn_stats_kernel<T, false>), grid, dim3(BN_THREADS), 0, st, (const T*)x,
-                                (double*)workspace, (int)N, (int)C, (int)HW, P);
+    prof_note((double)elem_bytes(dtype) * (double)N * (double)C * (double)HW, 0.0);
+    dispatch_float(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        dispatch_bool(v, [&](auto VEC) {
+            OFASR_LAUNCH((bn_stats_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, st, (const T*)x, (double*)workspace, (int)N,
+                         (int)C, (int)HW, P);
+        });
     });
     return check_launch(name);
 }
@@ -828,20 +828,12 @@ static int launch_bn_apply(const char* name, const void* x, const void* residual
     dim3 grid((unsigned)C, (unsigned)P);
     hipStream_t st = as_stream(stream);
     const bool v = vec_ok(HW, dtype, x, residual, y, nullptr);
-    prof_note((dtype == OFASR_F32 ? 4.0 : 2.0) * (double)N * (double)C * (double)HW * (residual ? 3.0 : 2.0), 0.0);
-#define OFASR_BNF(VEC, ACT, RES)                                                                                   \
-    OFASR_LAUNCH((bn_act_fwd_kernel<T, VEC, ACT, RES>), grid, dim3(BN_THREADS), 0, st, (const T*)x,          \
-                       (const T*)residual, (T*)y, src, (int)N, (int)C, (int)HW, P)
-    OFASR_BN_DISPATCH_T(dtype, {
-        if (v) {
-            if (act == 1) { if (residual) OFASR_BNF(true, 1, true); else OFASR_BNF(true, 1, false); }
-            else { if (residual) OFASR_BNF(true, 0, true); else OFASR_BNF(true, 0, false); }
-        } else {
-            if (act == 1) { if (residual) OFASR_BNF(false, 1, true); else OFASR_BNF(false, 1, false); }
-            else { if (residual) OFASR_BNF(false, 0, true); else OFASR_BNF(false, 0, false); }
-        }
+    prof_note((double)elem_bytes(dtype) * (double)N * (double)C * (double)HW * (residual ? 3.0 : 2.0), 0.0);
+    bn_dispatch(dtype, v, act, residual != nullptr, [&](auto t, auto VEC, auto ACT, auto RES) {
+        using T = typename decltype(t)::type;
+        OFASR_LAUNCH((bn_act_fwd_kernel<T, VEC, ACT, RES>), grid, dim3(BN_THREADS), 0, st, (const T*)x, (const T*)residual,
+                     (T*)y, src, (int)N, (int)C, (int)HW, P);
     });
-#undef OFASR_BNF
     return check_launch(name);
 }
 
@@ -918,6 +910,20 @@ OFASR_EXPORT int ofasr_bn_finalize_cp(const void* partial, int64_t P, int64_t C,
                           stats, stats + C, stats + 2 * C, stats + 3 * C, nullptr, nullptr, nullptr, stream);
 }
 
+// the reduction pass of the BN(+ReLU6)(+residual) backward: [P][C][2] fp64 partials.  Shared by ofasr_bn_act_bwd,
+// bn_bwd_reduce_coef and bn_bwd_reduce_only (those two: residual == nullptr).
+static void launch_bn_bwd_reduce(const void* dy, const void* x, const void* residual, const float* scale, const float* shift,
+                                 const float* mean, const float* invstd, double* partial, int64_t N, int64_t C, int64_t HW,
+                                 int P, int act, int dtype, bool v, hipStream_t st) {
+    dim3 grid((unsigned)C, (unsigned)P);
+    prof_note((double)elem_bytes(dtype) * (double)N * (double)C * (double)HW * (residual ? 3.0 : 2.0), 0.0);   // reads dy, x (, residual)
+    bn_dispatch(dtype, v, act, residual != nullptr, [&](auto t, auto VEC, auto ACT, auto RES) {
+        using T = typename decltype(t)::type;
+        OFASR_LAUNCH((bn_bwd_reduce_kernel<T, VEC, ACT, RES>), grid, dim3(BN_THREADS), 0, st, (const T*)dy, (const T*)x,
+                     (const T*)residual, scale, shift, mean, invstd, partial, (int)N, (int)C, (int)HW, P);
+    });
+}
+
 OFASR_EXPORT int ofasr_bn_act_bwd(const void* dy, const void* x, const void* residual, void* dx, void* dresidual,
                                   const float* scale, const float* shift, const float* mean, const float* invstd,
                                   float* dgamma, float* dbeta, int64_t N, int64_t C, int64_t HW, int act, int training,
@@ -929,60 +935,40 @@ OFASR_EXPORT int ofasr_bn_act_bwd(const void* dy, const void* x, const void* res
     OFASR_REQUIRE(act == 0 || act == 1, OFASR_ERR_UNSUPPORTED, "%s: act %d not in {0 none, 1 relu6}", name, act);
     const int P = bn_parts(N, C);
     const size_t need = (size_t)P * C * 2 * sizeof(double);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     double* partial = (double*)workspace;
     const double M = (double)N * (double)HW;
     dim3 grid((unsigned)C, (unsigned)P);
     hipStream_t st = as_stream(stream);
-    const bool v = vec_ok(HW, dtype, dy, x, residual, dx) && ((reinterpret_cast<uintptr_t>(dresidual) & 15) == 0);
+    const bool v = vec_ok(HW, dtype, dy, x, residual, dx) && aligned16(dresidual);
     {
         // small channels: reduction and apply by one workgroup per channel from registers (bn_bwd_onepass_kernel)
         // OFF by default (OFASR_BN_BWD_ONEPASS=1): in the training step 2604-2614 against 2686-2695 images/s (two A/B pairs)
         // -- 64 workgroups of 1024 threads are a latency-bound kernel on a quarter of the CUs and cannot share them with the
         // side stream's kernels; the two 7 us passes on the whole chip are shorter
-        static const bool onepass = [] { const char* e = getenv("OFASR_BN_BWD_ONEPASS"); return e && e[0] == '1'; }();
+        static const bool onepass = env_default_off("OFASR_BN_BWD_ONEPASS");
         if (onepass && v && act == 0 && !residual && !dresidual && dtype != OFASR_F32 && HW % 8 == 0 &&
             N * (HW / 8) <= (int64_t)BN1P_THREADS * BN1P_MAXCH && C <= 65535) {
             prof_note(2.0 * (double)N * (double)C * (double)HW * 3.0, 0.0);       // reads dy, x; writes dx
-            if (dtype == OFASR_BF16)
-                OFASR_LAUNCH((bn_bwd_onepass_kernel<bf16_t>), dim3((unsigned)C), dim3(BN1P_THREADS), 0, st, (const bf16_t*)dy,
-                             (const bf16_t*)x, (bf16_t*)dx, scale, mean, invstd, dgamma, dbeta, (int)N, (int)C, (int)HW, M,
-                             training);
-            else
-                OFASR_LAUNCH((bn_bwd_onepass_kernel<f16_t>), dim3((unsigned)C), dim3(BN1P_THREADS), 0, st, (const f16_t*)dy,
-                             (const f16_t*)x, (f16_t*)dx, scale, mean, invstd, dgamma, dbeta, (int)N, (int)C, (int)HW, M,
-                             training);
+            dispatch_16bit(dtype, [&](auto t) {
+                using T = typename decltype(t)::type;
+                OFASR_LAUNCH((bn_bwd_onepass_kernel<T>), dim3((unsigned)C), dim3(BN1P_THREADS), 0, st, (const T*)dy, (const T*)x,
+                             (T*)dx, scale, mean, invstd, dgamma, dbeta, (int)N, (int)C, (int)HW, M, training);
+            });
             return check_launch(name);
         }
     }
-#define OFASR_BNR(VEC, ACT, RES)                                                                                     \
-    OFASR_LAUNCH((bn_bwd_reduce_kernel<T, VEC, ACT, RES>), grid, dim3(BN_THREADS), 0, st, (const T*)dy,        \
-                       (const T*)x, (const T*)residual, scale, shift, mean, invstd, partial, (int)N, (int)C, (int)HW, P)
-#define OFASR_BNA(VEC, ACT, RES)                                                                                     \
-    OFASR_LAUNCH((bn_bwd_apply_kernel<T, VEC, ACT, RES>), grid, dim3(BN_THREADS), 0, st, (const T*)dy,         \
-                       (const T*)x, (const T*)residual, (T*)dx, (T*)dresidual, scale, shift, mean, invstd,           \
-                       (const double*)partial, P, M, training, dgamma, dbeta, (int)N, (int)C, (int)HW, P)
-#define OFASR_BN_BOTH(MACRO)                                                                              \
-    OFASR_BN_DISPATCH_T(dtype, {                                                                          \
-        if (v) {                                                                                          \
-            if (act == 1) { if (residual) MACRO(true, 1, true); else MACRO(true, 1, false); }             \
-            else { if (residual) MACRO(true, 0, true); else MACRO(true, 0, false); }                      \
-        } else {                                                                                          \
-            if (act == 1) { if (residual) MACRO(false, 1, true); else MACRO(false, 1, false); }           \
-            else { if (residual) MACRO(false, 0, true); else MACRO(false, 0, false); }                    \
-        }                                                                                                 \
-    })
-    const double tensor_bytes = (dtype == OFASR_F32 ? 4.0 : 2.0) * (double)N * (double)C * (double)HW;
-    prof_note(tensor_bytes * (residual ? 3.0 : 2.0), 0.0);                         // reads dy, x (, residual)
-    OFASR_BN_BOTH(OFASR_BNR);
+    launch_bn_bwd_reduce(dy, x, residual, scale, shift, mean, invstd, partial, N, C, HW, P, act, dtype, v, st);
     rc = check_launch(name);
     if (rc) return rc;
+    const double tensor_bytes = (double)elem_bytes(dtype) * (double)N * (double)C * (double)HW;
     prof_note(tensor_bytes * (3.0 + (residual ? 1.0 : 0.0) + (dresidual ? 1.0 : 0.0)), 0.0);   // + writes dx (, dresidual)
-    OFASR_BN_BOTH(OFASR_BNA);
-#undef OFASR_BNR
-#undef OFASR_BNA
-#undef OFASR_BN_BOTH
+    bn_dispatch(dtype, v, act, residual != nullptr, [&](auto t, auto VEC, auto ACT, auto RES) {
+        using T = typename decltype(t)::type;
+        OFASR_LAUNCH((bn_bwd_apply_kernel<T, VEC, ACT, RES>), grid, dim3(BN_THREADS), 0, st, (const T*)dy, (const T*)x,
+                     (const T*)residual, (T*)dx, (T*)dresidual, scale, shift, mean, invstd, (const double*)partial, P, M,
+                     training, dgamma, dbeta, (int)N, (int)C, (int)HW, P);
+    });
     return check_launch(name);
 }
 
@@ -1007,22 +993,11 @@ int bn_bwd_reduce_coef(const void* dy, const void* x, const float* scale, const 
     OFASR_REQUIRE(dy && x && scale && shift && mean && invstd && ka && kbi, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     const int P = bn_parts(N, C);
     const size_t need = (size_t)P * C * 2 * sizeof(double);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     double* partial = (double*)workspace;
-    dim3 grid((unsigned)C, (unsigned)P);
     hipStream_t st = as_stream(stream);
-    const bool v = vec_ok(HW, dtype, dy, x, nullptr, nullptr);
-    const void* residual = nullptr;
-    prof_note((dtype == OFASR_F32 ? 4.0 : 2.0) * (double)N * (double)C * (double)HW * 2.0, 0.0);
-#define OFASR_BNR2(VEC, ACT)                                                                                           \
-    OFASR_LAUNCH((bn_bwd_reduce_kernel<T, VEC, ACT, false>), grid, dim3(BN_THREADS), 0, st, (const T*)dy, (const T*)x, \
-                 (const T*)residual, scale, shift, mean, invstd, partial, (int)N, (int)C, (int)HW, P)
-    OFASR_BN_DISPATCH_T(dtype, {
-        if (v) { if (act == 1) OFASR_BNR2(true, 1); else OFASR_BNR2(true, 0); }
-        else { if (act == 1) OFASR_BNR2(false, 1); else OFASR_BNR2(false, 0); }
-    });
-#undef OFASR_BNR2
+    launch_bn_bwd_reduce(dy, x, nullptr, scale, shift, mean, invstd, partial, N, C, HW, P, act, dtype,
+                         vec_ok(HW, dtype, dy, x, nullptr, nullptr), st);
     rc = check_launch(name);
     if (rc) return rc;
     OFASR_LAUNCH(bn_bwd_coef_kernel, dim3((unsigned)cdiv(C, 64)), dim3(64), 0, st, (const double*)partial, P, (int)C,
@@ -1038,22 +1013,11 @@ int bn_bwd_reduce_only(const void* dy, const void* x, const float* scale, const 
     OFASR_REQUIRE(dy && x && scale && shift && mean && invstd && P_out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     const int P = bn_parts(N, C);
     const size_t need = (size_t)P * C * 2 * sizeof(double);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     double* partial = (double*)workspace;
-    dim3 grid((unsigned)C, (unsigned)P);
     hipStream_t st = as_stream(stream);
-    const bool v = vec_ok(HW, dtype, dy, x, nullptr, nullptr);
-    const void* residual = nullptr;
-    prof_note((dtype == OFASR_F32 ? 4.0 : 2.0) * (double)N * (double)C * (double)HW * 2.0, 0.0);
-#define OFASR_BNR2(VEC, ACT)                                                                                           \
-    OFASR_LAUNCH((bn_bwd_reduce_kernel<T, VEC, ACT, false>), grid, dim3(BN_THREADS), 0, st, (const T*)dy, (const T*)x, \
-                 (const T*)residual, scale, shift, mean, invstd, partial, (int)N, (int)C, (int)HW, P)
-    OFASR_BN_DISPATCH_T(dtype, {
-        if (v) { if (act == 1) OFASR_BNR2(true, 1); else OFASR_BNR2(true, 0); }
-        else { if (act == 1) OFASR_BNR2(false, 1); else OFASR_BNR2(false, 0); }
-    });
-#undef OFASR_BNR2
+    launch_bn_bwd_reduce(dy, x, nullptr, scale, shift, mean, invstd, partial, N, C, HW, P, act, dtype,
+                         vec_ok(HW, dtype, dy, x, nullptr, nullptr), st);
     *P_out = P;
     return check_launch(name);
 }
@@ -1074,15 +1038,13 @@ OFASR_EXPORT int ofasr_bn_bwd_ps2(const void* dout, const void* x, void* dx, con
     int rc = check_bn(name, N, C, H * W, dtype);
     if (rc) return rc;
     OFASR_REQUIRE(dout && x && dx && scale && mean && invstd, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit tensors only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit tensors only");
     OFASR_REQUIRE(C % 4 == 0 && W % 8 == 0 && H <= (1 << 20) && W <= (1 << 20), OFASR_ERR_UNSUPPORTED,
                   "%s: needs C %% 4 == 0 and W %% 8 == 0", name);
-    OFASR_REQUIRE(((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0,
-                  OFASR_ERR_UNSUPPORTED, "%s: tensors must be 16-byte aligned", name);
+    OFASR_REQUIRE(aligned16(dout, x, dx), OFASR_ERR_UNSUPPORTED, "%s: tensors must be 16-byte aligned", name);
     const int P = bn_parts(N, C / 4);
     const size_t need = (size_t)P * C * 2 * sizeof(double);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     double* partial = (double*)workspace;
     const int Wq = (int)(W / 8);
     const double M = (double)N * (double)H * (double)W;
@@ -1090,23 +1052,18 @@ OFASR_EXPORT int ofasr_bn_bwd_ps2(const void* dout, const void* x, void* dx, con
     hipStream_t st = as_stream(stream);
     const double tensor_bytes = 2.0 * (double)N * (double)C * (double)H * (double)W;
     prof_note(2.0 * tensor_bytes, 0.0);
-    if (dtype == OFASR_BF16)
-        OFASR_LAUNCH((bn_bwd_reduce_ps_kernel<bf16_t>), grid, dim3(BN_THREADS), 0, st, (const uint4*)dout, (const uint4*)x, mean,
-                     invstd, partial, (int)N, (int)C, (int)H, Wq, P);
-    else
-        OFASR_LAUNCH((bn_bwd_reduce_ps_kernel<f16_t>), grid, dim3(BN_THREADS), 0, st, (const uint4*)dout, (const uint4*)x, mean,
-                     invstd, partial, (int)N, (int)C, (int)H, Wq, P);
+    dispatch_16bit(dtype, [&](auto t) {
+        OFASR_LAUNCH((bn_bwd_reduce_ps_kernel<typename decltype(t)::type>), grid, dim3(BN_THREADS), 0, st, (const uint4*)dout,
+                     (const uint4*)x, mean, invstd, partial, (int)N, (int)C, (int)H, Wq, P);
+    });
     rc = check_launch(name);
     if (rc) return rc;
     prof_note(3.0 * tensor_bytes, 0.0);
-    if (dtype == OFASR_BF16)
-        OFASR_LAUNCH((bn_bwd_apply_ps_kernel<bf16_t>), grid, dim3(BN_THREADS), 0, st, (const uint4*)dout, (const uint4*)x,
-                     (uint4*)dx, scale, mean, invstd, (const double*)partial, P, M, training, dgamma, dbeta, (int)N, (int)C,
-                     (int)H, Wq, P);
-    else
-        OFASR_LAUNCH((bn_bwd_apply_ps_kernel<f16_t>), grid, dim3(BN_THREADS), 0, st, (const uint4*)dout, (const uint4*)x,
-                     (uint4*)dx, scale, mean, invstd, (const double*)partial, P, M, training, dgamma, dbeta, (int)N, (int)C,
-                     (int)H, Wq, P);
+    dispatch_16bit(dtype, [&](auto t) {
+        OFASR_LAUNCH((bn_bwd_apply_ps_kernel<typename decltype(t)::type>), grid, dim3(BN_THREADS), 0, st, (const uint4*)dout,
+                     (const uint4*)x, (uint4*)dx, scale, mean, invstd, (const double*)partial, P, M, training, dgamma, dbeta,
+                     (int)N, (int)C, (int)H, Wq, P);
+    });
     return check_launch(name);
 }
 

@@ -378,25 +378,17 @@ static int launch_conv_run(const char* name, const void* x, const void* ws, void
     dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N, (unsigned)p.nslab);
     prof_note((double)sizeof(T) * (double)N * (double)H * (double)W * (double)(Cin + Cout),
               2.0 * (double)N * (double)H * (double)W * (double)Cin * (double)Cout * K * K);
-#define OFASR_CV(KS, RB, WM, WP, ONEK)                                                                                  \
-    OFASR_LAUNCH((conv_igemm_kernel<T, KS, RB, WM, WP, ONEK>), grid, dim3(64 * WM * WP), 0, st, (const T*)x,         \
-                       (const T*)ws, (T*)y, p.Kdim, p.M, (int)H, (int)W, tiles_x, p.nkc, p.nrb, epi)
-#define OFASR_CVK(KS, ONEK)                                                                                         \
-    switch (p.cfg) {                                                                                                \
-        case 0: OFASR_CV(KS, 2, 4, 1, ONEK); break;                                                                 \
-        case 1: OFASR_CV(KS, 2, 2, 2, ONEK); break;                                                                 \
-        case 2: OFASR_CV(KS, 2, 1, 4, ONEK); break;                                                                 \
-        case 4: OFASR_CV(KS, 1, 2, 2, ONEK); break;                                                                 \
-        default: OFASR_CV(KS, 1, 1, 4, ONEK); break;                                                                \
-    }
-    const bool onek = p.Kdim <= 16;
-    if (K == 5) {
-        if (onek) { OFASR_CVK(5, true) } else { OFASR_CVK(5, false) }
-    } else {
-        if (onek) { OFASR_CVK(3, true) } else { OFASR_CVK(3, false) }
-    }
-#undef OFASR_CVK
-#undef OFASR_CV
+    struct Cfg { int rb, wm, wp; };                                     // of CvPlan::cfg 0 .. 4
+    static constexpr Cfg CFGS[5] = {{2, 4, 1}, {2, 2, 2}, {2, 1, 4}, {1, 1, 4}, {1, 2, 2}};
+    dispatch_int<5, 3>(K, [&](auto KS) {
+        dispatch_bool(p.Kdim <= 16, [&](auto ONEK) {
+            dispatch_int<0, 1, 2, 4, 3>(p.cfg, [&](auto CFG) {
+                constexpr Cfg c = CFGS[CFG];
+                OFASR_LAUNCH((conv_igemm_kernel<T, KS, c.rb, c.wm, c.wp, ONEK>), grid, dim3(64 * c.wm * c.wp), 0, st, (const T*)x,
+                             (const T*)ws, (T*)y, p.Kdim, p.M, (int)H, (int)W, tiles_x, p.nkc, p.nrb, epi);
+            });
+        });
+    });
     return check_launch(name);
 }
 
@@ -694,29 +686,21 @@ static int launch_conv2d_wgrad(const char* name, const void* dy, const void* x, 
     const CvWgParams& P = p.P;
     dim3 grid((unsigned)(cdiv(P.ksplit, 8) * 8 * K * P.nz));
     prof_note(p.note_bytes, p.note_flops);
-#define OFASR_WG(KS, RBW, WCO, WCI, WK)                                                                              \
-    {                                                                                                                \
-        OFASR_LAUNCH((conv_wgrad_kernel<T, KS, RBW, WCO, WCI, WK>), grid, dim3(256), 0, st, (const T*)dy,      \
-                           (const T*)x, (float*)ws, P);                                                              \
-        int rc = check_launch(name);                                                                                 \
-        if (rc) return rc;                                                                                           \
-        const long long tot = (long long)KS * P.nz * (WCO * WCI) * RBW * KS * 16 * 64;                               \
-        OFASR_LAUNCH((conv_wgrad_reduce_kernel<KS, RBW, WCO, WCI>), dim3((unsigned)cdiv(tot, 256)),            \
-                           dim3(256), 0, st, (const float*)ws, dw, P, tot);                                          \
-    }
-#define OFASR_WGK(KS)                                                                                                \
-    switch (p.cfg) {                                                                                                 \
-        case 0: OFASR_WG(KS, 2, 2, 2, 1) break;                                                                      \
-        case 1: OFASR_WG(KS, 2, 1, 2, 2) break;                                                                      \
-        case 2: OFASR_WG(KS, 1, 1, 2, 2) break;                                                                      \
-        case 3: OFASR_WG(KS, 2, 2, 1, 2) break;                                                                      \
-        case 4: OFASR_WG(KS, 2, 1, 1, 4) break;                                                                      \
-        default: OFASR_WG(KS, 1, 1, 1, 4) break;                                                                     \
-    }
-    if (K == 5) { OFASR_WGK(5) } else { OFASR_WGK(3) }
-#undef OFASR_WGK
-#undef OFASR_WG
-    return check_launch(name);
+    struct Cfg { int rbw, wco, wci, wk; };                              // of CvWgPlan::cfg 0 .. 5
+    static constexpr Cfg CFGS[6] = {{2, 2, 2, 1}, {2, 1, 2, 2}, {1, 1, 2, 2}, {2, 2, 1, 2}, {2, 1, 1, 4}, {1, 1, 1, 4}};
+    return dispatch_int<5, 3>(K, [&](auto KS) {
+        return dispatch_int<0, 1, 2, 3, 4, 5>(p.cfg, [&](auto CFG) {
+            constexpr Cfg c = CFGS[CFG];
+            OFASR_LAUNCH((conv_wgrad_kernel<T, KS, c.rbw, c.wco, c.wci, c.wk>), grid, dim3(256), 0, st, (const T*)dy, (const T*)x,
+                         (float*)ws, P);
+            int rc = check_launch(name);
+            if (rc) return rc;
+            const long long tot = (long long)KS * P.nz * (c.wco * c.wci) * c.rbw * KS * 16 * 64;
+            OFASR_LAUNCH((conv_wgrad_reduce_kernel<KS, c.rbw, c.wco, c.wci>), dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, st,
+                         (const float*)ws, dw, P, tot);
+            return check_launch(name);
+        });
+    });
 }
 
 static int conv_stat_units(int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int K) {
@@ -734,15 +718,12 @@ static int conv2d_entry(const char* name, const void* x, const float* w, void* y
                         StatOut so = StatOut{nullptr, 0}) {
     OFASR_REQUIRE(x && w && y, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, OFASR_ERR_INVALID_ARG, "%s: bad shape", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED,
-                  "%s: 16-bit activations only (fp32 runs on the vendor library)", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit activations only (fp32 runs on the vendor library)");
     OFASR_REQUIRE(K == 3 || K == 5, OFASR_ERR_UNSUPPORTED, "%s: K=%d not in {3,5}", name, K);
-    OFASR_REQUIRE(W % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
-                  OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
+    OFASR_REQUIRE(W % 8 == 0 && aligned16(x, y), OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
     OFASR_REQUIRE(N <= 65535 && H * W <= (1LL << 31), OFASR_ERR_UNSUPPORTED, "%s: too large", name);
     const CvPlan p = cv_plan(Cin, Cout, K, dgrad);
-    OFASR_REQUIRE(ws && ws_bytes >= p.img_bytes, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  ws_bytes, p.img_bytes);
+    OFASR_REQUIRE_WORKSPACE(ws, ws_bytes, p.img_bytes);
     hipStream_t st = as_stream(stream);
     {
         // a 3-channel result (the head's forward, the stem's input gradient): csrc/conv_thin.hip
@@ -764,8 +745,9 @@ static int conv2d_entry(const char* name, const void* x, const float* w, void* y
     if (so.partial)
         OFASR_REQUIRE(!dgrad && so.P == conv_stat_units(N, Cin, Cout, H, W, K), OFASR_ERR_INVALID_ARG,
                       "%s: statistics unit count %d does not match the launch", name, so.P);
-    if (dtype == OFASR_BF16) return launch_conv2d<bf16_t>(name, x, w, y, N, Cin, Cout, H, W, K, dgrad, ws, st, so);
-    return launch_conv2d<f16_t>(name, x, w, y, N, Cin, Cout, H, W, K, dgrad, ws, st, so);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_conv2d<typename decltype(t)::type>(name, x, w, y, N, Cin, Cout, H, W, K, dgrad, ws, st, so);
+    });
 }
 
 }  // namespace ofasr
@@ -784,7 +766,7 @@ OFASR_EXPORT int ofasr_conv2d_fwd(const void* x, const float* w, void* y, int64_
 
 // ---- inference: conv + eval-mode BN (+ ReLU6 | PixelShuffle(2)) as one kernel, operands prepared once per set of weights
 static size_t cv_infer_bytes(int64_t Cin, int64_t Cout, int K) {
-    return (cv_plan(Cin, Cout, K, 0).img_bytes + 255) / 256 * 256 + (size_t)(2 * Cout) * sizeof(float);
+    return align_up(cv_plan(Cin, Cout, K, 0).img_bytes, 256) + (size_t)(2 * Cout) * sizeof(float);
 }
 OFASR_EXPORT size_t ofasr_conv2d_infer_operand_bytes(int64_t Cin, int64_t Cout, int K) {
     if (Cin <= 0 || Cout <= 0 || !(K == 3 || K == 5)) return 0;
@@ -797,16 +779,17 @@ OFASR_EXPORT int ofasr_conv2d_infer_prepare(const float* w, const float* gamma, 
     const char* name = "ofasr_conv2d_infer_prepare";
     OFASR_REQUIRE(w && operands, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(Cin > 0 && Cout > 0, OFASR_ERR_INVALID_ARG, "%s: bad shape", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit activations only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit activations only");
     OFASR_REQUIRE(K == 3 || K == 5, OFASR_ERR_UNSUPPORTED, "%s: K=%d not in {3,5}", name, K);
     OFASR_REQUIRE(gamma == nullptr || (beta && running_mean && running_var), OFASR_ERR_INVALID_ARG, "%s: incomplete BN", name);
     OFASR_REQUIRE(operand_bytes >= cv_infer_bytes(Cin, Cout, K), OFASR_ERR_WORKSPACE, "%s: operand buffer %zu B < required %zu B",
                   name, operand_bytes, cv_infer_bytes(Cin, Cout, K));
-    float* ss = reinterpret_cast<float*>((char*)operands + (cv_plan(Cin, Cout, K, 0).img_bytes + 255) / 256 * 256);
+    float* ss = reinterpret_cast<float*>((char*)operands + align_up(cv_plan(Cin, Cout, K, 0).img_bytes, 256));
     const CvBn bn{ss, gamma, beta, running_mean, running_var, (float)eps};
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_BF16) return launch_conv_prep<bf16_t>(name, w, Cin, Cout, K, 0, operands, bn, st);
-    return launch_conv_prep<f16_t>(name, w, Cin, Cout, K, 0, operands, bn, st);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_conv_prep<typename decltype(t)::type>(name, w, Cin, Cout, K, 0, operands, bn, st);
+    });
 }
 
 OFASR_EXPORT int ofasr_conv2d_infer_run(const void* x, void* y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W,
@@ -814,19 +797,20 @@ OFASR_EXPORT int ofasr_conv2d_infer_run(const void* x, void* y, int64_t N, int64
     const char* name = "ofasr_conv2d_infer_run";
     OFASR_REQUIRE(x && y && operands, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, OFASR_ERR_INVALID_ARG, "%s: bad shape", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit activations only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit activations only");
     OFASR_REQUIRE(K == 3 || K == 5, OFASR_ERR_UNSUPPORTED, "%s: K=%d not in {3,5}", name, K);
     OFASR_REQUIRE(act >= 0 && act <= 2, OFASR_ERR_INVALID_ARG, "%s: act %d not in {0 none, 1 relu6, 2 pixel shuffle}", name, act);
     OFASR_REQUIRE(act != 2 || Cout % 4 == 0, OFASR_ERR_INVALID_ARG, "%s: PixelShuffle(2) needs Cout %% 4 == 0", name);
-    OFASR_REQUIRE(W % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
-                  OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
+    OFASR_REQUIRE(W % 8 == 0 && aligned16(x, y), OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
     OFASR_REQUIRE(N <= 65535 && H * W <= (1LL << 29), OFASR_ERR_UNSUPPORTED, "%s: too large", name);
     OFASR_REQUIRE(operand_bytes >= cv_infer_bytes(Cin, Cout, K), OFASR_ERR_WORKSPACE, "%s: operand buffer %zu B < required %zu B",
                   name, operand_bytes, cv_infer_bytes(Cin, Cout, K));
-    const float* ss = reinterpret_cast<const float*>((const char*)operands + (cv_plan(Cin, Cout, K, 0).img_bytes + 255) / 256 * 256);
+    const float* ss = reinterpret_cast<const float*>((const char*)operands + align_up(cv_plan(Cin, Cout, K, 0).img_bytes, 256));
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_BF16) return launch_conv_run<bf16_t>(name, x, operands, y, N, Cin, Cout, H, W, K, 0, CvEpi{ss, act, nullptr, 0}, st);
-    return launch_conv_run<f16_t>(name, x, operands, y, N, Cin, Cout, H, W, K, 0, CvEpi{ss, act, nullptr, 0}, st);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_conv_run<typename decltype(t)::type>(name, x, operands, y, N, Cin, Cout, H, W, K, 0,
+                                                           CvEpi{ss, act, nullptr, 0}, st);
+    });
 }
 
 // forward that also leaves the BatchNorm statistics partials of its output: partial[Cout][units] (sum, sum of squares),
@@ -869,11 +853,9 @@ OFASR_EXPORT int ofasr_conv2d_wgrad(const void* dy, const void* x, float* dw, in
     const char* name = "ofasr_conv2d_wgrad";
     OFASR_REQUIRE(dy && x && dw, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, OFASR_ERR_INVALID_ARG, "%s: bad shape", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED,
-                  "%s: 16-bit activations only (fp32 runs on the vendor library)", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit activations only (fp32 runs on the vendor library)");
     OFASR_REQUIRE(K == 3 || K == 5, OFASR_ERR_UNSUPPORTED, "%s: K=%d not in {3,5}", name, K);
-    OFASR_REQUIRE(W % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0,
-                  OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
+    OFASR_REQUIRE(W % 8 == 0 && aligned16(x, dy), OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
     OFASR_REQUIRE(N * H * W <= (1LL << 30), OFASR_ERR_UNSUPPORTED, "%s: too large", name);
     {
         const int64_t Ct = Cin < Cout ? Cin : Cout, Cw = Cin < Cout ? Cout : Cin;
@@ -881,9 +863,9 @@ OFASR_EXPORT int ofasr_conv2d_wgrad(const void* dy, const void* x, float* dw, in
             return conv_thin_wgrad(dy, x, dw, N, Cin, Cout, H, W, K, dtype, workspace, workspace_bytes, stream);
     }
     const CvWgPlan p = cv_wg_plan(N, Cin, Cout, H, W, K);
-    OFASR_REQUIRE(workspace && workspace_bytes >= p.part_bytes, OFASR_ERR_WORKSPACE,
-                  "%s: workspace %zu B < required %zu B", name, workspace_bytes, p.part_bytes);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, p.part_bytes);
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_BF16) return launch_conv2d_wgrad<bf16_t>(name, dy, x, dw, K, p, workspace, st);
-    return launch_conv2d_wgrad<f16_t>(name, dy, x, dw, K, p, workspace, st);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_conv2d_wgrad<typename decltype(t)::type>(name, dy, x, dw, K, p, workspace, st);
+    });
 }

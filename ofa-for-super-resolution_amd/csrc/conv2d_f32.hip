@@ -414,7 +414,7 @@ static int cf_nsplit(int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W)
     const int64_t groups = cdiv(Cout, 32 * CF_WG_RB) * cdiv(Cin, 32);
     // one block per CU, one round: each block pays its prologue (first tile's staging, exposed) and its partial slab
     // once (512 blocks: -1 %, 1024: -4 % on 64 -> 256 @128, -13 % @64)
-    static const int blocks = [] { const char* e = getenv("OFASR_CONV_F32_WG_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+    static const int blocks = env_positive_int("OFASR_CONV_F32_WG_BLOCKS", 256);
     int64_t want = blocks / (groups > 0 ? groups : 1);
     if (want > ntiles) want = ntiles;
     if (want < 1) want = 1;
@@ -438,7 +438,7 @@ static int conv2d_f32_entry(const char* name, const void* x, const float* w, voi
     OFASR_REQUIRE(K == 3 || K == 5, OFASR_ERR_UNSUPPORTED, "%s: K=%d not in {3,5}", name, K);
     OFASR_REQUIRE(N <= 65535 && H * W <= (1LL << 31), OFASR_ERR_UNSUPPORTED, "%s: too large", name);
     const size_t need = ofasr_conv2d_f32_workspace(Cin, Cout, K, dgrad);
-    OFASR_REQUIRE(ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, OFASR_ERR_WORKSPACE,
+    OFASR_REQUIRE(ws && ws_bytes >= need && aligned16(ws), OFASR_ERR_WORKSPACE,
                   "%s: workspace %zu B < required %zu B (or not 16-byte aligned)", name, ws_bytes, need);
     {
         // a 3-channel result (the head's forward, the stem's input gradient): csrc/conv_thin.hip
@@ -460,12 +460,10 @@ static int conv2d_f32_entry(const char* name, const void* x, const float* w, voi
     dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N, (unsigned)(Mpad / CF_MB));
     prof_note(4.0 * (double)N * (double)H * (double)W * (double)(Cin + Cout),
               2.0 * (double)N * (double)H * (double)W * (double)Cin * (double)Cout * K * K);
-    if (K == 5)
-        OFASR_LAUNCH(conv_f32_kernel<5>, grid, dim3(256), 0, st, (const float*)x, (const float*)ws, (float*)y, Kdim, M, Mpad,
+    dispatch_int<5, 3>(K, [&](auto KS) {
+        OFASR_LAUNCH(conv_f32_kernel<KS>, grid, dim3(256), 0, st, (const float*)x, (const float*)ws, (float*)y, Kdim, M, Mpad,
                      (int)H, (int)W, tiles_x, nkc);
-    else
-        OFASR_LAUNCH(conv_f32_kernel<3>, grid, dim3(256), 0, st, (const float*)x, (const float*)ws, (float*)y, Kdim, M, Mpad,
-                     (int)H, (int)W, tiles_x, nkc);
+    });
     return check_launch(name);
 }
 
@@ -498,8 +496,7 @@ OFASR_EXPORT int ofasr_conv2d_f32_wgrad(const void* dy, const void* x, float* dw
     OFASR_REQUIRE(K == 3 || K == 5, OFASR_ERR_UNSUPPORTED, "%s: K=%d not in {3,5}", name, K);
     OFASR_REQUIRE(N * H * W <= (1LL << 30), OFASR_ERR_UNSUPPORTED, "%s: too large", name);
     const size_t need = ofasr_conv2d_f32_wgrad_workspace(N, Cin, Cout, H, W, K);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     {
         const int64_t Ct = Cin < Cout ? Cin : Cout, Cw = Cin < Cout ? Cout : Cin;
         if (conv_thin_wgrad_supported(Ct, Cw, K, H, W, OFASR_F32, dy, x))

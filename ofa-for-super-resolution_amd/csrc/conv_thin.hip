@@ -865,10 +865,7 @@ template <typename T> static CtGeom ct_geom(int64_t N, int64_t Ct, int64_t Cw, i
 }
 
 bool conv_thin_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("OFASR_CONV_THIN");   // A/B switch: 0 keeps the 3-channel convs on the implicit-GEMM kernels
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_default_on("OFASR_CONV_THIN");   // A/B switch: 0 keeps the 3-channel convs on the implicit-GEMM kernels
     return on;
 }
 
@@ -883,13 +880,12 @@ template <typename T> static CtGeom ct_geom_in(int64_t N, int64_t Ct, int64_t Cw
 
 bool conv_thin_in_supported(int64_t Ct, int64_t Cw, int K, int64_t W, int dtype, const void* x, const void* y) {
     if (!conv_thin_enabled() || !(K == 3 || K == 5) || Ct * K > 16 || Ct > 4 || !(Cw == 32 || Cw == 64)) return false;
-    const int epc = dtype == OFASR_F32 ? 4 : 8;
-    if (W % epc != 0) return false;
-    return ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+    const int epc = 16 / (int)elem_bytes(dtype);
+    return W % epc == 0 && aligned16(x, y);
 }
 
 int conv_thin_in_units(int64_t N, int64_t Ct, int64_t Cw, int64_t H, int64_t W, int dtype) {
-    const CtGeom g = dtype == OFASR_F32 ? ct_geom_in<float>(N, Ct, Cw, H, W) : ct_geom_in<bf16_t>(N, Ct, Cw, H, W);
+    const CtGeom g = dispatch_float(dtype, [&](auto t) { return ct_geom_in<typename decltype(t)::type>(N, Ct, Cw, H, W); });
     return g.N * g.segs * g.strips;
 }
 
@@ -912,24 +908,15 @@ int conv_thin_in(const void* x, const float* w, void* y, int64_t N, int64_t Ct, 
                  int dtype, int dgrad, StatOut so, void* stream) {
     hipStream_t st = as_stream(stream);
     CtW Wt{w, dgrad ? (int)(Cw * K * K) : K * K, dgrad ? K * K : (int)(Ct * K * K), dgrad ? 1 : 0};
-    const double es = dtype == OFASR_F32 ? 4.0 : 2.0;
+    const double es = (double)elem_bytes(dtype);
     prof_note(es * (double)N * (double)H * (double)W * (double)(Ct + Cw), 2.0 * (double)N * (double)H * (double)W * (double)Ct * (double)Cw * K * K);
-#define OFASR_CTI(TT, KK, NMM)                                            \
-    {                                                                     \
-        const CtGeom g = ct_geom_in<TT>(N, Ct, Cw, H, W);                 \
-        ct_in_launch<TT, KK, NMM>(x, Wt, y, g, so, st);                   \
-    }
-#define OFASR_CTI_T(TT)                                                   \
-    if (K == 5) {                                                         \
-        if (Cw == 64) OFASR_CTI(TT, 5, 4) else OFASR_CTI(TT, 5, 2)        \
-    } else {                                                              \
-        if (Cw == 64) OFASR_CTI(TT, 3, 4) else OFASR_CTI(TT, 3, 2)        \
-    }
-    if (dtype == OFASR_BF16) { OFASR_CTI_T(bf16_t) }
-    else if (dtype == OFASR_F16) { OFASR_CTI_T(f16_t) }
-    else { OFASR_CTI_T(float) }
-#undef OFASR_CTI_T
-#undef OFASR_CTI
+    dispatch_float(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const CtGeom g = ct_geom_in<T>(N, Ct, Cw, H, W);
+        dispatch_int<5, 3>(K, [&](auto KK) {
+            dispatch_int<64, 32>((int)Cw, [&](auto CW) { ct_in_launch<T, KK, CW / 16>(x, Wt, y, g, so, st); });
+        });
+    });
     return check_launch("conv_thin_in");
 }
 
@@ -954,11 +941,11 @@ bool conv_thin_wgrad_supported(int64_t Ct, int64_t Cw, int K, int64_t H, int64_t
     if (!conv_thin_enabled() || !(K == 3 || K == 5) || Ct * K > 16 || Ct > 4 || !(Cw == 32 || Cw == 64)) return false;
     // a lane's wide fragment is 8 consecutive pixels of a row in either dtype: they must be all inside or all outside it
     if (W % 8 != 0 || W > 1024) return false;
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+    return aligned16(a, b);
 }
 
 size_t conv_thin_wgrad_workspace(int64_t N, int64_t Ct, int64_t Cw, int64_t H, int64_t W, int K, int dtype) {
-    const CtWgGeom g = ct_wg_geom(N, Ct, Cw, H, W, dtype == OFASR_F32 ? 4 : 2);
+    const CtWgGeom g = ct_wg_geom(N, Ct, Cw, H, W, (int)elem_bytes(dtype));
     return (size_t)g.N * g.segs * K * (Cw / 16) * 256 * sizeof(float);
 }
 
@@ -988,42 +975,34 @@ int conv_thin_wgrad(const void* dy, const void* x, float* dw, int64_t N, int64_t
     OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "conv_thin_wgrad: workspace %zu B < required %zu B",
                   workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    const CtWgGeom g = ct_wg_geom(N, Ct, Cw, H, W, dtype == OFASR_F32 ? 4 : 2);
-    const double es = dtype == OFASR_F32 ? 4.0 : 2.0;
+    const CtWgGeom g = ct_wg_geom(N, Ct, Cw, H, W, (int)elem_bytes(dtype));
+    const double es = (double)elem_bytes(dtype);
     prof_note(es * (double)N * (double)H * (double)W * (double)(Ct + Cw), 2.0 * (double)N * (double)H * (double)W * (double)Ct * (double)Cw * K * K);
-#define OFASR_CTW(TT, KK, NTT) ct_wg_launch<TT, KK, NTT>(thin, wide, (float*)workspace, g, st);
-#define OFASR_CTW_T(TT)                                                   \
-    if (K == 5) {                                                         \
-        if (Cw == 64) OFASR_CTW(TT, 5, 4) else OFASR_CTW(TT, 5, 2)        \
-    } else {                                                              \
-        if (Cw == 64) OFASR_CTW(TT, 3, 4) else OFASR_CTW(TT, 3, 2)        \
-    }
-    if (dtype == OFASR_BF16) { OFASR_CTW_T(bf16_t) }
-    else if (dtype == OFASR_F16) { OFASR_CTW_T(f16_t) }
-    else { OFASR_CTW_T(float) }
-#undef OFASR_CTW_T
-#undef OFASR_CTW
+    dispatch_float(dtype, [&](auto t) {
+        dispatch_int<5, 3>(K, [&](auto KK) {
+            dispatch_int<64, 32>((int)Cw, [&](auto CW) {
+                ct_wg_launch<typename decltype(t)::type, KK, CW / 16>(thin, wide, (float*)workspace, g, st);
+            });
+        });
+    });
     int rc = check_launch("conv_thin_wgrad");
     if (rc) return rc;
     const unsigned rblocks = (unsigned)(K * (Cw / 16) * 256 / 16);
-    if (K == 5)
-        OFASR_LAUNCH(ct_wg_reduce_kernel<5>, dim3(rblocks), dim3(256), 0, st, (const float*)workspace, dw, g.N * g.segs, (int)Ct,
+    dispatch_int<5, 3>(K, [&](auto KK) {
+        OFASR_LAUNCH(ct_wg_reduce_kernel<KK>, dim3(rblocks), dim3(256), 0, st, (const float*)workspace, dw, g.N * g.segs, (int)Ct,
                      (int)Cw, (int)(Cw / 16), role);
-    else
-        OFASR_LAUNCH(ct_wg_reduce_kernel<3>, dim3(rblocks), dim3(256), 0, st, (const float*)workspace, dw, g.N * g.segs, (int)Ct,
-                     (int)Cw, (int)(Cw / 16), role);
+    });
     return check_launch("conv_thin_wgrad_reduce");
 }
 
 bool conv_thin_out_supported(int64_t Ct, int64_t Cw, int K, int64_t W, int dtype, const void* x, const void* y) {
     if (!conv_thin_enabled() || !(K == 3 || K == 5) || Ct * K > 16 || Ct > 4 || !(Cw == 32 || Cw == 64)) return false;
-    const int epc = dtype == OFASR_F32 ? 4 : 8;
-    if (W % epc != 0) return false;
-    return ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+    const int epc = 16 / (int)elem_bytes(dtype);
+    return W % epc == 0 && aligned16(x, y);
 }
 
 int conv_thin_out_units(int64_t N, int64_t Ct, int64_t Cw, int64_t H, int64_t W, int dtype) {
-    const CtGeom g = dtype == OFASR_F32 ? ct_geom<float>(N, Ct, Cw, H, W) : ct_geom<bf16_t>(N, Ct, Cw, H, W);
+    const CtGeom g = dispatch_float(dtype, [&](auto t) { return ct_geom<typename decltype(t)::type>(N, Ct, Cw, H, W); });
     return g.N * g.segs * g.strips;
 }
 
@@ -1046,24 +1025,15 @@ int conv_thin_out(const void* x, const float* w, void* y, int64_t N, int64_t Ct,
                   int dtype, int dgrad, StatOut so, void* stream) {
     hipStream_t st = as_stream(stream);
     CtW Wt{w, dgrad ? K * K : (int)(Cw * K * K), dgrad ? (int)(Ct * K * K) : K * K, dgrad ? 1 : 0};
-    const double es = dtype == OFASR_F32 ? 4.0 : 2.0;
+    const double es = (double)elem_bytes(dtype);
     prof_note(es * (double)N * (double)H * (double)W * (double)(Ct + Cw), 2.0 * (double)N * (double)H * (double)W * (double)Ct * (double)Cw * K * K);
-#define OFASR_CTO(TT, KK, NCC)                                            \
-    {                                                                     \
-        const CtGeom g = ct_geom<TT>(N, Ct, Cw, H, W);                    \
-        ct_out_launch<TT, KK, NCC>(x, Wt, y, g, so, st);                  \
-    }
-#define OFASR_CTO_T(TT)                                                   \
-    if (K == 5) {                                                         \
-        if (Cw == 64) OFASR_CTO(TT, 5, 2) else OFASR_CTO(TT, 5, 1)        \
-    } else {                                                              \
-        if (Cw == 64) OFASR_CTO(TT, 3, 2) else OFASR_CTO(TT, 3, 1)        \
-    }
-    if (dtype == OFASR_BF16) { OFASR_CTO_T(bf16_t) }
-    else if (dtype == OFASR_F16) { OFASR_CTO_T(f16_t) }
-    else { OFASR_CTO_T(float) }
-#undef OFASR_CTO_T
-#undef OFASR_CTO
+    dispatch_float(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const CtGeom g = ct_geom<T>(N, Ct, Cw, H, W);
+        dispatch_int<5, 3>(K, [&](auto KK) {
+            dispatch_int<64, 32>((int)Cw, [&](auto CW) { ct_out_launch<T, KK, CW / 32>(x, Wt, y, g, so, st); });
+        });
+    });
     return check_launch("conv_thin_out");
 }
 

@@ -27,11 +27,6 @@
 
 namespace ofasr {
 
-template <typename T> struct d4_vec4;
-template <> struct d4_vec4<float> { typedef float4 type; };
-template <> struct d4_vec4<bf16_t> { typedef uint2 type; };
-template <> struct d4_vec4<f16_t> { typedef uint2 type; };
-
 template <typename T> __device__ __forceinline__ uint32_t d4_bits(T v) { return (uint32_t)v.v; }
 template <> __device__ __forceinline__ uint32_t d4_bits<float>(float v) { return __float_as_uint(v); }
 template <typename T> __device__ __forceinline__ T d4_from_bits(uint32_t b) {
@@ -61,7 +56,7 @@ template <typename T, bool ACC, bool VEC>
 __global__ void __launch_bounds__(256) d4_flip_kernel(const T* __restrict__ src, void* __restrict__ dstv, long long planes,
                                                       int Hd, int Wd, int fx, int fy, int first, float scale) {
     typedef typename std::conditional<ACC, float, T>::type D;
-    typedef typename d4_vec4<T>::type SV;
+    typedef typename vec4<T>::type SV;
     D* dst = reinterpret_cast<D*>(dstv);
     const unsigned gw = ((unsigned)Wd + 3u) >> 2;
     const unsigned per = (unsigned)Hd * gw;
@@ -223,20 +218,18 @@ static void d4_launch(const void* src, void* dst, int64_t planes, int64_t Hd, in
     const size_t sal = 4 * sizeof(T), dal = ACC ? 16 : 4 * sizeof(T);
     const bool vec = Wd % 4 == 0 && reinterpret_cast<uintptr_t>(src) % sal == 0 && reinterpret_cast<uintptr_t>(dst) % dal == 0;
     const dim3 grid(d4_cap(cdiv(Hd * cdiv(Wd, 4), 256), 4096), gy);
-    if (vec)
-        OFASR_LAUNCH((d4_flip_kernel<T, ACC, true>), grid, dim3(256), 0, st, (const T*)src, dst, (long long)planes, (int)Hd,
+    dispatch_bool(vec, [&](auto VEC) {
+        OFASR_LAUNCH((d4_flip_kernel<T, ACC, VEC>), grid, dim3(256), 0, st, (const T*)src, dst, (long long)planes, (int)Hd,
                      (int)Wd, fx, fy, first, scale);
-    else
-        OFASR_LAUNCH((d4_flip_kernel<T, ACC, false>), grid, dim3(256), 0, st, (const T*)src, dst, (long long)planes, (int)Hd,
-                     (int)Wd, fx, fy, first, scale);
+    });
 }
 
 template <bool ACC>
 static void d4_dispatch(const void* src, void* dst, int64_t planes, int64_t Hd, int64_t Wd, int tr, int fx, int fy, int first,
                         float scale, int dtype, hipStream_t st) {
-    if (dtype == OFASR_F32) d4_launch<float, ACC>(src, dst, planes, Hd, Wd, tr, fx, fy, first, scale, st);
-    else if (dtype == OFASR_BF16) d4_launch<bf16_t, ACC>(src, dst, planes, Hd, Wd, tr, fx, fy, first, scale, st);
-    else d4_launch<f16_t, ACC>(src, dst, planes, Hd, Wd, tr, fx, fy, first, scale, st);
+    dispatch_float(dtype, [&](auto t) {
+        d4_launch<typename decltype(t)::type, ACC>(src, dst, planes, Hd, Wd, tr, fx, fy, first, scale, st);
+    });
 }
 
 static int d4_check(const char* name, const void* src, const void* dst, int64_t N, int64_t C, int64_t H, int64_t W, int t,
@@ -245,8 +238,7 @@ static int d4_check(const char* name, const void* src, const void* dst, int64_t 
     OFASR_REQUIRE(src != dst, OFASR_ERR_INVALID_ARG, "%s: source and destination are the same buffer", name);
     OFASR_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
     OFASR_REQUIRE(t >= 0 && t < 8, OFASR_ERR_INVALID_ARG, "%s: transform %d outside 0..7", name, t);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG, "%s: bad dtype",
-                  name);
+    OFASR_REQUIRE_DTYPE(dtype);
     // 32-bit walk inside a plane (the rounded-up extents included), 64-bit across planes
     OFASR_REQUIRE(H < (1LL << 30) && W < (1LL << 30) && (H + 64) * (W + 64) < (1LL << 31), OFASR_ERR_UNSUPPORTED,
                   "%s: a %lldx%lld plane is too large", name, (long long)H, (long long)W);

@@ -513,8 +513,7 @@ __global__ void __launch_bounds__(64 * DW_WAVES) dw_mfma_kernel(const T* __restr
 }
 
 static bool mfma_geom_ok(int64_t H, int64_t W, int K, const void* a, const void* b) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
-    return K >= 5 && (W == 32 || W == 64) && H >= 32 && H <= 64 && (H % 32) == 0 && (bits & 15) == 0;
+    return K >= 5 && (W == 32 || W == 64) && H >= 32 && H <= 64 && (H % 32) == 0 && aligned16(a, b);
 }
 
 struct VecGeom {
@@ -782,8 +781,7 @@ __global__ void __launch_bounds__(256) dw_wgrad_vec_reduce_kernel(const float* _
 
 // PXL = pixels per lane the kernel for (dtype, K) uses; ok = the vector path applies
 static bool vec_geom(int64_t H, int64_t W, int esize, int PXL, const void* a, const void* b, VecGeom& vg) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
-    if (H <= 0 || W <= 0 || W % PXL != 0 || W / PXL > 64 || (bits & 15) != 0) return false;
+    if (H <= 0 || W <= 0 || W % PXL != 0 || W / PXL > 64 || !aligned16(a, b)) return false;
     (void)esize;
     vg.G = (int)(W / PXL);
     vg.gpw = 64 / vg.G;
@@ -828,38 +826,27 @@ static int launch_conv(const char* name, const void* x, const float* f, void* y,
                 return OFASR_ERR_INVALID_ARG;
             }
             const long long units = (long long)C * cdiv(N, DWM_NPW);
-            if (K == 5)
-                OFASR_LAUNCH((dw_mfma_kernel<T, 5, FLIP, XF, STAT, BX>), dim3((unsigned)cdiv(units, DW_WAVES)),
-                                   dim3(64 * DW_WAVES), 0, st, (const T*)x, f, (T*)y, (int)N, (int)C, (int)H, (int)W, nslabs,
-                                   xf, so, fold, bx);
-            else
-                OFASR_LAUNCH((dw_mfma_kernel<T, 7, FLIP, XF, STAT, BX>), dim3((unsigned)cdiv(units, DW_WAVES)),
-                                   dim3(64 * DW_WAVES), 0, st, (const T*)x, f, (T*)y, (int)N, (int)C, (int)H, (int)W, nslabs,
-                                   xf, so, fold, bx);
+            dispatch_int<5, 7>(K, [&](auto KK) {
+                OFASR_LAUNCH((dw_mfma_kernel<T, KK, FLIP, XF, STAT, BX>), dim3((unsigned)cdiv(units, DW_WAVES)),
+                             dim3(64 * DW_WAVES), 0, st, (const T*)x, f, (T*)y, (int)N, (int)C, (int)H, (int)W, nslabs, xf, so,
+                             fold, bx);
+            });
             return check_launch(name);
         }
     }
-    {
-        VecGeom vg;
-#define OFASR_DWV(KK)                                                                                               \
-    if (vec_geom(H, W, (int)sizeof(T), VecPx<T, KK>::N, x, y, vg)) {                                               \
-        const long long nwaves = (long long)N * C * vg.nslabs;                                                     \
-        if (STAT && so.P != (int)(N * vg.nslabs)) {                                                                \
-            set_error("%s: statistics slab count %d != %lld", name, so.P, (long long)(N * vg.nslabs));             \
-            return OFASR_ERR_INVALID_ARG;                                                                          \
-        }                                                                                                          \
-        OFASR_LAUNCH((dw_vec_kernel<T, KK, FLIP, XF, STAT, BX>), dim3((unsigned)cdiv(nwaves, DW_WAVES)),     \
-                           dim3(64 * DW_WAVES), 0, st, (const T*)x, f, (T*)y, (int)C, (int)H, (int)W, vg, nwaves,  \
-                           xf, so, fold, bx);                                                                      \
-        return check_launch(name);                                                                                 \
-    }
-        switch (K) {
-            case 1: OFASR_DWV(1) break;
-            case 3: OFASR_DWV(3) break;
-            case 5: OFASR_DWV(5) break;
-            default: OFASR_DWV(7) break;
+    VecGeom vg;
+    const int pxl = dispatch_int<1, 3, 5, 7>(K, [](auto KK) { return (int)VecPx<T, KK>::N; });
+    if (vec_geom(H, W, (int)sizeof(T), pxl, x, y, vg)) {
+        const long long nwaves = (long long)N * C * vg.nslabs;
+        if (STAT && so.P != (int)(N * vg.nslabs)) {
+            set_error("%s: statistics slab count %d != %lld", name, so.P, (long long)(N * vg.nslabs));
+            return OFASR_ERR_INVALID_ARG;
         }
-#undef OFASR_DWV
+        dispatch_int<1, 3, 5, 7>(K, [&](auto KK) {
+            OFASR_LAUNCH((dw_vec_kernel<T, KK, FLIP, XF, STAT, BX>), dim3((unsigned)cdiv(nwaves, DW_WAVES)), dim3(64 * DW_WAVES),
+                         0, st, (const T*)x, f, (T*)y, (int)C, (int)H, (int)W, vg, nwaves, xf, so, fold, bx);
+        });
+        return check_launch(name);
     }
     if constexpr (XF || BX) {
         set_error("%s: fused input transform needs the vector kernel", name);
@@ -867,21 +854,12 @@ static int launch_conv(const char* name, const void* x, const float* f, void* y,
     }
     const int rows_per_chunk = H <= 32 ? (int)H : 32;
     const int nchunks = (int)cdiv(H, rows_per_chunk);
-#define OFASR_DW_LAUNCH(KK)                                                                                  \
-    {                                                                                                        \
-        const int nstrips = Strips<KK>::count((int)W);                                                       \
-        const long long units = (long long)N * C * nstrips * nchunks;                                        \
-        OFASR_LAUNCH((dw_strip_kernel<T, KK, FLIP>), dim3((unsigned)cdiv(units, DW_WAVES)),            \
-                           dim3(64 * DW_WAVES), 0, st, (const T*)x, f, (T*)y, (int)C, (int)H, (int)W, nstrips, \
-                           nchunks, rows_per_chunk, units);                                                  \
-    }
-    switch (K) {
-        case 1: OFASR_DW_LAUNCH(1); break;
-        case 3: OFASR_DW_LAUNCH(3); break;
-        case 5: OFASR_DW_LAUNCH(5); break;
-        default: OFASR_DW_LAUNCH(7); break;
-    }
-#undef OFASR_DW_LAUNCH
+    dispatch_int<1, 3, 5, 7>(K, [&](auto KK) {
+        const int nstrips = Strips<KK>::count((int)W);
+        const long long units = (long long)N * C * nstrips * nchunks;
+        OFASR_LAUNCH((dw_strip_kernel<T, KK, FLIP>), dim3((unsigned)cdiv(units, DW_WAVES)), dim3(64 * DW_WAVES), 0, st,
+                     (const T*)x, f, (T*)y, (int)C, (int)H, (int)W, nstrips, nchunks, rows_per_chunk, units);
+    });
     return check_launch(name);
 }
 
@@ -890,8 +868,7 @@ static int check_conv_args(const char* name, const void* a, const void* b, const
     OFASR_REQUIRE(a && b && c, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0, OFASR_ERR_INVALID_ARG, "%s: negative size", name);
     OFASR_REQUIRE(K == 1 || K == 3 || K == 5 || K == 7, OFASR_ERR_UNSUPPORTED, "%s: K=%d not in {1,3,5,7}", name, K);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG,
-                  "%s: bad dtype %d", name, dtype);
+    OFASR_REQUIRE(is_float_dtype(dtype), OFASR_ERR_INVALID_ARG, "%s: bad dtype %d", name, dtype);
     OFASR_REQUIRE(C <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX && N <= INT32_MAX, OFASR_ERR_UNSUPPORTED,
                   "%s: dimension too large", name);
     return OFASR_OK;
@@ -904,11 +881,9 @@ static int conv_entry(const char* name, const void* x, const float* f, void* y, 
     if (rc) return rc;
     if (N * C * H * W == 0) return OFASR_OK;
     hipStream_t st = as_stream(stream);
-    switch (dtype) {
-        case OFASR_F32: return launch_conv<float, FLIP>(name, x, f, y, N, C, H, W, K, st);
-        case OFASR_F16: return launch_conv<f16_t, FLIP>(name, x, f, y, N, C, H, W, K, st);
-        default: return launch_conv<bf16_t, FLIP>(name, x, f, y, N, C, H, W, K, st);
-    }
+    return dispatch_float(dtype, [&](auto t) {
+        return launch_conv<typename decltype(t)::type, FLIP>(name, x, f, y, N, C, H, W, K, st);
+    });
 }
 
 // =================================================================================================
@@ -1055,10 +1030,21 @@ __global__ void __launch_bounds__(DWG_THREADS) dw_wgrad_mfma_kernel(const T* __r
 }
 
 static bool dw_wgrad_mfma_ok(const void* dy, const void* x, int64_t N, int64_t C, int64_t H, int64_t W, int K, size_t es) {
-    static const bool on = [] { const char* e = getenv("OFASR_DW_WGRAD_MFMA"); return !(e && e[0] == '0'); }();
+    static const bool on = env_default_on("OFASR_DW_WGRAD_MFMA");
     return on && es == 2 && (K == 3 || K == 5 || K == 7) && (W == 32 || W == 64) && H % 16 == 0 && H >= 16 && H <= 64 &&
-           N >= 1 && C >= 1 && C <= INT32_MAX && N <= INT32_MAX &&
-           ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+           N >= 1 && C >= 1 && C <= INT32_MAX && N <= INT32_MAX && aligned16(dy, x);
+}
+
+// the matrix-core weight gradient for a shape dw_wgrad_mfma_ok has accepted (W in {64, 32}, K in {7, 5, 3})
+template <typename T, bool XF, bool GBX>
+static void launch_wgrad_mfma(const void* dy, const void* x, float* df, int64_t N, int64_t C, int64_t H, int64_t W, int K,
+                              InputXf xf, BwdXf bx, hipStream_t st) {
+    dispatch_int<64, 32>((int)W, [&](auto WW) {
+        dispatch_int<7, 5, 3>(K, [&](auto KK) {
+            OFASR_LAUNCH((dw_wgrad_mfma_kernel<T, KK, WW / 32, XF, GBX>), dim3((unsigned)C), dim3(DWG_THREADS), 0, st,
+                         (const T*)dy, (const T*)x, df, (int)N, (int)C, (int)H, xf, bx);
+        });
+    });
 }
 
 template <typename T, bool XF = false>
@@ -1068,15 +1054,7 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
               2.0 * K * K * (double)N * (double)C * (double)H * (double)W);
     if constexpr (!std::is_same<T, float>::value) {
         if (dw_wgrad_mfma_ok(dy, x, N, C, H, W, K, sizeof(T))) {
-#define OFASR_DWGM(KK, WT)                                                                                          \
-    OFASR_LAUNCH((dw_wgrad_mfma_kernel<T, KK, WT, XF>), dim3((unsigned)C), dim3(DWG_THREADS), 0, st, (const T*)dy,   \
-                 (const T*)x, df, (int)N, (int)C, (int)H, xf)
-            if (W == 64) {
-                if (K == 7) OFASR_DWGM(7, 2); else if (K == 5) OFASR_DWGM(5, 2); else OFASR_DWGM(3, 2);
-            } else {
-                if (K == 7) OFASR_DWGM(7, 1); else if (K == 5) OFASR_DWGM(5, 1); else OFASR_DWGM(3, 1);
-            }
-#undef OFASR_DWGM
+            launch_wgrad_mfma<T, XF, false>(dy, x, df, N, C, H, W, K, xf, BwdXf{}, st);
             return check_launch(name);
         }
     }
@@ -1085,16 +1063,10 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
         if (vec_geom(H, W, (int)sizeof(T), 4, dy, x, vg)) {
             const long long nwaves = (long long)N * C * vg.nslabs;
             const unsigned grid = (unsigned)cdiv(nwaves, DW_WAVES);
-#define OFASR_DWWV(KK)                                                                                              \
-    OFASR_LAUNCH((dw_wgrad_vec_kernel<T, KK, XF>), dim3(grid), dim3(64 * DW_WAVES), 0, st, (const T*)dy,      \
-                       (const T*)x, ws, (int)H, (int)W, vg, nwaves, (int)C, xf)
-            switch (K) {
-                case 1: OFASR_DWWV(1); break;
-                case 3: OFASR_DWWV(3); break;
-                case 5: OFASR_DWWV(5); break;
-                default: OFASR_DWWV(7); break;
-            }
-#undef OFASR_DWWV
+            dispatch_int<1, 3, 5, 7>(K, [&](auto KK) {
+                OFASR_LAUNCH((dw_wgrad_vec_kernel<T, KK, XF>), dim3(grid), dim3(64 * DW_WAVES), 0, st, (const T*)dy, (const T*)x,
+                             ws, (int)H, (int)W, vg, nwaves, (int)C, xf);
+            });
             int rc0 = check_launch(name);
             if (rc0) return rc0;
             const long long CKK0 = (long long)C * K * K;
@@ -1109,17 +1081,10 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
     }
     const int nparts = wgrad_parts(N, C);
     const long long units = (long long)C * nparts;
-#define OFASR_DW_WG(KK)                                                                                        \
-    OFASR_LAUNCH((dw_wgrad_kernel<T, KK>), dim3((unsigned)cdiv(units, DW_WAVES)), dim3(64 * DW_WAVES), 0, \
-                       st, (const T*)dy, (const T*)x, ws, (int)N, (int)C, (int)H, (int)W,                      \
-                       Strips<KK>::count((int)W), nparts, units)
-    switch (K) {
-        case 1: OFASR_DW_WG(1); break;
-        case 3: OFASR_DW_WG(3); break;
-        case 5: OFASR_DW_WG(5); break;
-        default: OFASR_DW_WG(7); break;
-    }
-#undef OFASR_DW_WG
+    dispatch_int<1, 3, 5, 7>(K, [&](auto KK) {
+        OFASR_LAUNCH((dw_wgrad_kernel<T, KK>), dim3((unsigned)cdiv(units, DW_WAVES)), dim3(64 * DW_WAVES), 0, st, (const T*)dy,
+                     (const T*)x, ws, (int)N, (int)C, (int)H, (int)W, Strips<KK>::count((int)W), nparts, units);
+    });
     int rc = check_launch(name);
     if (rc) return rc;
     const long long CKK = (long long)C * K * K;
@@ -1129,7 +1094,7 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
 }
 
 bool dwconv_xf_supported(const void* x, const void* y, int64_t H, int64_t W, int K, int dtype) {
-    if (dtype != OFASR_F16 && dtype != OFASR_BF16) return false;
+    if (!is_16bit(dtype)) return false;
     VecGeom vg;
     const int pxl = K <= 3 ? 8 : 4;
     return vec_geom(H, W, 2, pxl, x, y, vg) && vec_geom(H, W, 2, 4, x, y, vg);
@@ -1149,7 +1114,7 @@ bool dwconv_stat_supported(const void* x, const void* y, int64_t H, int64_t W, i
     VecGeom vg;
     const int pxl = (K <= 3 && dtype != OFASR_F32) ? 8 : 4;
     if (dtype != OFASR_F32 && mfma_geom_ok(H, W, K, x, y)) return vec_geom(H, W, 2, 4, x, y, vg);
-    return vec_geom(H, W, dtype == OFASR_F32 ? 4 : 2, pxl, x, y, vg);
+    return vec_geom(H, W, (int)elem_bytes(dtype), pxl, x, y, vg);
 }
 int dwconv_fwd_stat(const void* x, const float* f, void* y, int64_t N, int64_t C, int64_t H, int64_t W, int K, int dtype,
                     StatOut so, void* stream) {
@@ -1160,9 +1125,9 @@ int dwconv_fwd_stat(const void* x, const float* f, void* y, int64_t N, int64_t C
                   "%s: needs the vector kernel and a statistics buffer", name);
     if (N * C * H * W == 0) return OFASR_OK;
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F32) return launch_conv<float, false, false, true>(name, x, f, y, N, C, H, W, K, st, InputXf{}, so);
-    if (dtype == OFASR_F16) return launch_conv<f16_t, false, false, true>(name, x, f, y, N, C, H, W, K, st, InputXf{}, so);
-    return launch_conv<bf16_t, false, false, true>(name, x, f, y, N, C, H, W, K, st, InputXf{}, so);
+    return dispatch_float(dtype, [&](auto t) {
+        return launch_conv<typename decltype(t)::type, false, false, true>(name, x, f, y, N, C, H, W, K, st, InputXf{}, so);
+    });
 }
 
 int dwconv_fwd_xf(const void* x, const float* f, void* y, int64_t N, int64_t C, int64_t H, int64_t W, int K, int dtype,
@@ -1173,17 +1138,15 @@ int dwconv_fwd_xf(const void* x, const float* f, void* y, int64_t N, int64_t C, 
     OFASR_REQUIRE((xf.scale && xf.shift && xf.mean) ||
                       (fold.cp && fold.P > 0 && fold.mean && fold.invstd && fold.scale && fold.shift),
                   OFASR_ERR_INVALID_ARG, "%s: null transform", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit only");
     if (N * C * H * W == 0) return OFASR_OK;
     hipStream_t st = as_stream(stream);
-    if (so.partial) {
-        if (dtype == OFASR_F16)
-            return launch_conv<f16_t, false, true, true>(name, x, f, y, N, C, H, W, K, st, xf, so, fold);
-        return launch_conv<bf16_t, false, true, true>(name, x, f, y, N, C, H, W, K, st, xf, so, fold);
-    }
-    if (dtype == OFASR_F16)
-        return launch_conv<f16_t, false, true>(name, x, f, y, N, C, H, W, K, st, xf, StatOut{nullptr, 0}, fold);
-    return launch_conv<bf16_t, false, true>(name, x, f, y, N, C, H, W, K, st, xf, StatOut{nullptr, 0}, fold);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return dispatch_bool(so.partial != nullptr, [&](auto STAT) {
+            return launch_conv<typename decltype(t)::type, false, true, STAT>(name, x, f, y, N, C, H, W, K, st, xf,
+                                                                              STAT ? so : StatOut{nullptr, 0}, fold);
+        });
+    });
 }
 
 int dwconv_wgrad_xf(const void* dy, const void* x, float* df, int64_t N, int64_t C, int64_t H, int64_t W, int K,
@@ -1192,23 +1155,22 @@ int dwconv_wgrad_xf(const void* dy, const void* x, float* df, int64_t N, int64_t
     int rc = check_conv_args(name, dy, x, df, N, C, H, W, K, dtype);
     if (rc) return rc;
     OFASR_REQUIRE(xf.scale && xf.shift && xf.mean, OFASR_ERR_INVALID_ARG, "%s: null transform", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit only");
     OFASR_REQUIRE(N * C * H * W > 0, OFASR_ERR_UNSUPPORTED, "%s: empty tensor", name);
     const size_t need = ofasr_dwconv_wgrad_workspace(N, C, H, W, K);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16) return launch_wgrad<f16_t, true>(name, dy, x, df, N, C, H, W, K, (float*)workspace, st, xf);
-    return launch_wgrad<bf16_t, true>(name, dy, x, df, N, C, H, W, K, (float*)workspace, st, xf);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_wgrad<typename decltype(t)::type, true>(name, dy, x, df, N, C, H, W, K, (float*)workspace, st, xf);
+    });
 }
 
 // weight gradient on the matrix cores with BOTH operands formed on read: a = relu6(BN(x)) (InputXf) and the gradient
 // dy(da, y) through the BN backward (BwdXf).  Only where dw_wgrad_mfma_kernel applies (dwconv_wgrad_bx_supported).
 bool dwconv_wgrad_bx_supported(const void* da, const void* x, const void* y, int64_t N, int64_t C, int64_t H, int64_t W,
                                int K, int dtype) {
-    static const bool on = [] { const char* e = getenv("OFASR_DW_WGRAD_BX"); return !(e && e[0] == '0'); }();
-    return on && (dtype == OFASR_F16 || dtype == OFASR_BF16) && dw_wgrad_mfma_ok(da, x, N, C, H, W, K, 2) &&
-           (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    static const bool on = env_default_on("OFASR_DW_WGRAD_BX");
+    return on && is_16bit(dtype) && dw_wgrad_mfma_ok(da, x, N, C, H, W, K, 2) && aligned16(y);
 }
 
 int dwconv_wgrad_xf_bx(const void* da, const void* x, float* df, int64_t N, int64_t C, int64_t H, int64_t W, int K,
@@ -1222,21 +1184,9 @@ int dwconv_wgrad_xf_bx(const void* da, const void* x, float* df, int64_t N, int6
     hipStream_t st = as_stream(stream);
     prof_note(2.0 * 3.0 * (double)N * (double)C * (double)H * (double)W + 4.0 * (double)C * K * K,
               2.0 * K * K * (double)N * (double)C * (double)H * (double)W);
-#define OFASR_DWGB(TT, KK, WT)                                                                                       \
-    OFASR_LAUNCH((dw_wgrad_mfma_kernel<TT, KK, WT, true, true>), dim3((unsigned)C), dim3(DWG_THREADS), 0, st,         \
-                 (const TT*)da, (const TT*)x, df, (int)N, (int)C, (int)H, xf, bx)
-#define OFASR_DWGB_T(TT)                                                                                             \
-    do {                                                                                                            \
-        if (W == 64) {                                                                                              \
-            if (K == 7) OFASR_DWGB(TT, 7, 2); else if (K == 5) OFASR_DWGB(TT, 5, 2); else OFASR_DWGB(TT, 3, 2);       \
-        } else {                                                                                                    \
-            if (K == 7) OFASR_DWGB(TT, 7, 1); else if (K == 5) OFASR_DWGB(TT, 5, 1); else OFASR_DWGB(TT, 3, 1);       \
-        }                                                                                                           \
-    } while (0)
-    if (dtype == OFASR_F16) OFASR_DWGB_T(f16_t);
-    else OFASR_DWGB_T(bf16_t);
-#undef OFASR_DWGB_T
-#undef OFASR_DWGB
+    dispatch_16bit(dtype, [&](auto t) {
+        launch_wgrad_mfma<typename decltype(t)::type, true, true>(da, x, df, N, C, H, W, K, xf, bx, st);
+    });
     return check_launch(name);
 }
 
@@ -1250,16 +1200,14 @@ int dwconv_dgrad_bx(const void* da, const float* f, void* dx, int64_t N, int64_t
     OFASR_REQUIRE(bx.y && bx.mean && bx.scale && bx.shift &&
                       ((bx.ka && bx.kbi) || (bx.fold_partial && bx.fold_invstd && bx.fold_P > 0 && bx.fold_C == C)),
                   OFASR_ERR_INVALID_ARG, "%s: null transform", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit only", name);
-    OFASR_REQUIRE(((reinterpret_cast<uintptr_t>(bx.y) | reinterpret_cast<uintptr_t>(bx.dy_out)) & 15) == 0,
-                  OFASR_ERR_UNSUPPORTED, "%s: unaligned y / dy_out", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit only");
+    OFASR_REQUIRE(aligned16(bx.y, bx.dy_out), OFASR_ERR_UNSUPPORTED, "%s: unaligned y / dy_out", name);
     if (N * C * H * W == 0) return OFASR_OK;
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16)
-        return launch_conv<f16_t, true, false, false, true>(name, da, f, dx, N, C, H, W, K, st, InputXf{}, StatOut{nullptr, 0},
-                                                            BnFold{}, bx);
-    return launch_conv<bf16_t, true, false, false, true>(name, da, f, dx, N, C, H, W, K, st, InputXf{}, StatOut{nullptr, 0},
-                                                         BnFold{}, bx);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_conv<typename decltype(t)::type, true, false, false, true>(name, da, f, dx, N, C, H, W, K, st, InputXf{},
+                                                                                 StatOut{nullptr, 0}, BnFold{}, bx);
+    });
 }
 
 }  // namespace ofasr
@@ -1300,12 +1248,7 @@ OFASR_EXPORT int ofasr_dwconv_wgrad(const void* dy, const void* x, float* df, in
         return OFASR_OK;
     }
     const size_t need = ofasr_dwconv_wgrad_workspace(N, C, H, W, K);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     float* ws = (float*)workspace;
-    switch (dtype) {
-        case OFASR_F32: return launch_wgrad<float>(name, dy, x, df, N, C, H, W, K, ws, st);
-        case OFASR_F16: return launch_wgrad<f16_t>(name, dy, x, df, N, C, H, W, K, ws, st);
-        default: return launch_wgrad<bf16_t>(name, dy, x, df, N, C, H, W, K, ws, st);
-    }
+    return dispatch_float(dtype, [&](auto t) { return launch_wgrad<typename decltype(t)::type>(name, dy, x, df, N, C, H, W, K, ws, st); });
 }

@@ -416,8 +416,7 @@ OFASR_EXPORT int ofasr_ktransform_bwd(const float* w_max, const int* ks, int nst
     const bool chain = p.transform && nsteps > 0;
     if (chain) {
         const size_t need = ofasr_ktransform_bwd_workspace(ks, nsteps, C);
-        OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE,
-                      "%s: workspace %zu B < required %zu B", name, workspace_bytes, need);
+        OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
         int64_t off = 0;
         for (int s = 0; s < nsteps; ++s) {
             OFASR_REQUIRE(dmats && dmats[s], OFASR_ERR_INVALID_ARG, "%s: dmats[%d] is null", name, s);

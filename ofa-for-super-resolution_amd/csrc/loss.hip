@@ -286,8 +286,7 @@ __global__ void __launch_bounds__(256) sr_loss_bwd_kernel(LOperand O, LOperand T
     }
 }
 
-static bool l_fmt_ok(int f) { return f == OFASR_F32 || f == OFASR_F16 || f == OFASR_BF16; }
-static double l_fmt_bytes(int f) { return f == OFASR_F32 ? 4.0 : 2.0; }
+static double l_fmt_bytes(int f) { return (double)elem_bytes(f); }
 static bool l_kind_ok(int k) { return k == OFASR_LOSS_MSE || k == OFASR_LOSS_L1 || k == OFASR_LOSS_CHARBONNIER; }
 
 static int l_parts(int64_t elems) {
@@ -297,16 +296,14 @@ static int l_parts(int64_t elems) {
 
 // 16-byte requests: every tensor of the call at a 16-byte aligned address, H * W % 8 == 0
 static bool l_vec(int64_t plane, const void* a, const void* b, const void* c, const void* d) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                           reinterpret_cast<uintptr_t>(d);
-    return bits % 16 == 0 && plane % LC == 0;
+    return aligned16(a, b, c, d) && plane % LC == 0;
 }
 
 // what the two entry points check alike; 0 when the call may go on
 static int l_check(const char* name, const void* o, int fmt_o, const void* t, int fmt_t, const void* s, int fmt_s, int64_t N,
                    int64_t H, int64_t W, int kind, double eps) {
     OFASR_REQUIRE(o && t, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
-    OFASR_REQUIRE(l_fmt_ok(fmt_o) && l_fmt_ok(fmt_t) && (!s || l_fmt_ok(fmt_s)), OFASR_ERR_INVALID_ARG,
+    OFASR_REQUIRE(is_float_dtype(fmt_o) && is_float_dtype(fmt_t) && (!s || is_float_dtype(fmt_s)), OFASR_ERR_INVALID_ARG,
                   "%s: operands are f32 / f16 / bf16 (formats %d / %d / %d)", name, fmt_o, fmt_t, fmt_s);
     OFASR_REQUIRE(l_kind_ok(kind), OFASR_ERR_INVALID_ARG, "%s: unknown loss kind %d", name, kind);
     OFASR_REQUIRE(N > 0 && H > 0 && W > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
@@ -349,7 +346,7 @@ OFASR_EXPORT int ofasr_sr_loss_fwd(const void* o, int fmt_o, const void* t, int 
     OFASR_REQUIRE(reinterpret_cast<uintptr_t>(result) % 8 == 0, OFASR_ERR_INVALID_ARG, "%s: result is not 8-byte aligned", name);
     const int64_t plane = H * W, elems = 3 * N * plane;
     const size_t need = ofasr_sr_loss_workspace(elems);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+    OFASR_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
                   OFASR_ERR_WORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", name, need,
                   workspace_bytes);
     const int P = l_parts(elems);
@@ -359,17 +356,13 @@ OFASR_EXPORT int ofasr_sr_loss_fwd(const void* o, int fmt_o, const void* t, int 
     const bool vec = l_vec(plane, o, t, s, nullptr);
     hipStream_t st = as_stream(stream);
     prof_note((double)elems * (l_fmt_bytes(fmt_o) + l_fmt_bytes(fmt_t) + (s ? l_fmt_bytes(fmt_s) : 0.0)), 0.0);
-#define L_FWD(K)                                                                                                      \
-    do {                                                                                                              \
-        if (s && vec) l_fwd_launch<K, true, true>(P, st, O, T, S, plane, cpi, total, eps2, (LPartial*)workspace);      \
-        else if (s) l_fwd_launch<K, true, false>(P, st, O, T, S, plane, cpi, total, eps2, (LPartial*)workspace);       \
-        else if (vec) l_fwd_launch<K, false, true>(P, st, O, T, S, plane, cpi, total, eps2, (LPartial*)workspace);     \
-        else l_fwd_launch<K, false, false>(P, st, O, T, S, plane, cpi, total, eps2, (LPartial*)workspace);             \
-    } while (0)
-    if (kind == OFASR_LOSS_MSE) L_FWD(OFASR_LOSS_MSE);
-    else if (kind == OFASR_LOSS_L1) L_FWD(OFASR_LOSS_L1);
-    else L_FWD(OFASR_LOSS_CHARBONNIER);
-#undef L_FWD
+    dispatch_int<OFASR_LOSS_MSE, OFASR_LOSS_L1, OFASR_LOSS_CHARBONNIER>(kind, [&](auto K) {
+        dispatch_bool(s != nullptr, [&](auto KD) {
+            dispatch_bool(vec, [&](auto VEC) {
+                l_fwd_launch<K, KD, VEC>(P, st, O, T, S, plane, cpi, total, eps2, (LPartial*)workspace);
+            });
+        });
+    });
     OFASR_LAUNCH(sr_loss_fold_kernel, dim3(1), dim3(256), 0, st, (const LPartial*)workspace, P, (double)elems, w_main, w_kd,
                  psnr_count, result);
     return check_launch(name);
@@ -392,16 +385,12 @@ OFASR_EXPORT int ofasr_sr_loss_bwd(const void* o, int fmt_o, const void* t, int 
     const bool vec = l_vec(plane, o, t, s, grad);
     hipStream_t st = as_stream(stream);
     prof_note((double)elems * (2.0 * l_fmt_bytes(fmt_o) + l_fmt_bytes(fmt_t) + (s ? l_fmt_bytes(fmt_s) : 0.0)), 0.0);
-#define L_BWD(K)                                                                                                      \
-    do {                                                                                                              \
-        if (s && vec) l_bwd_launch<K, true, true>(P, st, O, T, S, g, ca, cb, plane, cpi, total, eps2, grad);           \
-        else if (s) l_bwd_launch<K, true, false>(P, st, O, T, S, g, ca, cb, plane, cpi, total, eps2, grad);            \
-        else if (vec) l_bwd_launch<K, false, true>(P, st, O, T, S, g, ca, cb, plane, cpi, total, eps2, grad);          \
-        else l_bwd_launch<K, false, false>(P, st, O, T, S, g, ca, cb, plane, cpi, total, eps2, grad);                  \
-    } while (0)
-    if (kind == OFASR_LOSS_MSE) L_BWD(OFASR_LOSS_MSE);
-    else if (kind == OFASR_LOSS_L1) L_BWD(OFASR_LOSS_L1);
-    else L_BWD(OFASR_LOSS_CHARBONNIER);
-#undef L_BWD
+    dispatch_int<OFASR_LOSS_MSE, OFASR_LOSS_L1, OFASR_LOSS_CHARBONNIER>(kind, [&](auto K) {
+        dispatch_bool(s != nullptr, [&](auto KD) {
+            dispatch_bool(vec, [&](auto VEC) {
+                l_bwd_launch<K, KD, VEC>(P, st, O, T, S, g, ca, cb, plane, cpi, total, eps2, grad);
+            });
+        });
+    });
     return check_launch(name);
 }

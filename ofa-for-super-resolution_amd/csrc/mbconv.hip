@@ -16,16 +16,15 @@
 
 namespace ofasr {
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static bool bn_fold_enabled() {
-    static const bool on = [] { const char* e = getenv("OFASR_MBCONV_BN_BWD_FOLD"); return !(e && e[0] == '0'); }();
+    static const bool on = env_default_on("OFASR_MBCONV_BN_BWD_FOLD");
     return on;
 }
 // set by ofasr_mbstack_fwd / _bwd around their per-block calls: the stack runs the kernel transforms of all blocks in one
 // launch per phase itself (bit 0: the active filter is already in stat_buf; bit 1: leave the filter gradient's chain to the
 // caller)
 static thread_local int t_skip_kt = 0;
-static std::atomic<int> g_bn_bwd_stat{[] { const char* e = getenv("OFASR_MBCONV_BN_BWD_STAT"); return (e && e[0] == '1') ? 1 : 0; }()};
+static std::atomic<int> g_bn_bwd_stat{env_default_off("OFASR_MBCONV_BN_BWD_STAT") ? 1 : 0};
 
 struct MbSizes {
     size_t es;            // activation element size
@@ -47,7 +46,7 @@ struct MbSizes {
 static MbSizes mb_sizes(const ofasr_mbconv_desc* d) {
     MbSizes s;
     const int64_t HW = d->H * d->W;
-    s.es = d->dtype == OFASR_F32 ? 4 : 2;
+    s.es = elem_bytes(d->dtype);
     s.mid_elems = (size_t)(d->N * d->mid * HW);
     s.out_elems = (size_t)(d->N * d->Cout * HW);
     const int64_t cbig = d->mid > d->Cout ? d->mid : d->Cout;
@@ -130,13 +129,12 @@ static SideStream& side_stream() {
     static SideStream ss;
     if (!ss.ready) {
         ss.ready = true;
-        const char* e = getenv("OFASR_MBCONV_SIDE_STREAM");
-        ss.enabled = !(e && e[0] == '0');
+        ss.enabled = env_default_on("OFASR_MBCONV_SIDE_STREAM");
         if (ss.enabled) {
             // default priority.  OFASR_SIDE_STREAM_PRIORITY=low|high for experiments: measured on the north-star step,
             // low 2160-2200 and high 2280 against 2275 images/s at the default -- the input-gradient chain is
             // the critical path, yet starving the weight gradients only moves the wait to the end of backward
-            const char* pe = getenv("OFASR_SIDE_STREAM_PRIORITY");
+            const char* pe = env_value("OFASR_SIDE_STREAM_PRIORITY");
             int least = 0, greatest = 0;
             bool ok;
             if (pe && (pe[0] == 'l' || pe[0] == 'h') && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
@@ -239,13 +237,11 @@ OFASR_EXPORT int ofasr_mbconv_fwd(const ofasr_mbconv_desc* d, const void* x, voi
     if (rc) return rc;
     OFASR_REQUIRE(x && act_buf && stat_buf, OFASR_ERR_INVALID_ARG, "%s: null buffer", name);
     const MbSizes s = mb_sizes(d);
-    OFASR_REQUIRE(workspace && workspace_bytes >= s.total, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, s.total);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, s.total);
     const int64_t HW = d->H * d->W;
     char* a = (char*)act_buf;
     const ActLayout lay = act_layout(d, s);
-    OFASR_REQUIRE(!lay.fused || (reinterpret_cast<uintptr_t>(act_buf) & 15) == 0, OFASR_ERR_INVALID_ARG,
-                  "%s: act_buf must be 16-byte aligned", name);
+    OFASR_REQUIRE(!lay.fused || aligned16(act_buf), OFASR_ERR_INVALID_ARG, "%s: act_buf must be 16-byte aligned", name);
     void* y1 = a + lay.y1 * s.es;
     void* a1 = a + lay.a1 * s.es;
     void* y2 = a + lay.y2 * s.es;
@@ -269,7 +265,7 @@ OFASR_EXPORT int ofasr_mbconv_fwd(const ofasr_mbconv_desc* d, const void* x, voi
     // 5-round cross-lane reduce at the tail of a kernel whose blocks all run in phase): +0.8 % on the step, kept behind
     // a switch (OFASR_PW_EPILOGUE_STATS=0 goes back to the pass); the depthwise kernel's statistics are free (one wave
     // owns a whole plane).
-    static const bool pw_stat = [] { const char* e = getenv("OFASR_PW_EPILOGUE_STATS"); return !(e && e[0] == '0'); }();
+    static const bool pw_stat = env_default_on("OFASR_PW_EPILOGUE_STATS");
     if (pw_stat && d->bn_training[0])   // fused or not: the un-fused path folds the partials in its BN apply (below)
         rc = pwconv_fwd_stat(x, d->w1, d->ldw1, y1, d->N, d->Cin, d->mid, HW, d->dtype,
                              StatOut{(float2*)workspace, pwconv_stat_units(d->N, d->Cin, HW)}, stream);
@@ -423,14 +419,12 @@ static int mbconv_bwd_impl(const ofasr_mbconv_desc* d, const void* x, const void
     for (int i = 0; i < 3; ++i)
         OFASR_REQUIRE(g->dgamma[i] && g->dbeta[i], OFASR_ERR_INVALID_ARG, "%s: null BN gradient %d", name, i);
     const MbSizes s = mb_sizes(d);
-    OFASR_REQUIRE(workspace && workspace_bytes >= s.total, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, s.total);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, s.total);
     const int64_t HW = d->H * d->W;
     hipStream_t st = as_stream(stream);
     const char* a = (const char*)act_buf;
     const ActLayout lay = act_layout(d, s);
-    OFASR_REQUIRE(!lay.fused || (reinterpret_cast<uintptr_t>(act_buf) & 15) == 0, OFASR_ERR_INVALID_ARG,
-                  "%s: act_buf must be 16-byte aligned", name);
+    OFASR_REQUIRE(!lay.fused || aligned16(act_buf), OFASR_ERR_INVALID_ARG, "%s: act_buf must be 16-byte aligned", name);
     const void* y1 = a + lay.y1 * s.es;
     const void* a1 = a + lay.a1 * s.es;
     const void* y2 = a + lay.y2 * s.es;
@@ -539,7 +533,7 @@ static int mbconv_bwd_impl(const ofasr_mbconv_desc* d, const void* x, const void
     };
     const bool fused = lay.fused;
     if (fused)
-        OFASR_REQUIRE((reinterpret_cast<uintptr_t>(tmp_buf) & 15) == 0, OFASR_ERR_UNSUPPORTED,
+        OFASR_REQUIRE(aligned16(tmp_buf), OFASR_ERR_UNSUPPORTED,
                       "%s: tmp_buf must be 16-byte aligned (the forward pass did not materialise the activations)", name);
     // project 1x1: weight gradient (side) beside input gradient + BN2 backward (main)
     rc = fork(0);   // dy3 (t3) is final
@@ -576,7 +570,7 @@ static int mbconv_bwd_impl(const ofasr_mbconv_desc* d, const void* x, const void
     // the weight-gradient kernel 39 us longer (28 -> 67 us: ten vector instructions per element on twelve fragments per
     // quad make it issue-bound), and with the host out of the way (round 3) the step is bound by the GPU's total work:
     // 2445 against 2514 images/s, two A/B pairs on one box.  (While the step was host-bound the same switch gained 1.2 %.)
-    static const bool wg1_env = [] { const char* e = getenv("OFASR_MBCONV_WG1_BX"); return e && e[0] == '1'; }();
+    static const bool wg1_env = env_default_off("OFASR_MBCONV_WG1_BX");
     const bool wg1_bx = fused && bn_fold && wg1_env &&
                         pwconv_wgrad_bx_supported(tB, y1, x, d->Cin, d->mid, HW, d->dtype);
     BwdXf bx1{y1, s1.mean, s1.scale, s1.shift, coef + 2 * d->mid, coef + 3 * d->mid,
@@ -584,7 +578,7 @@ static int mbconv_bwd_impl(const ofasr_mbconv_desc* d, const void* x, const void
     // The consumers fold the reduction pass's partial slabs themselves (BwdXf::fold_*): no coefficient launch between a
     // reduction and its consumer on the chain (2 x 5.7 us of pure latency per block); the depthwise input gradient also
     // publishes (ka2, kbi2) for the side stream's weight gradient.  OFASR_MBCONV_BN_COEF_FOLD=0: the coefficient kernel.
-    static const bool coef_fold = [] { const char* e = getenv("OFASR_MBCONV_BN_COEF_FOLD"); return !(e && e[0] == '0'); }();
+    static const bool coef_fold = env_default_on("OFASR_MBCONV_BN_COEF_FOLD");
     auto arm_fold = [&](BwdXf& bx, int P, const StatView& sv, int which) {
         bx.fold_partial = (const double*)workspace;
         bx.fold_P = P;
@@ -598,7 +592,7 @@ static int mbconv_bwd_impl(const ofasr_mbconv_desc* d, const void* x, const void
         bx.coef_kbi = const_cast<float*>(bx.kbi);
     };
     const bool bxp = fused && bn_fold && dwconv_xf_supported(tA, tB, d->H, d->W, d->K, d->dtype) &&
-                     (reinterpret_cast<uintptr_t>(tC) & 15) == 0 &&
+                     aligned16(tC) &&
                      pwconv_dgrad_bx_supported(tB, y1, dx, d->residual ? dout : nullptr, d->w1, d->ldw1, d->Cin, d->mid, HW,
                                                d->dtype);
     // ... and, optionally, without the reduction pass where the producer of da can take the sums itself (BwdStatOut): the
@@ -739,13 +733,13 @@ static int mbconv_bwd_impl(const ofasr_mbconv_desc* d, const void* x, const void
 // above the C ABI (autograd node, descriptor marshalling, three allocations, the foreign call itself).
 static const void* stack_out_of(const ofasr_mbstack_item& it) {
     const ofasr_mbconv_desc* d = it.desc;
-    const size_t es = d->dtype == OFASR_F32 ? 4 : 2;
+    const size_t es = elem_bytes(d->dtype);
     const size_t out_elems = (size_t)(d->N * d->Cout * d->H * d->W);
     return (const char*)it.act_buf + (ofasr_mbconv_act_elems(d) - out_elems) * es;
 }
 
 static bool stack_kt_batch_enabled() {
-    static const bool on = [] { const char* e = getenv("OFASR_MBSTACK_KT_BATCH"); return !(e && e[0] == '0'); }();
+    static const bool on = env_default_on("OFASR_MBSTACK_KT_BATCH");
     return on;
 }
 

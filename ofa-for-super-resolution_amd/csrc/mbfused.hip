@@ -575,7 +575,6 @@ __global__ void __launch_bounds__(256) mb_fused_sum_kernel(const float* __restri
     }
 }
 
-static size_t mf_align(size_t v) { return (v + 255) / 256 * 256; }
 struct MfPlan {
     int tw, th, tiles_x, tiles_y, nsplit;
     long long tiles;
@@ -584,7 +583,7 @@ struct MfPlan {
 // is nchunk x (a latency-bound chunk), so a launch that cannot fill the chip is shortened by spreading the chunks.
 // OFASR_MBFUSED_SPLIT=0 disables it.
 constexpr int MF_CUS = 256;
-static std::atomic<int> g_mf_split{[] { const char* e = getenv("OFASR_MBFUSED_SPLIT"); return (e && e[0] == '0') ? 0 : 1; }()};
+static std::atomic<int> g_mf_split{env_default_on("OFASR_MBFUSED_SPLIT") ? 1 : 0};
 static MfPlan mf_plan(const ofasr_mbconv_desc* d, int tw) {
     const bool split_ok = g_mf_split.load(std::memory_order_relaxed) != 0;
     MfPlan pl;
@@ -613,25 +612,25 @@ static MfWs mf_ws(const ofasr_mbconv_desc* d) {
     MfWs s;
     const int npair = (K + 1) / 2;
     size_t o = 0;
-    s.f = o;    o += mf_align((size_t)mid * K * K * sizeof(float));
-    s.w1f = o;  o += mf_align((size_t)mid * 64 * 2);
-    s.b1 = o;   o += mf_align((size_t)mid * sizeof(float));
-    s.taps = o; o += mf_align((size_t)mid * ((K * npair + 1 + 3) / 4 * 4) * sizeof(uint32_t));
-    s.b2 = o;   o += mf_align((size_t)mid * sizeof(float));
-    s.w2f = o;  o += mf_align((size_t)64 * mid * 2);
-    s.b3 = o;   o += mf_align(64 * sizeof(float));
-    s.part = o;     o += mf_align(n_part * sizeof(float));
+    s.f = o;    o += align_up((size_t)mid * K * K * sizeof(float), 256);
+    s.w1f = o;  o += align_up((size_t)mid * 64 * 2, 256);
+    s.b1 = o;   o += align_up((size_t)mid * sizeof(float), 256);
+    s.taps = o; o += align_up((size_t)mid * ((K * npair + 1 + 3) / 4 * 4) * sizeof(uint32_t), 256);
+    s.b2 = o;   o += align_up((size_t)mid * sizeof(float), 256);
+    s.w2f = o;  o += align_up((size_t)64 * mid * 2, 256);
+    s.b3 = o;   o += align_up(64 * sizeof(float), 256);
+    s.part = o;     o += align_up(n_part * sizeof(float), 256);
     s.total = o;
     return s;
 }
 
 static bool mf_supported(const ofasr_mbconv_desc* d) {
-    return d && (d->dtype == OFASR_BF16 || d->dtype == OFASR_F16) && d->Cin == 64 && d->Cout == 64 && d->mid > 0 &&
+    return d && is_16bit(d->dtype) && d->Cin == 64 && d->Cout == 64 && d->mid > 0 &&
            d->mid % MF_MC == 0 && (d->K == 3 || d->K == 5 || d->K == 7) && !d->bn_training[0] && !d->bn_training[1] &&
            !d->bn_training[2] && d->N > 0 && d->H > 0 && d->W > 0;
 }
 
-static std::atomic<int> g_mf_tile{[] { const char* e = getenv("OFASR_MBFUSED_TILE"); return e ? atoi(e) : 0; }()};
+static std::atomic<int> g_mf_tile{env_positive_int("OFASR_MBFUSED_TILE", 0)};
 
 // Tile shape.  Wide tiles move whole 128-byte lines (the 16x16 tile touches 32-byte row pieces, four workgroups per
 // line) and measured 7 % (8x32) / 12 % (4x64) faster than 16x16 on images they cover without waste (N=16, mid 384:
@@ -688,30 +687,19 @@ static int mf_run(const ofasr_mbconv_desc* d, const void* x, void* out, char* ws
     OFASR_REQUIRE(blocks <= INT32_MAX, OFASR_ERR_UNSUPPORTED, "ofasr_mbconv_infer: too many tiles");
     const double px = (double)d->N * (double)d->H * (double)d->W;
     prof_note(2.0 * px * 64 * (d->residual ? 3.0 : 2.0), 2.0 * px * (2.0 * 64 * d->mid + (double)d->K * d->K * d->mid));
-#define OFASR_MF(KK, TH, TW)                                                                                          \
-    OFASR_LAUNCH((mb_fused_kernel<T, KK, TH, TW>), dim3((unsigned)blocks), dim3(MF_THREADS), 0, st, (const T*)x,       \
-                 (T*)out, (const T*)w1f, (const float*)b1, (const uint32_t*)taps, (const float*)b2, (const T*)w2f,     \
-                 (const float*)b3, (int)d->mid, (int)d->H, (int)d->W, tiles_x, tiles_y, d->residual, nsplit, part)
-#define OFASR_MFK(TH, TW)                  \
-    do {                                   \
-        if (d->K == 7) OFASR_MF(7, TH, TW); \
-        else if (d->K == 5) OFASR_MF(5, TH, TW); \
-        else OFASR_MF(3, TH, TW);          \
-    } while (0)
-    if (tw == 64) OFASR_MFK(4, 64);
-    else if (tw == 32) OFASR_MFK(8, 32);
-    else OFASR_MFK(16, 16);
-#undef OFASR_MFK
-#undef OFASR_MF
+    dispatch_int<64, 32, 16>(tw, [&](auto TW) {                 // tiles of 256 pixels: 4x64, 8x32, 16x16
+        dispatch_int<7, 5, 3>(d->K, [&](auto KK) {
+            OFASR_LAUNCH((mb_fused_kernel<T, KK, 256 / TW, TW>), dim3((unsigned)blocks), dim3(MF_THREADS), 0, st, (const T*)x,
+                         (T*)out, (const T*)w1f, (const float*)b1, (const uint32_t*)taps, (const float*)b2, (const T*)w2f,
+                         (const float*)b3, (int)d->mid, (int)d->H, (int)d->W, tiles_x, tiles_y, d->residual, nsplit, part);
+        });
+    });
     rc = check_launch("ofasr_mbconv_infer");
     if (rc || nsplit == 1) return rc;
-#define OFASR_MFS(TH, TW)                                                                                              \
-    OFASR_LAUNCH((mb_fused_sum_kernel<T, TH, TW>), dim3((unsigned)(pl.tiles * 8)), dim3(256), 0, st, (const float*)part, \
-                 (const T*)x, (T*)out, (const float*)b3, (int)d->H, (int)d->W, tiles_x, tiles_y, d->residual, nsplit)
-    if (tw == 64) OFASR_MFS(4, 64);
-    else if (tw == 32) OFASR_MFS(8, 32);
-    else OFASR_MFS(16, 16);
-#undef OFASR_MFS
+    dispatch_int<64, 32, 16>(tw, [&](auto TW) {
+        OFASR_LAUNCH((mb_fused_sum_kernel<T, 256 / TW, TW>), dim3((unsigned)(pl.tiles * 8)), dim3(256), 0, st, (const float*)part,
+                     (const T*)x, (T*)out, (const float*)b3, (int)d->H, (int)d->W, tiles_x, tiles_y, d->residual, nsplit);
+    });
     return check_launch("ofasr_mbconv_infer");
 }
 
@@ -763,8 +751,7 @@ OFASR_EXPORT int ofasr_mbconv_infer_prepare(const ofasr_mbconv_desc* d, void* op
                               reinterpret_cast<float*>(ws + s.f), d->mid, stream);
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
-    if (d->dtype == OFASR_F16) return mf_fold<f16_t>(d, ws, s, st);
-    return mf_fold<bf16_t>(d, ws, s, st);
+    return dispatch_16bit(d->dtype, [&](auto t) { return mf_fold<typename decltype(t)::type>(d, ws, s, st); });
 }
 
 OFASR_EXPORT int ofasr_mbconv_infer_run(const ofasr_mbconv_desc* d, const void* x, void* out, const void* operands,
@@ -780,8 +767,9 @@ OFASR_EXPORT int ofasr_mbconv_infer_run(const ofasr_mbconv_desc* d, const void* 
                   "%s: scratch %zu B < required %zu B", name, scratch_bytes, s.total - s.part);
     hipStream_t st = as_stream(stream);
     char* ws = (char*)const_cast<void*>(operands);
-    if (d->dtype == OFASR_F16) return mf_run<f16_t>(d, x, out, ws, s, (float*)scratch, st);
-    return mf_run<bf16_t>(d, x, out, ws, s, (float*)scratch, st);
+    return dispatch_16bit(d->dtype, [&](auto t) {
+        return mf_run<typename decltype(t)::type>(d, x, out, ws, s, (float*)scratch, st);
+    });
 }
 
 OFASR_EXPORT int ofasr_mbconv_infer(const ofasr_mbconv_desc* d, const void* x, void* out, void* workspace,
@@ -790,8 +778,7 @@ OFASR_EXPORT int ofasr_mbconv_infer(const ofasr_mbconv_desc* d, const void* x, v
     int rc = mf_check(name, d);
     if (rc) return rc;
     const MfWs s = mf_ws(d);
-    OFASR_REQUIRE(workspace && workspace_bytes >= s.total, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  workspace_bytes, s.total);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, s.total);
     rc = ofasr_mbconv_infer_prepare(d, workspace, s.part, stream);
     if (rc) return rc;
     return ofasr_mbconv_infer_run(d, x, out, workspace, s.part, (char*)workspace + s.part, s.total - s.part, stream);

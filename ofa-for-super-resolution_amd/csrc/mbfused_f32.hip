@@ -302,7 +302,6 @@ __global__ void __launch_bounds__(MG_THREADS) mb_fused_f32_kernel(const float* _
     }
 }
 
-static size_t mg_align(size_t v) { return (v + 255) / 256 * 256; }
 struct MgWs {
     size_t f, w1f, b1, taps, w2f, b3, total;
 };
@@ -311,12 +310,12 @@ static MgWs mg_ws(const ofasr_mbconv_desc* d) {
     const int K = d->K;
     MgWs s;
     size_t o = 0;
-    s.f = o;    o += mg_align(mid * K * K * sizeof(float));
-    s.w1f = o;  o += mg_align(mid * 64 * sizeof(float));
-    s.b1 = o;   o += mg_align(mid * sizeof(float));
-    s.taps = o; o += mg_align(mid * ((K * K + 1 + 3) / 4 * 4) * sizeof(float));
-    s.w2f = o;  o += mg_align(64 * mid * sizeof(float));
-    s.b3 = o;   o += mg_align(64 * sizeof(float));
+    s.f = o;    o += align_up(mid * K * K * sizeof(float), 256);
+    s.w1f = o;  o += align_up(mid * 64 * sizeof(float), 256);
+    s.b1 = o;   o += align_up(mid * sizeof(float), 256);
+    s.taps = o; o += align_up(mid * ((K * K + 1 + 3) / 4 * 4) * sizeof(float), 256);
+    s.w2f = o;  o += align_up(64 * mid * sizeof(float), 256);
+    s.b3 = o;   o += align_up(64 * sizeof(float), 256);
     s.total = o;
     return s;
 }
@@ -406,12 +405,9 @@ OFASR_EXPORT int ofasr_mbconv_infer_f32_run(const ofasr_mbconv_desc* d, const vo
     const double px = (double)d->N * (double)d->H * (double)d->W;
     prof_note(4.0 * px * 64 * (d->residual ? 3.0 : 2.0), 2.0 * px * (2.0 * 64 * d->mid + (double)d->K * d->K * d->mid));
     hipStream_t st = as_stream(stream);
-#define OFASR_MG(KK)                                                                                                 \
-    OFASR_LAUNCH(mb_fused_f32_kernel<KK>, dim3((unsigned)blocks), dim3(MG_THREADS), 0, st, (const float*)x, (float*)out, \
-                 w1f, b1, taps, w2f, b3, (int)d->mid, (int)d->H, (int)d->W, tiles_x, tiles_y, d->residual)
-    if (d->K == 7) OFASR_MG(7);
-    else if (d->K == 5) OFASR_MG(5);
-    else OFASR_MG(3);
-#undef OFASR_MG
+    dispatch_int<7, 5, 3>(d->K, [&](auto KK) {
+        OFASR_LAUNCH(mb_fused_f32_kernel<KK>, dim3((unsigned)blocks), dim3(MG_THREADS), 0, st, (const float*)x, (float*)out, w1f,
+                     b1, taps, w2f, b3, (int)d->mid, (int)d->H, (int)d->W, tiles_x, tiles_y, d->residual);
+    });
     return check_launch(name);
 }

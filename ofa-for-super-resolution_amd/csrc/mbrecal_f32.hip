@@ -470,7 +470,6 @@ __global__ void __launch_bounds__(MR_THREADS) mb_recal_f32_kernel(const float* _
     wave_merge(0, 64, 64, 0);
 }
 
-static size_t mr_align(size_t v) { return (v + 255) / 256 * 256; }
 struct MrWs {
     size_t f, w1f, b1, taps, w2f, b3, stats, bn3, part, y3, total;
 };
@@ -480,16 +479,16 @@ static MrWs mr_ws(const ofasr_mbconv_desc* d) {
     const size_t blocks = (size_t)d->N * cdiv(d->H, MR_TILE) * cdiv(d->W, MR_TILE);
     MrWs s;
     size_t o = 0;
-    s.f = o;     o += mr_align(mid * K * K * sizeof(float));
-    s.w1f = o;   o += mr_align(mid * 64 * sizeof(float));
-    s.b1 = o;    o += mr_align(mid * sizeof(float));
-    s.taps = o;  o += mr_align(mid * ((K * K + 1 + 3) / 4 * 4) * sizeof(float));
-    s.w2f = o;   o += mr_align(64 * mid * sizeof(float));
-    s.b3 = o;    o += mr_align(64 * sizeof(float));
-    s.stats = o; o += mr_align(2 * 2 * mid * sizeof(float));       // mean | var of BN1, then of BN2
-    s.bn3 = o;   o += mr_align(4 * 64 * sizeof(float));            // mean | invstd | scale | shift of BN3
-    s.part = o;  o += mr_align(blocks * (mid > 64 ? mid : 64) * sizeof(float2));   // S3 writes 64 channels
-    s.y3 = o;    o += mr_align((size_t)d->N * 64 * d->H * d->W * sizeof(float));
+    s.f = o;     o += align_up(mid * K * K * sizeof(float), 256);
+    s.w1f = o;   o += align_up(mid * 64 * sizeof(float), 256);
+    s.b1 = o;    o += align_up(mid * sizeof(float), 256);
+    s.taps = o;  o += align_up(mid * ((K * K + 1 + 3) / 4 * 4) * sizeof(float), 256);
+    s.w2f = o;   o += align_up(64 * mid * sizeof(float), 256);
+    s.b3 = o;    o += align_up(64 * sizeof(float), 256);
+    s.stats = o; o += align_up(2 * 2 * mid * sizeof(float), 256);       // mean | var of BN1, then of BN2
+    s.bn3 = o;   o += align_up(4 * 64 * sizeof(float), 256);            // mean | invstd | scale | shift of BN3
+    s.part = o;  o += align_up(blocks * (mid > 64 ? mid : 64) * sizeof(float2), 256);   // S3 writes 64 channels
+    s.y3 = o;    o += align_up((size_t)d->N * 64 * d->H * d->W * sizeof(float), 256);
     s.total = o;
     return s;
 }
@@ -526,8 +525,7 @@ OFASR_EXPORT int ofasr_mbconv_recal_f32(const ofasr_mbconv_desc* d, const void* 
     OFASR_REQUIRE(d->ldw1 >= 64 && d->ldw2 >= d->mid && d->Cmid_max >= d->mid, OFASR_ERR_INVALID_ARG,
                   "%s: weight shapes smaller than the block", name);
     const MrWs s = mr_ws(d);
-    OFASR_REQUIRE(workspace && workspace_bytes >= s.total, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, s.total);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, s.total);
     char* ws = (char*)workspace;
     float* f = reinterpret_cast<float*>(ws + s.f);
     float* w1f = reinterpret_cast<float*>(ws + s.w1f);
@@ -567,28 +565,23 @@ OFASR_EXPORT int ofasr_mbconv_recal_f32(const ofasr_mbconv_desc* d, const void* 
                      C, H, W, tiles_x, tiles_y, o);
     };
     const double px = (double)d->N * H * W;
-#define OFASR_MR(KK)                                                                                                   \
-    do {                                                                                                               \
-        const double win = (double)MrGeom<KK>::NBLK * 32.0 / 256.0;                                                   \
-        fold(0);                                                                                                       \
-        prof_note(4.0 * px * 64, 2.0 * px * 64 * mid);                                                                 \
-        OFASR_LAUNCH((mb_recal_f32_kernel<KK, 1>), dim3((unsigned)blocks), dim3(MR_THREADS), 0, strm, (const float*)x,  \
-                     y3, part, w1f, b1, taps, w2f, mid, H, W, tiles_x, tiles_y);                                       \
-        merge(mid, acc1, st, st + mid, nullptr, nullptr, nullptr, 0);                                                  \
-        fold(1);                                                                                                       \
-        prof_note(4.0 * px * 64, 2.0 * px * (win * 64.0 * mid + (double)KK * KK * mid));                               \
-        OFASR_LAUNCH((mb_recal_f32_kernel<KK, 2>), dim3((unsigned)blocks), dim3(MR_THREADS), 0, strm, (const float*)x,  \
-                     y3, part, w1f, b1, taps, w2f, mid, H, W, tiles_x, tiles_y);                                       \
-        merge(mid, acc2, st + 2 * mid, st + 3 * mid, nullptr, nullptr, nullptr, 1);                                    \
-        fold(2);                                                                                                       \
-        prof_note(8.0 * px * 64, 2.0 * px * (win * 64.0 * mid + (double)KK * KK * mid + 64.0 * mid));                  \
-        OFASR_LAUNCH((mb_recal_f32_kernel<KK, 3>), dim3((unsigned)blocks), dim3(MR_THREADS), 0, strm, (const float*)x,  \
-                     y3, part, w1f, b1, taps, w2f, mid, H, W, tiles_x, tiles_y);                                       \
-    } while (0)
-    if (d->K == 7) OFASR_MR(7);
-    else if (d->K == 5) OFASR_MR(5);
-    else OFASR_MR(3);
-#undef OFASR_MR
+    dispatch_int<7, 5, 3>(d->K, [&](auto KK) {
+        const double win = (double)MrGeom<KK>::NBLK * 32.0 / 256.0;
+        fold(0);
+        prof_note(4.0 * px * 64, 2.0 * px * 64 * mid);
+        OFASR_LAUNCH((mb_recal_f32_kernel<KK, 1>), dim3((unsigned)blocks), dim3(MR_THREADS), 0, strm, (const float*)x, y3, part,
+                     w1f, b1, taps, w2f, mid, H, W, tiles_x, tiles_y);
+        merge(mid, acc1, st, st + mid, nullptr, nullptr, nullptr, 0);
+        fold(1);
+        prof_note(4.0 * px * 64, 2.0 * px * (win * 64.0 * mid + (double)KK * KK * mid));
+        OFASR_LAUNCH((mb_recal_f32_kernel<KK, 2>), dim3((unsigned)blocks), dim3(MR_THREADS), 0, strm, (const float*)x, y3, part,
+                     w1f, b1, taps, w2f, mid, H, W, tiles_x, tiles_y);
+        merge(mid, acc2, st + 2 * mid, st + 3 * mid, nullptr, nullptr, nullptr, 1);
+        fold(2);
+        prof_note(8.0 * px * 64, 2.0 * px * (win * 64.0 * mid + (double)KK * KK * mid + 64.0 * mid));
+        OFASR_LAUNCH((mb_recal_f32_kernel<KK, 3>), dim3((unsigned)blocks), dim3(MR_THREADS), 0, strm, (const float*)x, y3, part,
+                     w1f, b1, taps, w2f, mid, H, W, tiles_x, tiles_y);
+    });
     rc = check_launch(name);
     if (rc) return rc;
     merge(64, acc3, bn3, nullptr, bn3 + 64, bn3 + 128, bn3 + 192, 2);

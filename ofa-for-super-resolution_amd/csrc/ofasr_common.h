@@ -173,9 +173,17 @@ template <> struct uint_of<2> { using type = uint16_t; };
 template <> struct uint_of<4> { using type = uint32_t; };
 template <> struct uint_of<8> { using type = uint64_t; };
 
+// 4 consecutive elements as one vector access
+template <typename T> struct vec4;
+template <> struct vec4<float> { typedef float4 type; };
+template <> struct vec4<bf16_t> { typedef uint2 type; };
+template <> struct vec4<f16_t> { typedef uint2 type; };
+
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace ofasr
+// the host-side launch layer: dtype / bool / integer dispatch, environment switches, operand checks
+#include "launch.h"
 // the BatchNorm rules of the training path and the operand transforms (InputXf, BwdXf, BwdStatOut, BnFold, StatOut)
 #include "bn_math.h"
 namespace ofasr {

@@ -162,33 +162,23 @@ static int launch(const void* x, void* y, int64_t N, int64_t C, int64_t H, int64
     const int64_t total = N * C * r * r * H * W;
     if (total == 0) return OFASR_OK;
     prof_note(2.0 * (double)total * es, 0.0);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
-    if (r == 2 && (es == 2 || es == 4) && aligned && (W * es) % 16 == 0) {
+    if (r == 2 && (es == 2 || es == 4) && aligned16(x, y) && (W * es) % 16 == 0) {
         const int Wq = (int)(W * es / 16);
         const int64_t items = N * C * H * Wq;
         const int64_t blocks = cdiv(items, 256);
         const int grid = (int)(blocks < 65536 ? blocks : 65536);
-        if (es == 4)
-            OFASR_LAUNCH((ps_r2_kernel<4, SHUFFLE>), dim3(grid), dim3(256), 0, st, (const uint4*)x,
-                               (uint4*)y, items, (int)H, Wq);
-        else
-            OFASR_LAUNCH((ps_r2_kernel<2, SHUFFLE>), dim3(grid), dim3(256), 0, st, (const uint4*)x,
-                               (uint4*)y, items, (int)H, Wq);
+        dispatch_int<4, 2>(es, [&](auto ES) {
+            OFASR_LAUNCH((ps_r2_kernel<ES, SHUFFLE>), dim3(grid), dim3(256), 0, st, (const uint4*)x, (uint4*)y, items, (int)H, Wq);
+        });
         return check_launch(name);
     }
     const int64_t blocks = cdiv(total, 256);
     const int grid = (int)(blocks < 65536 ? blocks : 65536);
-#define OFASR_PS_GENERIC(ES)                                                                       \
-    OFASR_LAUNCH((ps_generic_kernel<typename uint_of<ES>::type, SHUFFLE>), dim3(grid), dim3(256), \
-                       0, st, (const typename uint_of<ES>::type*)x, (typename uint_of<ES>::type*)y,    \
-                       total, (int)C, (int)H, (int)W, r)
-    switch (es) {
-        case 1: OFASR_PS_GENERIC(1); break;
-        case 2: OFASR_PS_GENERIC(2); break;
-        case 4: OFASR_PS_GENERIC(4); break;
-        default: OFASR_PS_GENERIC(8); break;
-    }
-#undef OFASR_PS_GENERIC
+    dispatch_int<1, 2, 4, 8>(es, [&](auto ES) {
+        using U = typename uint_of<ES>::type;
+        OFASR_LAUNCH((ps_generic_kernel<U, SHUFFLE>), dim3(grid), dim3(256), 0, st, (const U*)x, (U*)y, total, (int)C, (int)H,
+                     (int)W, r);
+    });
     return check_launch(name);
 }
 
@@ -212,9 +202,8 @@ OFASR_EXPORT int ofasr_pixel_shuffle2_bn(const void* x, void* y, const float* st
     const char* name = "ofasr_pixel_shuffle2_bn";
     OFASR_REQUIRE(x && y && stats, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, OFASR_ERR_INVALID_ARG, "%s: bad shape", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit tensors only", name);
-    OFASR_REQUIRE(W % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
-                  OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit tensors only");
+    OFASR_REQUIRE(W % 8 == 0 && aligned16(x, y), OFASR_ERR_UNSUPPORTED, "%s: needs W %% 8 == 0 and 16-byte aligned tensors", name);
     OFASR_REQUIRE(C <= INT32_MAX / 4 && 2 * H <= INT32_MAX && 2 * W <= INT32_MAX, OFASR_ERR_UNSUPPORTED, "%s: too large", name);
     const int64_t Cin = 4 * C;
     const float *mean = stats, *scale = stats + 2 * Cin, *shift = stats + 3 * Cin;
@@ -224,11 +213,9 @@ OFASR_EXPORT int ofasr_pixel_shuffle2_bn(const void* x, void* y, const float* st
     const int grid = (int)(blocks < 65536 ? blocks : 65536);
     hipStream_t st = as_stream(stream);
     prof_note(2.0 * 2.0 * (double)N * (double)Cin * (double)H * (double)W, 0.0);
-    if (dtype == OFASR_BF16)
-        OFASR_LAUNCH((ps_r2_bn_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const uint4*)x, (uint4*)y, mean, scale, shift, items,
-                     (int)C, (int)H, Wq);
-    else
-        OFASR_LAUNCH((ps_r2_bn_kernel<f16_t>), dim3(grid), dim3(256), 0, st, (const uint4*)x, (uint4*)y, mean, scale, shift, items,
-                     (int)C, (int)H, Wq);
+    dispatch_16bit(dtype, [&](auto t) {
+        OFASR_LAUNCH((ps_r2_bn_kernel<typename decltype(t)::type>), dim3(grid), dim3(256), 0, st, (const uint4*)x, (uint4*)y, mean,
+                     scale, shift, items, (int)C, (int)H, Wq);
+    });
     return check_launch(name);
 }

@@ -1734,9 +1734,9 @@ static WdPlan wd_plan(int64_t N, int64_t Cin, int64_t Cout, int64_t HW) {
     p.quads_per_img = (int)cdiv(HW, 64);
     p.total_quads = (int)(N * p.quads_per_img);
     const int64_t tiles = cdiv(p.MR, WD_ROWS) * cdiv(p.NS, WD_COLS);
-    static const int blocks = [] { const char* e = getenv("OFASR_PW_WGRAD_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+    static const int blocks = env_positive_int("OFASR_PW_WGRAD_BLOCKS", 256);
     // OFASR_PW_WGRAD_STREAM=0: the per-lane-load body for every shape (A/B runs)
-    static const bool stream_on = [] { const char* e = getenv("OFASR_PW_WGRAD_STREAM"); return !(e && e[0] == '0'); }();
+    static const bool stream_on = env_default_on("OFASR_PW_WGRAD_STREAM");
     p.stream = stream_on && ws_shape_ok(p.NS, HW) ? 1 : 0;
     p.pairs = 0;
     if (p.stream) {
@@ -1850,7 +1850,7 @@ __global__ void __launch_bounds__(512) pw_wgrad_direct_f32_kernel(const float* _
 }
 
 static bool wgrad_f32_direct_on() {
-    static const bool on = [] { const char* e = getenv("OFASR_PW_WGRAD_F32_DIRECT"); return e && e[0] == '1'; }();
+    static const bool on = env_default_off("OFASR_PW_WGRAD_F32_DIRECT");
     return on;
 }
 
@@ -1891,8 +1891,14 @@ static WgradPlan wgrad_plan(int64_t N, int64_t Cin, int64_t Cout, int64_t HW, in
 }
 
 static bool aligned_for(const void* a, const void* b, int64_t HW, bool is16) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
-    return (bits & 15) == 0 && (HW % (is16 ? 8 : 4)) == 0;
+    return aligned16(a, b) && (HW % (is16 ? 8 : 4)) == 0;
+}
+
+// OFASR_PW_FANIN_FAST=0: the pipelined fan-in kernel without its 32-bit-offset fast path (and no fused BN backward in the
+// expand input gradient, which only that path implements).  One reader for the launch and for pwconv_dgrad_bx_supported.
+static bool pw_fanin_fast_on() {
+    static const bool on = env_default_on("OFASR_PW_FANIN_FAST");
+    return on;
 }
 
 template <typename T, bool AL, bool WV, bool XF = false>
@@ -1902,17 +1908,17 @@ static void launch_gemm_v(const void* x, WView wv, void* y, int64_t HW, int tile
     if (wv.K <= 64) {
         if constexpr (Elem<T>::is16 && AL && WV && !XF) {
             // one block per pixel tile walking the row slabs (OFASR_PW_FANOUT_SLABS=0: per-slab grid)
-            static const bool slabs = [] { const char* e = getenv("OFASR_PW_FANOUT_SLABS"); return !(e && e[0] == '0'); }();
+            static const bool slabs = env_default_on("OFASR_PW_FANOUT_SLABS");
             const int nslab = wv.M / FO_ROWS;
             if (slabs && addend == nullptr && wv.K == 64 && wv.M % FO_ROWS == 0 && (nslab == 2 || nslab == 3) &&
                 HW % PW_TILE == 0) {
                 dim3 g1((unsigned)total_tiles);
-#define OFASR_FO_SLABS(NS, ST)                                                                                       \
-    OFASR_LAUNCH((pw_fanout_slabs_kernel<T, NS, ST>), g1, dim3(PW_THREADS), 0, st, (const T*)x, wv, (T*)y, (int)HW, \
-                       tiles_per_img, so, BwdStatOut{})
-                if (nslab == 3) { if (so.partial) OFASR_FO_SLABS(3, 1); else OFASR_FO_SLABS(3, 0); }
-                else { if (so.partial) OFASR_FO_SLABS(2, 1); else OFASR_FO_SLABS(2, 0); }
-#undef OFASR_FO_SLABS
+                dispatch_int<3, 2>(nslab, [&](auto NS) {
+                    dispatch_int<1, 0>(so.partial ? 1 : 0, [&](auto ST) {
+                        OFASR_LAUNCH((pw_fanout_slabs_kernel<T, NS, ST>), g1, dim3(PW_THREADS), 0, st, (const T*)x, wv, (T*)y,
+                                     (int)HW, tiles_per_img, so, BwdStatOut{});
+                    });
+                });
                 return;
             }
         }
@@ -1922,15 +1928,12 @@ static void launch_gemm_v(const void* x, WView wv, void* y, int64_t HW, int tile
     } else {
         dim3 grid((unsigned)total_tiles, (unsigned)cdiv(wv.M, 64));
         if constexpr (Elem<T>::is16 && AL && WV) {
-            static const bool fast_ok = [] { const char* e = getenv("OFASR_PW_FANIN_FAST"); return !(e && e[0] == '0'); }();
             const bool span32 = (long long)wv.K * HW < (1LL << 31) &&
                                 (long long)wv.M * wv.sm + (long long)wv.K * wv.sk < (1LL << 31);   // 32-bit lane offsets
-            if (fast_ok && wv.K % 4 == 0 && wv.M % 4 == 0 && span32)
-                OFASR_LAUNCH((pw_fanin_pipe_kernel<T, XF, true>), grid, dim3(PW_THREADS), 0, st, (const T*)x, wv,
-                                   (T*)y, (int)HW, tiles_per_img, (int)cdiv(wv.K, 64), xf, (const T*)addend, so, fold);
-            else
-                OFASR_LAUNCH((pw_fanin_pipe_kernel<T, XF, false>), grid, dim3(PW_THREADS), 0, st, (const T*)x, wv,
-                                   (T*)y, (int)HW, tiles_per_img, (int)cdiv(wv.K, 64), xf, (const T*)addend, so, fold);
+            dispatch_bool(pw_fanin_fast_on() && wv.K % 4 == 0 && wv.M % 4 == 0 && span32, [&](auto FAST) {
+                OFASR_LAUNCH((pw_fanin_pipe_kernel<T, XF, FAST>), grid, dim3(PW_THREADS), 0, st, (const T*)x, wv, (T*)y, (int)HW,
+                             tiles_per_img, (int)cdiv(wv.K, 64), xf, (const T*)addend, so, fold);
+            });
             return;
         }
         OFASR_LAUNCH((pw_fanin_kernel<T, AL, WV, XF>), grid, dim3(PW_THREADS), 0, st, (const T*)x, wv, (T*)y,
@@ -1946,7 +1949,7 @@ static int launch_gemm(const char* name, const void* x, WView wv, void* y, int64
     const bool al = aligned_for(x, y, HW, is16);
     const long long ld = wv.sk == 1 ? wv.sm : wv.sk;
     // vector weight staging: 16-byte aligned rows AND K, M multiples of 4, so that a chunk never straddles the slice
-    const bool wvec = (reinterpret_cast<uintptr_t>(wv.w) & 15) == 0 && (ld % 4) == 0 && wv.K % 4 == 0 && wv.M % 4 == 0;
+    const bool wvec = aligned16(wv.w) && (ld % 4) == 0 && wv.K % 4 == 0 && wv.M % 4 == 0;
     const int tiles_per_img = (int)cdiv(HW, PW_TILE);
     const int64_t total64 = N * tiles_per_img;
     OFASR_REQUIRE(total64 <= INT32_MAX, OFASR_ERR_UNSUPPORTED, "%s: too many pixel tiles", name);
@@ -1967,22 +1970,20 @@ static int launch_gemm(const char* name, const void* x, WView wv, void* y, int64
         else launch_gemm_v<T, true, false, true>(x, wv, y, HW, tiles_per_img, total_tiles, st, xf, nullptr, so);
         return check_launch(name);
     }
-    const bool al2 = al && (addend == nullptr || (reinterpret_cast<uintptr_t>(addend) & 15) == 0);
-    if (al2 && wvec) launch_gemm_v<T, true, true>(x, wv, y, HW, tiles_per_img, total_tiles, st, InputXf{}, addend, so);
-    else if (al2) launch_gemm_v<T, true, false>(x, wv, y, HW, tiles_per_img, total_tiles, st, InputXf{}, addend, so);
-    else if (wvec) launch_gemm_v<T, false, true>(x, wv, y, HW, tiles_per_img, total_tiles, st, InputXf{}, addend, so);
-    else launch_gemm_v<T, false, false>(x, wv, y, HW, tiles_per_img, total_tiles, st, InputXf{}, addend, so);
+    dispatch_bool(al && aligned16(addend), [&](auto AL) {
+        dispatch_bool(wvec, [&](auto WV) {
+            launch_gemm_v<T, AL, WV>(x, wv, y, HW, tiles_per_img, total_tiles, st, InputXf{}, addend, so);
+        });
+    });
     return check_launch(name);
 }
 
 static int gemm_entry(const char* name, const void* x, WView wv, void* y, int64_t N, int64_t HW, int dtype,
                       void* stream, const void* addend = nullptr, StatOut so = StatOut{nullptr, 0}) {
     hipStream_t st = as_stream(stream);
-    switch (dtype) {
-        case OFASR_F32: return launch_gemm<float>(name, x, wv, y, N, HW, st, InputXf{}, addend, so);
-        case OFASR_F16: return launch_gemm<f16_t>(name, x, wv, y, N, HW, st, InputXf{}, addend, so);
-        default: return launch_gemm<bf16_t>(name, x, wv, y, N, HW, st, InputXf{}, addend, so);
-    }
+    return dispatch_float(dtype, [&](auto t) {
+        return launch_gemm<typename decltype(t)::type>(name, x, wv, y, N, HW, st, InputXf{}, addend, so);
+    });
 }
 
 static int check_pw_args(const char* name, const void* a, const void* b, const void* c, int64_t ldw, int64_t N,
@@ -1992,8 +1993,7 @@ static int check_pw_args(const char* name, const void* a, const void* b, const v
                   "%s: bad shape N=%lld Cin=%lld Cout=%lld HW=%lld", name, (long long)N, (long long)Cin,
                   (long long)Cout, (long long)HW);
     OFASR_REQUIRE(ldw >= Cin, OFASR_ERR_INVALID_ARG, "%s: ldw=%lld < Cin=%lld", name, (long long)ldw, (long long)Cin);
-    OFASR_REQUIRE(dtype == OFASR_F32 || dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_INVALID_ARG,
-                  "%s: bad dtype %d", name, dtype);
+    OFASR_REQUIRE(is_float_dtype(dtype), OFASR_ERR_INVALID_ARG, "%s: bad dtype %d", name, dtype);
     OFASR_REQUIRE(Cin <= 65536 && Cout <= 65536 && HW <= (1 << 30) && N <= (1 << 24), OFASR_ERR_UNSUPPORTED,
                   "%s: dimension too large", name);
     return OFASR_OK;
@@ -2022,12 +2022,9 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
             dim3 grid((unsigned)(wp.pairs ? wp.nsplit / 2 : wp.nsplit), (unsigned)cdiv(wp.MR, wp.stream ? WS_ROWS : WD_ROWS),
                       (unsigned)cdiv(wp.NS, WD_COLS));
             if constexpr (XF) {
-                if (big_is_dy)   // x is the S operand
-                    OFASR_LAUNCH((pw_wgrad_direct_kernel<T, 2>), grid, dim3(512), 0, st, R, S, ws, wp.MR, wp.NS,
-                                       (int)HW, wp, xf);
-                else
-                    OFASR_LAUNCH((pw_wgrad_direct_kernel<T, 1>), grid, dim3(512), 0, st, R, S, ws, wp.MR, wp.NS,
-                                       (int)HW, wp, xf);
+                dispatch_int<2, 1>(big_is_dy ? 2 : 1, [&](auto XOP) {   // 2: x is the S operand
+                    OFASR_LAUNCH((pw_wgrad_direct_kernel<T, XOP>), grid, dim3(512), 0, st, R, S, ws, wp.MR, wp.NS, (int)HW, wp, xf);
+                });
             } else if constexpr (BXM) {
                 if (!big_is_dy) {
                     set_error("%s: the fused BN backward is implemented for the wide gradient operand (Cout >= Cin)", name);
@@ -2069,12 +2066,10 @@ static int launch_wgrad(const char* name, const void* dy, const void* x, float* 
         }
     }
     dim3 grid((unsigned)cdiv(p.MR, 64), (unsigned)cdiv(p.NS, 64), (unsigned)p.nsplit);
-    if (al)
-        OFASR_LAUNCH((pw_wgrad_kernel<T, true>), grid, dim3(PW_THREADS), 0, st, R, S, ws, p.MR, p.NS, (int)HW,
-                           p.stages_per_img, p.total_stages, p.stages_per_split);
-    else
-        OFASR_LAUNCH((pw_wgrad_kernel<T, false>), grid, dim3(PW_THREADS), 0, st, R, S, ws, p.MR, p.NS, (int)HW,
-                           p.stages_per_img, p.total_stages, p.stages_per_split);
+    dispatch_bool(al, [&](auto AL) {
+        OFASR_LAUNCH((pw_wgrad_kernel<T, AL>), grid, dim3(PW_THREADS), 0, st, R, S, ws, p.MR, p.NS, (int)HW, p.stages_per_img,
+                     p.total_stages, p.stages_per_split);
+    });
     int rc = check_launch(name);
     if (rc) return rc;
     const long long tot = (long long)p.MR * p.NS;
@@ -2098,11 +2093,9 @@ int pwconv_dgrad_add(const void* dy, const float* w, int64_t ldw, void* dx, cons
 // Only the pipelined fan-in kernel implements it: 16-bit, aligned, 64 < Cout <= FOLD_KMAX, vector-loadable weight slice.
 bool pwconv_dgrad_bx_supported(const void* da, const void* y, const void* dx, const void* addend, const float* w,
                                int64_t ldw, int64_t Cin, int64_t Cout, int64_t HW, int dtype) {
-    if (dtype != OFASR_F16 && dtype != OFASR_BF16) return false;
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(da) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dx) |
-                           reinterpret_cast<uintptr_t>(addend) | reinterpret_cast<uintptr_t>(w);   // dy_out: checked by the caller
-    static const bool fast_ok = [] { const char* e = getenv("OFASR_PW_FANIN_FAST"); return !(e && e[0] == '0'); }();
-    return fast_ok && (bits & 15) == 0 && HW % 8 == 0 && ldw % 4 == 0 && Cin % 4 == 0 && Cout % 4 == 0 && Cout > 64 &&
+    if (!is_16bit(dtype)) return false;
+    // dy_out: checked by the caller
+    return pw_fanin_fast_on() && aligned16(da, y, dx, addend, w) && HW % 8 == 0 && ldw % 4 == 0 && Cin % 4 == 0 && Cout % 4 == 0 && Cout > 64 &&
            Cout <= FOLD_KMAX && Cout * HW < (1LL << 31) && (Cin + Cout) * ldw < (1LL << 31);   // 32-bit lane offsets
 }
 
@@ -2135,21 +2128,21 @@ int pwconv_dgrad_add_bx(const void* da, const float* w, int64_t ldw, void* dx, c
     if (N * HW == 0) return OFASR_OK;
     WView wv{w, 1, ldw, (int)Cin, (int)Cout};   // dgrad: M = Cin rows of W^T, K = Cout
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16) return launch_dgrad_bx<f16_t>(name, da, wv, dx, addend, N, HW, bx, st);
-    return launch_dgrad_bx<bf16_t>(name, da, wv, dx, addend, N, HW, bx, st);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_dgrad_bx<typename decltype(t)::type>(name, da, wv, dx, addend, N, HW, bx, st);
+    });
 }
 
 bool pwconv_xf_supported(const void* x, const void* y, int64_t HW, int dtype) {
-    return (dtype == OFASR_F16 || dtype == OFASR_BF16) && aligned_for(x, y, HW, true);
+    return is_16bit(dtype) && aligned_for(x, y, HW, true);
 }
 
 // project-conv input gradient da2 = W2^T dy3 that also leaves the BN2-backward sums of what it writes (BwdStatOut):
 // the slab-walk kernel only (16-bit, aligned, vector weights, 64 gradient channels in, 256 / 384 out, HW % 128 == 0)
 bool pwconv_dgrad_bstat_supported(const void* dy, const void* y, const void* dx, const float* w, int64_t ldw, int64_t Cin,
                                   int64_t Cout, int64_t HW, int dtype) {
-    const bool wvec = (reinterpret_cast<uintptr_t>(w) & 15) == 0 && (ldw % 4) == 0;
-    return (dtype == OFASR_F16 || dtype == OFASR_BF16) && aligned_for(dy, dx, HW, true) &&
-           (reinterpret_cast<uintptr_t>(y) & 15) == 0 && wvec && Cout == 64 && (Cin == 2 * FO_ROWS || Cin == 3 * FO_ROWS) &&
+    const bool wvec = aligned16(w) && (ldw % 4) == 0;
+    return is_16bit(dtype) && aligned_for(dy, dx, HW, true) && aligned16(y) && wvec && Cout == 64 && (Cin == 2 * FO_ROWS || Cin == 3 * FO_ROWS) &&
            HW % PW_TILE == 0;
 }
 
@@ -2159,12 +2152,10 @@ static int launch_dgrad_bstat(const void* dy, WView wv, void* dx, int64_t N, int
     const int total_tiles = (int)(N * tiles_per_img);
     const double px = (double)N * (double)HW;
     prof_note(2.0 * px * (wv.K + 2.0 * wv.M) + 4.0 * wv.K * wv.M, 2.0 * px * wv.K * wv.M);
-    if (wv.M == 3 * FO_ROWS)
-        OFASR_LAUNCH((pw_fanout_slabs_kernel<T, 3, 2>), dim3((unsigned)total_tiles), dim3(PW_THREADS), 0, st, (const T*)dy, wv,
+    dispatch_int<3, 2>(wv.M / FO_ROWS, [&](auto NS) {
+        OFASR_LAUNCH((pw_fanout_slabs_kernel<T, NS, 2>), dim3((unsigned)total_tiles), dim3(PW_THREADS), 0, st, (const T*)dy, wv,
                      (T*)dx, (int)HW, tiles_per_img, StatOut{nullptr, 0}, bs);
-    else
-        OFASR_LAUNCH((pw_fanout_slabs_kernel<T, 2, 2>), dim3((unsigned)total_tiles), dim3(PW_THREADS), 0, st, (const T*)dy, wv,
-                     (T*)dx, (int)HW, tiles_per_img, StatOut{nullptr, 0}, bs);
+    });
     return check_launch("pwconv_dgrad_bstat");
 }
 
@@ -2180,8 +2171,7 @@ int pwconv_dgrad_bstat(const void* dy, const float* w, int64_t ldw, void* dx, in
                   "%s: unit count %d does not match the launch", name, bs.P);
     WView wv{w, 1, ldw, (int)Cin, (int)Cout};  // rows = input channels, reduction over output channels
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16) return launch_dgrad_bstat<f16_t>(dy, wv, dx, N, HW, bs, st);
-    return launch_dgrad_bstat<bf16_t>(dy, wv, dx, N, HW, bs, st);
+    return dispatch_16bit(dtype, [&](auto t) { return launch_dgrad_bstat<typename decltype(t)::type>(dy, wv, dx, N, HW, bs, st); });
 }
 
 int pwconv_stat_units(int64_t N, int64_t Cin, int64_t HW) {
@@ -2200,7 +2190,7 @@ int pwconv_fwd_stat(const void* x, const float* w, int64_t ldw, void* y, int64_t
 }
 
 bool pwconv_fold_supported(const void* x, const void* y, const float* w, int64_t ldw, int64_t Cin, int64_t HW, int dtype) {
-    const bool wvec = (reinterpret_cast<uintptr_t>(w) & 15) == 0 && (ldw % 4) == 0;
+    const bool wvec = aligned16(w) && (ldw % 4) == 0;
     return pwconv_xf_supported(x, y, HW, dtype) && wvec && Cin > 64 && Cin <= FOLD_KMAX && Cin % 4 == 0;
 }
 
@@ -2211,12 +2201,13 @@ int pwconv_fwd_fold(const void* x, const float* w, int64_t ldw, void* y, int64_t
     if (rc) return rc;
     OFASR_REQUIRE(fold.cp && fold.P > 0 && fold.mean && fold.invstd && fold.scale && fold.shift, OFASR_ERR_INVALID_ARG,
                   "%s: incomplete statistics source", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit only");
     OFASR_REQUIRE(N * HW > 0, OFASR_ERR_UNSUPPORTED, "%s: empty tensor", name);
     WView wv{w, ldw, 1, (int)Cout, (int)Cin};
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16) return launch_gemm<f16_t, true>(name, x, wv, y, N, HW, st, InputXf{}, nullptr, so, fold);
-    return launch_gemm<bf16_t, true>(name, x, wv, y, N, HW, st, InputXf{}, nullptr, so, fold);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_gemm<typename decltype(t)::type, true>(name, x, wv, y, N, HW, st, InputXf{}, nullptr, so, fold);
+    });
 }
 
 int pwconv_fwd_xf(const void* x, const float* w, int64_t ldw, void* y, int64_t N, int64_t Cin, int64_t Cout, int64_t HW,
@@ -2225,12 +2216,13 @@ int pwconv_fwd_xf(const void* x, const float* w, int64_t ldw, void* y, int64_t N
     int rc = check_pw_args(name, x, w, y, ldw, N, Cin, Cout, HW, dtype);
     if (rc) return rc;
     OFASR_REQUIRE(xf.scale && xf.shift && xf.mean, OFASR_ERR_INVALID_ARG, "%s: null transform", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit only");
     if (N * HW == 0) return OFASR_OK;
     WView wv{w, ldw, 1, (int)Cout, (int)Cin};
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16) return launch_gemm<f16_t, true>(name, x, wv, y, N, HW, st, xf, nullptr, so);
-    return launch_gemm<bf16_t, true>(name, x, wv, y, N, HW, st, xf, nullptr, so);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_gemm<typename decltype(t)::type, true>(name, x, wv, y, N, HW, st, xf, nullptr, so);
+    });
 }
 
 int pwconv_wgrad_xf(const void* dy, const void* x, float* dw, int64_t ldw, int64_t N, int64_t Cin, int64_t Cout,
@@ -2239,19 +2231,18 @@ int pwconv_wgrad_xf(const void* dy, const void* x, float* dw, int64_t ldw, int64
     int rc = check_pw_args(name, dy, x, dw, ldw, N, Cin, Cout, HW, dtype);
     if (rc) return rc;
     OFASR_REQUIRE(xf.scale && xf.shift && xf.mean, OFASR_ERR_INVALID_ARG, "%s: null transform", name);
-    OFASR_REQUIRE(dtype == OFASR_F16 || dtype == OFASR_BF16, OFASR_ERR_UNSUPPORTED, "%s: 16-bit only", name);
+    OFASR_REQUIRE_16BIT(dtype, "16-bit only");
     OFASR_REQUIRE(N * HW > 0, OFASR_ERR_UNSUPPORTED, "%s: empty tensor", name);
     const size_t need = ofasr_pwconv_wgrad_workspace(N, Cin, Cout, HW);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16)
-        return launch_wgrad<f16_t, true>(name, dy, x, dw, ldw, N, Cin, Cout, HW, (float*)workspace, st, xf);
-    return launch_wgrad<bf16_t, true>(name, dy, x, dw, ldw, N, Cin, Cout, HW, (float*)workspace, st, xf);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_wgrad<typename decltype(t)::type, true>(name, dy, x, dw, ldw, N, Cin, Cout, HW, (float*)workspace, st, xf);
+    });
 }
 
 bool pwconv_wgrad_bx_supported(const void* da, const void* y, const void* x, int64_t Cin, int64_t Cout, int64_t HW, int dtype) {
-    if (!(dtype == OFASR_F16 || dtype == OFASR_BF16) || Cout < Cin) return false;
+    if (!is_16bit(dtype) || Cout < Cin) return false;
     return aligned_for(da, x, HW, true) && aligned_for(y, x, HW, true);
 }
 
@@ -2266,12 +2257,12 @@ int pwconv_wgrad_bx(const void* da, const void* x, float* dw, int64_t ldw, int64
                   "%s: needs 16-bit aligned tensors and Cout >= Cin", name);
     OFASR_REQUIRE(N * HW > 0, OFASR_ERR_UNSUPPORTED, "%s: empty tensor", name);
     const size_t need = ofasr_pwconv_wgrad_workspace(N, Cin, Cout, HW);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    if (dtype == OFASR_F16)
-        return launch_wgrad<f16_t, false, true>(name, da, x, dw, ldw, N, Cin, Cout, HW, (float*)workspace, st, InputXf{}, bx);
-    return launch_wgrad<bf16_t, false, true>(name, da, x, dw, ldw, N, Cin, Cout, HW, (float*)workspace, st, InputXf{}, bx);
+    return dispatch_16bit(dtype, [&](auto t) {
+        return launch_wgrad<typename decltype(t)::type, false, true>(name, da, x, dw, ldw, N, Cin, Cout, HW, (float*)workspace, st,
+                                                                     InputXf{}, bx);
+    });
 }
 
 }  // namespace ofasr
@@ -2336,13 +2327,10 @@ OFASR_EXPORT int ofasr_pwconv_wgrad(const void* dy, const void* x, float* dw, in
         return OFASR_OK;
     }
     const size_t need = ofasr_pwconv_wgrad_workspace(N, Cin, Cout, HW);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B",
-                  name, workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     float* ws = (float*)workspace;
-    switch (dtype) {
-        case OFASR_F32: return launch_wgrad<float>(name, dy, x, dw, ldw, N, Cin, Cout, HW, ws, st);
-        case OFASR_F16: return launch_wgrad<f16_t>(name, dy, x, dw, ldw, N, Cin, Cout, HW, ws, st);
-        default: return launch_wgrad<bf16_t>(name, dy, x, dw, ldw, N, Cin, Cout, HW, ws, st);
-    }
+    return dispatch_float(dtype, [&](auto t) {
+        return launch_wgrad<typename decltype(t)::type>(name, dy, x, dw, ldw, N, Cin, Cout, HW, ws, st);
+    });
 }
 

@@ -255,13 +255,11 @@ static void q_mse_launch(const void* a, const void* b, int64_t N, int64_t elems,
 template <typename TA>
 static void q_mse_b(const void* a, const void* b, int fmt_b, int64_t N, int64_t elems, double* mse, double* part,
                     hipStream_t st) {
-    if (fmt_b == OFASR_F32) q_mse_launch<TA, float>(a, b, N, elems, mse, part, st);
-    else if (fmt_b == OFASR_BF16) q_mse_launch<TA, bf16_t>(a, b, N, elems, mse, part, st);
-    else q_mse_launch<TA, f16_t>(a, b, N, elems, mse, part, st);
+    dispatch_float(fmt_b, [&](auto tb) { q_mse_launch<TA, typename decltype(tb)::type>(a, b, N, elems, mse, part, st); });
 }
 
-static bool q_fmt_ok(int f) { return f == OFASR_F32 || f == OFASR_F16 || f == OFASR_BF16 || f == OFASR_U8_HWC; }
-static double q_fmt_bytes(int f) { return f == OFASR_F32 ? 4.0 : (f == OFASR_U8_HWC ? 1.0 : 2.0); }
+static bool q_fmt_ok(int f) { return is_float_dtype(f) || f == OFASR_U8_HWC; }
+static double q_fmt_bytes(int f) { return f == OFASR_U8_HWC ? 1.0 : (double)elem_bytes(f); }
 
 // 0 unless the shape is one ofasr_quality_y accepts
 static int64_t q_tiles(int64_t N, int64_t H, int64_t W, int64_t shave, int64_t* ty, int64_t* tx) {
@@ -302,7 +300,7 @@ OFASR_EXPORT int ofasr_quality_y(const void* a, int fmt_a, const void* b, int fm
     OFASR_REQUIRE(N <= 65535 && ty <= 65535 && H <= (1LL << 40) / W, OFASR_ERR_UNSUPPORTED,
                   "%s: too many images or too large an image", name);
     const size_t need = (size_t)(tiles * N) * sizeof(QPartial);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+    OFASR_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
                   OFASR_ERR_WORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", name, need,
                   workspace_bytes);
     QGauss G;
@@ -339,8 +337,6 @@ OFASR_EXPORT int ofasr_quality_mse(const void* a, int fmt_a, const void* b, int 
     hipStream_t st = as_stream(stream);
     const double eb = q_fmt_bytes(fmt_a) + q_fmt_bytes(fmt_b);
     prof_note((double)N * (double)elems * eb, 0.0);
-    if (fmt_a == OFASR_F32) q_mse_b<float>(a, b, fmt_b, N, elems, mse, (double*)workspace, st);
-    else if (fmt_a == OFASR_BF16) q_mse_b<bf16_t>(a, b, fmt_b, N, elems, mse, (double*)workspace, st);
-    else q_mse_b<f16_t>(a, b, fmt_b, N, elems, mse, (double*)workspace, st);
+    dispatch_float(fmt_a, [&](auto ta) { q_mse_b<typename decltype(ta)::type>(a, b, fmt_b, N, elems, mse, (double*)workspace, st); });
     return check_launch(name);
 }

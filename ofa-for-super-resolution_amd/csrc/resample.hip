@@ -111,7 +111,6 @@ static int rs_ksize(int64_t in_size, int64_t out_size) {
     if ((double)c < support) ++c;   // ceil
     return 2 * c + 1;
 }
-static size_t rs_align(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace ofasr
 
@@ -120,9 +119,9 @@ using namespace ofasr;
 OFASR_EXPORT size_t ofasr_bicubic_resize_u8_workspace(int64_t planes, int64_t in_h, int64_t in_w, int64_t out_h,
                                                       int64_t out_w) {
     if (planes <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) return 0;
-    const size_t tw = rs_align((size_t)out_w * (2 + rs_ksize(in_w, out_w)) * sizeof(int));
-    const size_t th = rs_align((size_t)out_h * (2 + rs_ksize(in_h, out_h)) * sizeof(int));
-    return tw + th + rs_align((size_t)planes * in_h * out_w);
+    const size_t tw = align_up((size_t)out_w * (2 + rs_ksize(in_w, out_w)) * sizeof(int), 256);
+    const size_t th = align_up((size_t)out_h * (2 + rs_ksize(in_h, out_h)) * sizeof(int), 256);
+    return tw + th + align_up((size_t)planes * in_h * out_w, 256);
 }
 
 OFASR_EXPORT int ofasr_bicubic_resize_u8(const void* src, void* dst, int64_t planes, int64_t in_h, int64_t in_w,
@@ -135,14 +134,13 @@ OFASR_EXPORT int ofasr_bicubic_resize_u8(const void* src, void* dst, int64_t pla
     const int kw = rs_ksize(in_w, out_w), kh = rs_ksize(in_h, out_h);
     OFASR_REQUIRE(kw <= RS_KMAX && kh <= RS_KMAX, OFASR_ERR_UNSUPPORTED, "%s: down-scale factor above 8 not supported", name);
     const size_t need = ofasr_bicubic_resize_u8_workspace(planes, in_h, in_w, out_h, out_w);
-    OFASR_REQUIRE(workspace && workspace_bytes >= need, OFASR_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", name,
-                  workspace_bytes, need);
+    OFASR_REQUIRE_WORKSPACE(workspace, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     char* ws = (char*)workspace;
     int* tw = (int*)ws;
-    const size_t tw_bytes = rs_align((size_t)out_w * (2 + kw) * sizeof(int));
+    const size_t tw_bytes = align_up((size_t)out_w * (2 + kw) * sizeof(int), 256);
     int* th = (int*)(ws + tw_bytes);
-    const size_t th_bytes = rs_align((size_t)out_h * (2 + kh) * sizeof(int));
+    const size_t th_bytes = align_up((size_t)out_h * (2 + kh) * sizeof(int), 256);
     uint8_t* mid = (uint8_t*)(ws + tw_bytes + th_bytes);
     OFASR_LAUNCH(rs_coeff_kernel, dim3((unsigned)cdiv(out_w, 64)), dim3(64), 0, st, tw, (int)in_w, (int)out_w, kw);
     OFASR_LAUNCH(rs_coeff_kernel, dim3((unsigned)cdiv(out_h, 64)), dim3(64), 0, st, th, (int)in_h, (int)out_h, kh);

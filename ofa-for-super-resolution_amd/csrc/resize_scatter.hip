@@ -161,7 +161,7 @@ static int rsz_dispatch(const char* name, const void* src, int64_t n, int64_t sh
     OFASR_REQUIRE(src && table && vtab && htab, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && TH > 0 && TW > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG,
                   "%s: non-positive size", name);
-    TILE_REQUIRE_DTYPE(dtype);
+    OFASR_REQUIRE_DTYPE(dtype);
     OFASR_REQUIRE(kh >= 1 && kw >= 1, OFASR_ERR_INVALID_ARG, "%s: a coefficient table without taps", name);
     OFASR_REQUIRE(kh <= RS_TAPS && kw <= RS_TAPS, OFASR_ERR_UNSUPPORTED,
                   "%s: %d x %d taps; at most %d per axis (lanczos at a 4 : 1 reduction)", name, kh, kw, RS_TAPS);

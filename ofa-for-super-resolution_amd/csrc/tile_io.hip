@@ -129,12 +129,10 @@ static void tio_gather(const void* img, int64_t H, int64_t W, const int64_t* ori
     const bool vec = w % 4 == 0 && reinterpret_cast<uintptr_t>(out) % al == 0;
     const dim3 grid(grid_blocks(h * cdiv(w, 4)), (unsigned)n);
     prof_note((double)n * (double)(h * w) * (3.0 + 3.0 * sizeof(T)), 0.0);
-    if (vec)
-        OFASR_LAUNCH((tile_gather_u8_kernel<T, true>), grid, dim3(256), 0, st, (const uint8_t*)img, (long long)H,
-                     (long long)W, (const long long*)origins, (long long)h, (long long)w, (T*)out);
-    else
-        OFASR_LAUNCH((tile_gather_u8_kernel<T, false>), grid, dim3(256), 0, st, (const uint8_t*)img, (long long)H,
-                     (long long)W, (const long long*)origins, (long long)h, (long long)w, (T*)out);
+    dispatch_bool(vec, [&](auto VEC) {
+        OFASR_LAUNCH((tile_gather_u8_kernel<T, VEC>), grid, dim3(256), 0, st, (const uint8_t*)img, (long long)H, (long long)W,
+                     (const long long*)origins, (long long)h, (long long)w, (T*)out);
+    });
 }
 
 template <typename T>
@@ -143,14 +141,10 @@ static void tio_scatter(const void* src, int64_t n, int64_t sh, int64_t sw, cons
     const bool wide = reinterpret_cast<uintptr_t>(img) % 4 == 0;
     const dim3 grid(grid_blocks(max_eh * ((max_ew >> 2) + 2)), (unsigned)n);
     prof_note((double)n * (double)(max_eh * max_ew) * (3.0 + 3.0 * sizeof(T)), 0.0);
-    if (wide)
-        OFASR_LAUNCH((tile_scatter_u8_kernel<T, true>), grid, dim3(256), 0, st, (const T*)src, (long long)sh,
-                     (long long)sw, (const long long*)table, (uint8_t*)img, (long long)OH, (long long)OW,
-                     (long long)max_eh, (long long)max_ew);
-    else
-        OFASR_LAUNCH((tile_scatter_u8_kernel<T, false>), grid, dim3(256), 0, st, (const T*)src, (long long)sh,
-                     (long long)sw, (const long long*)table, (uint8_t*)img, (long long)OH, (long long)OW,
-                     (long long)max_eh, (long long)max_ew);
+    dispatch_bool(wide, [&](auto WIDE) {
+        OFASR_LAUNCH((tile_scatter_u8_kernel<T, WIDE>), grid, dim3(256), 0, st, (const T*)src, (long long)sh, (long long)sw,
+                     (const long long*)table, (uint8_t*)img, (long long)OH, (long long)OW, (long long)max_eh, (long long)max_ew);
+    });
 }
 
 }  // namespace ofasr
@@ -162,7 +156,7 @@ OFASR_EXPORT int ofasr_tile_gather_u8(const void* img, int64_t H, int64_t W, con
     const char* name = "ofasr_tile_gather_u8";
     OFASR_REQUIRE(img && origins && out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(H > 0 && W > 0 && n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
-    TILE_REQUIRE_DTYPE(dtype);
+    OFASR_REQUIRE_DTYPE(dtype);
     TILE_REQUIRE_WINDOWS(n, h, w, H, W, "image", "too many windows or too large an image");
     hipStream_t st = as_stream(stream);
     dispatch_float(dtype, [&](auto t) { tio_gather<typename decltype(t)::type>(img, H, W, origins, n, h, w, out, st); });
@@ -175,7 +169,7 @@ OFASR_EXPORT int ofasr_tile_scatter_u8(const void* src, int64_t n, int64_t sh, i
     OFASR_REQUIRE(src && table && img, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && OH > 0 && OW > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG,
                   "%s: non-positive size", name);
-    TILE_REQUIRE_DTYPE(dtype);
+    OFASR_REQUIRE_DTYPE(dtype);
     OFASR_REQUIRE(max_eh <= sh && max_ew <= sw, OFASR_ERR_INVALID_ARG, "%s: extent bound larger than the source window",
                   name);
     TILE_REQUIRE_COUNT(n, OH, OW, "too many windows or too large an image");

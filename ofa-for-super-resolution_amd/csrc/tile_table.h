@@ -5,9 +5,9 @@
 //                         and the destination (scatter_dest: the destination half alone);
 //   window_slabs / slab_rows     how many row slabs a window is cut into and which rows a slab owns;
 //   window_compact_by_class      the ordered compaction of plan rows by class in one workgroup;
-//   vec4 / pack4 / unpack4 / quant / grid_blocks   the 4-element accesses of a tile row, the quantisation of network
-//                         output, the grid size of a grid-stride kernel;
-//   host side: the checks of a window table's entry point (TILE_REQUIRE_*) and dispatch_float.
+//   pack4 / unpack4 / quant / grid_blocks   the 4-element accesses of a tile row (vec4: ofasr_common.h), the quantisation
+//                         of network output, the grid size of a grid-stride kernel;
+//   host side: the checks of a window table's entry point (TILE_REQUIRE_*; the dtype check and dispatch_float: launch.h).
 // The clamps are __host__ __device__: tests/host/tile_table_check.hip runs them on the CPU over extreme rows and asserts
 // the post-conditions that make every later access legal.  Everything is __forceinline__ and changes no access width.
 #pragma once
@@ -90,11 +90,6 @@ __host__ __device__ __forceinline__ void slab_rows(long long nrows, long long s,
 }
 
 // ---- 4 elements of a tile row, quantisation, grid size -------------------------------------------------------------------
-template <typename T> struct vec4;
-template <> struct vec4<float> { typedef float4 type; };
-template <> struct vec4<bf16_t> { typedef uint2 type; };
-template <> struct vec4<f16_t> { typedef uint2 type; };
-
 template <typename T> __device__ __forceinline__ typename vec4<T>::type pack4(const float* v);
 template <> __device__ __forceinline__ float4 pack4<float>(const float* v) { return make_float4(v[0], v[1], v[2], v[3]); }
 template <> __device__ __forceinline__ uint2 pack4<bf16_t>(const float* v) {
@@ -194,21 +189,10 @@ __device__ __forceinline__ void window_compact_by_class(Classify cls_of, const l
     }
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------
-// f(tag) with tag.type = float / bf16_t / f16_t for a dtype that TILE_REQUIRE_DTYPE has accepted
-template <typename T> struct type_tag { typedef T type; };
-template <typename F> inline void dispatch_float(int dtype, F&& f) {
-    if (dtype == OFASR_F32) f(type_tag<float>{});
-    else if (dtype == OFASR_BF16) f(type_tag<bf16_t>{});
-    else f(type_tag<f16_t>{});
-}
-
 }  // namespace ofasr
 
+// ---- host side ---------------------------------------------------------------------------------------------------------
 // The checks of an entry point that takes a window table; `name` is the entry point's.  The sizes are positive already.
-#define TILE_REQUIRE_DTYPE(dtype)                                                                                       \
-    OFASR_REQUIRE((dtype) == OFASR_F32 || (dtype) == OFASR_F16 || (dtype) == OFASR_BF16, OFASR_ERR_INVALID_ARG,        \
-                  "%s: bad dtype", name)
 #define TILE_REQUIRE_FRAME_CAP(H, W)                                                                                   \
     OFASR_REQUIRE((H) <= (1LL << 40) / (W), OFASR_ERR_UNSUPPORTED, "%s: too large a frame", name)
 // at most 65535 rows (grid.y) and an H x W frame of at most 2^40 pixels; `msg` is the entry point's own wording

@@ -226,7 +226,7 @@ static int yuv_tile_gather(const char* name, const void* y, const void* u, const
     OFASR_REQUIRE(y && u && v && coeffs && origins && out, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && h > 0 && w > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
     YUV_REQUIRE_FRAME(H, W);
-    TILE_REQUIRE_DTYPE(dtype);
+    OFASR_REQUIRE_DTYPE(dtype);
     TILE_REQUIRE_WINDOWS(n, h, w, H, W, "frame", "too many windows");
     OFASR_REQUIRE(yuv_coeffs_ok(coeffs, 6), OFASR_ERR_INVALID_ARG, "%s: coefficient outside the 14-bit tables' range", name);
     hipStream_t st = as_stream(stream);
@@ -242,7 +242,7 @@ static int yuv_tile_scatter(const char* name, const void* src, int64_t n, int64_
     OFASR_REQUIRE(src && table && coeffs && y && u && v, OFASR_ERR_INVALID_ARG, "%s: null pointer", name);
     OFASR_REQUIRE(n > 0 && sh > 0 && sw > 0 && max_eh > 0 && max_ew > 0, OFASR_ERR_INVALID_ARG, "%s: non-positive size", name);
     YUV_REQUIRE_FRAME(OH, OW);
-    TILE_REQUIRE_DTYPE(dtype);
+    OFASR_REQUIRE_DTYPE(dtype);
     OFASR_REQUIRE(max_eh <= sh && max_ew <= sw, OFASR_ERR_INVALID_ARG, "%s: extent bound larger than the source window",
                   name);
     TILE_REQUIRE_COUNT(n, OH, OW, "too many windows");

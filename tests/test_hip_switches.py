@@ -12,7 +12,8 @@ default kernel served them there: a switch the library silently ignores fails it
 Children run one at a time (with the parent: two processes on the GPU).  After a child that ended by a signal, by an
 abort / fault status or at its time limit, no further child is started.  No row is retried.
 
-tests/test_switch_coverage.py keeps the table complete: every getenv("OFASR_...") of csrc/ has a row here or a named
+tests/test_switch_coverage.py keeps the table complete: every switch csrc/ reads (csrc/launch.h: env_*("OFASR_..."))
+has a row here or a named
 test elsewhere."""
 import json
 import os

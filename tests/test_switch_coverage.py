@@ -1,8 +1,9 @@
 """Every environment switch the library reads has a test of its other side.  (No GPU: this compares names only.)
 
-A getenv("OFASR_...") in csrc/ must have a row in tests/test_hip_switches.py::SWITCHES -- a fresh process under the
-switch, checked against the CPU oracle -- or an entry in COVERED_ELSEWHERE naming the test that flips it, or the reason
-it changes no result.  A name in either table must still be read by the sources."""
+A switch read in csrc/ -- through one of the readers of csrc/launch.h: env_default_on / env_default_off /
+env_positive_int("OFASR_...") or the raw env_value -- must have a row in tests/test_hip_switches.py::SWITCHES -- a fresh
+process under the switch, checked against the CPU oracle -- or an entry in COVERED_ELSEWHERE naming the test that flips
+it, or the reason it changes no result.  A name in either table must still be read by the sources."""
 import glob
 import os
 import re
@@ -25,7 +26,7 @@ def _names_in_sources():
     files = glob.glob(os.path.join(ROOT, PKG, "csrc", "*.hip")) + glob.glob(os.path.join(ROOT, PKG, "csrc", "*.h"))
     assert len(files) > 20, files
     for f in files:
-        names.update(re.findall(r'getenv\("(OFASR_[A-Z0-9_]+)"\)', open(f).read()))
+        names.update(re.findall(r'\benv_(?:default_on|default_off|positive_int|value)\("(OFASR_[A-Z0-9_]+)"', open(f).read()))
     return names
 
 
