@@ -3,7 +3,8 @@
 OFAMobileNetS4(k7,e6,d4,pd2), load a checkpoint, fix a sub-network and report (loss, Y-PSNR) on the test loader
 (BASELINE config 5; full-resolution images, sides multiples of 4).  Images of equal size are batched together
 (--batched, the default: SRRunManager.validate_batched; per-image loss / PSNR, identical to the batch-1 pass) and the
-pass is timed: images/s of the evaluation, after one untimed warm-up pass."""
+pass is timed: images/s of the evaluation, after one untimed warm-up pass.  --degrade-blur S / --degrade-noise V score
+on LR inputs under one fixed degradation (degrade.py; stream = the image's running index), made on the GPU."""
 import argparse
 import importlib
 import os
@@ -68,10 +69,35 @@ def main(argv=None):
     ap.add_argument("--self-ensemble", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
                     help="with --static: also score the geometric self-ensemble, the fp32 mean of the outputs under the "
                          "first K of the 8 flips / transposes (2: + horizontal flip, 4: + vertical flips, 8: + transposes)")
+    ap.add_argument("--degrade-blur", type=float, default=None, metavar="S",
+                    help="score on degraded LR inputs (degrade.py): every test image blurred with sigma_x = sigma_y = S HR "
+                         "pixels before the down-sampling")
+    ap.add_argument("--degrade-noise", type=float, default=None, metavar="V",
+                    help="score on degraded LR inputs: noise of sigma V 8-bit levels after the down-sampling, a stream per "
+                         "image (its running index)")
+    ap.add_argument("--degrade-seed", type=int, default=0, metavar="N", help="the seed of the noise generator (default 0)")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     a = ap.parse_args(argv)
     video_kw = vf.take_video_args(a)        # --video: evaluate on the evaluation frames of raw YUV 4:2:0 video
+    degrade = None
+    if a.degrade_blur is not None or a.degrade_noise is not None:
+        dg = importlib.import_module(PKG + ".degrade")
+        try:
+            dg.blur_radius(a.degrade_blur or 0.0)
+        except ValueError as e:
+            ap.error("--degrade-blur: %s" % e)
+        try:
+            dg.noise_amplitude(a.degrade_noise or 0.0)
+        except ValueError as e:
+            ap.error("--degrade-noise: %s" % e)
+        if video_kw and video_kw.get("videos_lr"):
+            ap.error("--degrade-blur / --degrade-noise with --video-lr: the LR inputs of paired video are the decoded LR "
+                     "stream's, there is no bicubic to degrade")
+        degrade = (a.degrade_blur or 0.0, a.degrade_noise or 0.0, a.degrade_seed)
+    elif a.degrade_seed != 0:
+        ap.error("--degrade-seed needs --degrade-blur S or --degrade-noise V")
+    dkw = {} if degrade is None else {"degrade": degrade}      # without the options every call is what it was
     if a.self_ensemble != 1 and not a.static:
         ap.error("--self-ensemble needs an exported static network (--static DIR)")
     import torch
@@ -95,7 +121,8 @@ def main(argv=None):
         cfg = rm.VideoFramesRunConfig(image_size=32, **dict(kw, **video_kw))
     else:
         cfg = rm.Div2K_SetXXRunConfig(image_size=256, test_sizes=sizes, n_train_batches=1,
-                                      allow_synthetic=True if a.synthetic else None, **kw)
+                                      allow_synthetic=True if a.synthetic else None,
+                                      **({} if degrade is None else {"lr_on_device": True}), **kw)
     mgr = rm.SRRunManager(a.path, net, cfg, init=a.checkpoint is None and not a.static, mix_prec=a.mix_prec, num_gpus=1)
     if a.static:
         key = input_key(net.upscale)
@@ -107,12 +134,15 @@ def main(argv=None):
         if a.export:
             export_static(net, a.export)
     import time
-    n_img = len(cfg.test_loader) if video_kw else sum(b["image"].shape[0] for b in cfg.test_loader)
+    if degrade is not None:
+        print("degraded LR inputs: blur sigma %g, noise sigma %g, seed %d" % degrade)
+    n_img = len(cfg.test_loader) if video_kw else sum(b["image" if degrade is None else "image_u8"].shape[0]
+                                                       for b in cfg.test_loader)
 
     def run():
         if a.batch1:
-            return mgr.validate(is_test=True, input_key=key) + (n_img,)
-        return mgr.validate_batched(is_test=True, input_key=key)
+            return mgr.validate(is_test=True, input_key=key, **dkw) + (n_img,)
+        return mgr.validate_batched(is_test=True, input_key=key, **dkw)
 
     run()                                   # warm-up (allocator, MIOpen find for the vendor-path convs)
     torch.cuda.synchronize()
@@ -124,10 +154,10 @@ def main(argv=None):
                                                                                        n_img / dt))
     q = None
     if a.ssim:
-        q = mgr.validate_quality(is_test=True, input_key=key, shave=a.shave)
+        q = mgr.validate_quality(is_test=True, input_key=key, shave=a.shave, **dkw)
         print("Y-SSIM %.4f  Y-PSNR %.3f dB  (exact luma, shave %d, scored on the GPU)" % (q["ssim"], q["psnr"], a.shave))
     if a.self_ensemble != 1:
-        q = mgr.validate_quality(is_test=True, input_key=key, shave=a.shave, self_ensemble=a.self_ensemble)
+        q = mgr.validate_quality(is_test=True, input_key=key, shave=a.shave, self_ensemble=a.self_ensemble, **dkw)
         print("self-ensemble x%d: Y-SSIM %.4f  Y-PSNR %.3f dB  loss %.5f  (exact luma, shave %d, %d forward calls)"
               % (a.self_ensemble, q["ssim"], q["psnr"], q["loss"], a.shave, q["calls"]))
     return q

@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 314 /* + ofasr_sr_loss_workspace / _fwd / _bwd */
+#define OFASR_VERSION 315 /* + ofasr_degrade_blur_u8, ofasr_degrade_noise_u8 */
 
 typedef enum {
     OFASR_OK = 0,
@@ -800,6 +800,39 @@ int ofasr_aug_gather_yuv420_pair(const void* hr_pool, int64_t hr_bytes, const vo
 int ofasr_aug_select(const void* pool, int64_t pool_bytes, const int64_t* cand, int64_t blocks, int64_t n, int64_t K,
                      int64_t S, int layout, int64_t* out_table, int32_t* choice, int64_t* activity, int64_t* stats,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* The blind-SR degradation of the training inputs, LR = (HR * k) downsampled + n, as two exact integer functions around
+ * ofasr_bicubic_resize_u8: a per-sample separable Gaussian blur of the uint8 HR batch and per-sample additive noise on a
+ * uint8 LR batch (host statement: degrade.py, blur_np / noise_np; the kernels equal it bit for bit).  One launch each, no
+ * host synchronisation, no atomics: two calls give identical bytes.
+ *   table:  device int32 [n][48], 4-byte aligned, one row per sample, serving both entry points:
+ *             0, 1   r_x, r_y (0 .. 10)     2  a     3  gray     4  stream (31 bits)     5  0
+ *             6..26  t_x: the tap for offset d at column 16 + d, zero outside the radius      27..47  t_y likewise (37 + d)
+ *           The taps are non-negative and sum to 2^14 per axis (degrade.blur_taps forms them in float64 on the host:
+ *           t[d] = floor(g[d] * 2^14 + 0.5) of the normalised Gaussian, radius min(10, max(1, ceil(3 sigma))), the centre
+ *           corrected to make the sum exact).
+ *   blur:   uint8 [n][3][H][W] -> dst of the same shape, src != dst, neither needs any alignment:
+ *             h[y][x]   = (sum_{|d| <= r_x} t_x[d] * src[y][clamp(x + d, 0, W - 1)] + 2^13) >> 14
+ *             dst[y][x] = (sum_{|d| <= r_y} t_y[d] * h[clamp(y + d, 0, H - 1)][x] + 2^13) >> 14
+ *           h is a uint8 (no clip is needed).  r_x = r_y = 0 is a copy.  `max_radius`: the largest radius the table's
+ *           rows hold, 0 .. 10 -- the table lives on the device, so this is what the host can check; a row's radius is
+ *           clamped to [0, max_radius], and every source address into the plane, whatever the table holds.
+ *   noise:  uint8 [n][3][H][W] -> out_u8 (may be src itself: in place) and, unless NULL, out_f32 = __fdiv_rn(v, 255.0f)
+ *           (float [n][3][H][W], 4-byte aligned), ToTensor's bits.  Per element one Philox4x32-10 call (multipliers
+ *           D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85) with counter (y * W + x, channel, stream, scale) and
+ *           key (seed_lo, seed_hi); s = the sum of its 16 output bytes, c = s - 2040 (mean 0, std sqrt(16 * 65535 / 12) =
+ *           295.601, near-Gaussian); out = clip(v + ((a * c + 2^15) >> 16), 0, 255), arithmetic shift; a = round(sigma_n *
+ *           2^16 / 295.601) is formed by the host (degrade.noise_amplitude) and clamped to [0, 2^19] here.  With gray != 0
+ *           the three channels use channel 0's call.  a = 0 is a copy.  `scale`: the down-scale of the image the noise is
+ *           laid on, so that the 2x and 4x images of one sample get different noise.
+ * OFASR_ERR_INVALID_ARG: a null pointer (out_f32 excepted), n < 0, a non-positive H or W, src == dst for the blur, a
+ * misaligned table or fp32 output.  OFASR_ERR_UNSUPPORTED: H * W >= 2^32 (the counter word), n > 21845, max_radius outside
+ * 0 .. 10, more than 65535 * 32 rows for the blur, a scale that is not 2 or 4.  Nothing is launched in any of these cases;
+ * n = 0 launches nothing and succeeds. */
+int ofasr_degrade_blur_u8(const void* src, const int32_t* table, int64_t n, int64_t H, int64_t W, int64_t max_radius,
+                          void* dst, void* stream);
+int ofasr_degrade_noise_u8(const void* src, const int32_t* table, uint32_t seed_lo, uint32_t seed_hi, int64_t scale,
+                           int64_t n, int64_t H, int64_t W, void* out_u8, void* out_f32, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Y-channel quality metrics: exact SSE (for Y-PSNR) and mean SSIM of two image batches, per image  -- replaces the host

@@ -168,6 +168,9 @@ SIGNATURES = {
                                               _c_vp, _c_vp, _c_vp]),
     "ofasr_aug_select": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
                                   _c_vp, _c_sz, _c_vp]),
+    "ofasr_degrade_blur_u8": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "ofasr_degrade_noise_u8": (_c_int, [_c_vp, _c_vp, ctypes.c_uint32, ctypes.c_uint32, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp,
+                                        _c_vp, _c_vp]),
     "ofasr_quality_y_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "ofasr_quality_y": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_sz,
                                  _c_vp]),

@@ -33,6 +33,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from ... import degrade as _degrade
+
 try:
     from PIL import Image
 except ImportError:   # pragma: no cover
@@ -731,9 +733,18 @@ class ResidentTrainLoader(object):
     winner on the device and its table goes to the unchanged gather: two small launches more and no host read.
     `last_params` is then the list of K-lists, `last_choice` (int32 [n]) and `last_activity` (int64 [n, K]) are device
     tensors, `batch(indices, params=...)` takes a list of K parameter sets per sample, and selection_stats() reads what
-    the batches since its last call accumulated.  With K = 1 none of this code runs."""
+    the batches since its last call accumulated.  With K = 1 none of this code runs.
 
-    def __init__(self, dataset, batch_size, sampler, size, drop_last=True, want_f32=False, ring=4, candidates=1):
+    `degrade=spec` (degrade.check_spec's keys): blurred, noisy LR inputs, the blind-SR degradation model of degrade.py.
+    Per batch one row per sample is drawn (degrade.draw_degrade, torch global RNG) after ALL crop draws of the batch, in
+    batch order, written into a pinned int32 ring like the crop table and uploaded non-blocking; the batch carries
+    'degrade' (the int32 [n, 48] device table) and 'degrade_seed', from which utils.device_batch makes the LR images
+    (ops.lr_images_from_u8(degrade=)), and `last_degrade` keeps the drawn rows beside `last_params`.
+    `batch(indices, degrade_rows=...)` takes the rows instead of drawing them.  A paired set brings its LR crops itself
+    and refuses the option.  With degrade=None no draw is made and no key added: RNG use and batches are what they were."""
+
+    def __init__(self, dataset, batch_size, sampler, size, drop_last=True, want_f32=False, ring=4, candidates=1,
+                 degrade=None, degrade_seed=0):
         self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
         self.size, self.drop_last, self.want_f32 = int(size), bool(drop_last), bool(want_f32)
         self.candidates = check_candidates(candidates)
@@ -751,17 +762,51 @@ class ResidentTrainLoader(object):
         self._done = [None] * ring
         self._turn = 0
         self.last_indices, self.last_params = None, None
+        self.degrade, self.degrade_seed, self.last_degrade = _degrade.check_spec(degrade), int(degrade_seed), None
+        if self.degrade is not None:
+            if hasattr(dataset, "make_table"):
+                raise ValueError("ResidentTrainLoader: degrade= with a paired set: its LR crops are the decoded LR stream's, "
+                                 "there is no bicubic to degrade")
+            self._dg_host = [torch.empty((self.batch_size, _degrade.TABLE_COLS), dtype=torch.int32).pin_memory()
+                             for _ in range(ring)]
+            self._dg_done = [None] * ring
+            self._dg_turn = 0
 
     def __len__(self):
         n = len(self.sampler)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
-    def batch(self, indices, params=None):
+    def batch(self, indices, params=None, degrade_rows=None):
         """the batch of images `indices`; `params` (a list of (i, j, flip, angle); with candidates = K > 1 a list of K such
-        sets per sample) are drawn when not given"""
+        sets per sample) are drawn when not given, and so are, with degrade=, the `degrade_rows` after them"""
+        out = self._batch_best_of(indices, params) if self.candidates > 1 else self._batch_plain(indices, params)
+        if self.degrade is None:
+            return out
+        return self._add_degrade(out, len(indices), degrade_rows)
+
+    def _add_degrade(self, out, n, rows):
+        """the batch's 'degrade' table: the rows are drawn here, after every crop draw of the batch"""
+        if rows is None:
+            rows = [_degrade.draw_degrade(self.degrade) for _ in range(n)]
+        if len(rows) != n:
+            raise ValueError("ResidentTrainLoader: %d degrade rows for %d samples" % (len(rows), n))
+        slot = self._dg_turn
+        self._dg_turn = (slot + 1) % len(self._dg_host)
+        if self._dg_done[slot] is not None:
+            self._dg_done[slot].synchronize()  # the upload that last read this pinned table
+        host = _degrade.degrade_table(rows, out=self._dg_host[slot])
+        with torch.cuda.device(self.dataset.device):
+            out["degrade"] = host.to(self.dataset.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._dg_done[slot] = ev
+        out["degrade_seed"] = self.degrade_seed
+        self.last_degrade = list(rows)
+        return out
+
+    def _batch_plain(self, indices, params):
+        """batch() with candidates = 1"""
         from ... import ops
-        if self.candidates > 1:
-            return self._batch_best_of(indices, params)
         ds, S = self.dataset, self.size
         draw = getattr(ds, "draw_params", None)       # a paired set draws on its LR grid
         if params is None and draw is not None:

@@ -245,13 +245,20 @@ class Div2K_SetXXDataProvider(DataProvider):
     `build_sub_train_loader`) come from augment.ResidentTrainLoader -- the same crop / flip / rotation, bit for bit, as
     one HIP gather per batch; the batches are {'image_u8'[, 'image']} on the GPU.  `valid` / `test` are unchanged.
     `crop_candidates=K` > 1 (resident only): every training crop is the most detailed of K drawn candidates
-    (augment.ResidentTrainLoader(candidates=K)); the sub-train, validation and test loaders are untouched."""
+    (augment.ResidentTrainLoader(candidates=K)); the sub-train, validation and test loaders are untouched.
+    `degrade=spec` (resident only; `degrade_seed`): the training batches carry the table of the blind-SR degradation
+    (degrade.py; augment.ResidentTrainLoader(degrade=spec)); the sub-train, validation and test loaders are untouched."""
     DEFAULT_PATH = "/SSD/div2k_setxx"
 
     def __init__(self, save_path=None, train_batch_size=256, test_batch_size=512, valid_size=None, n_worker=32,
                  resize_scale=0.08, distort_color=None, image_size=32, num_replicas=None, rank=None,
-                 lr_on_device=False, resident=False, resident_max_bytes=32 << 30, crop_candidates=1):
+                 lr_on_device=False, resident=False, resident_max_bytes=32 << 30, crop_candidates=1, degrade=None,
+                 degrade_seed=0):
         warnings.filterwarnings("ignore")
+        self.degrade, self.degrade_seed = degrade, int(degrade_seed)
+        if degrade is not None and not resident:
+            raise ValueError("degrade= needs resident=True: the blur and the noise run on the GPU around the resident "
+                             "loader's bicubic (ops.lr_images_from_u8); there is no PIL-side implementation")
         self.crop_candidates = int(crop_candidates)
         if self.crop_candidates != 1 and not resident:
             raise ValueError("crop_candidates=%d needs resident=True: the best-of-K crop selection runs on the resident "
@@ -292,7 +299,8 @@ class Div2K_SetXXDataProvider(DataProvider):
                                                  max_bytes=resident_max_bytes)
             self.train = ResidentTrainLoader(self.resident_set, train_batch_size, train_sampler, self.active_img_size,
                                              drop_last=True, want_f32=True,
-                                             **({} if self.crop_candidates == 1 else dict(candidates=self.crop_candidates)))
+                                             **({} if self.crop_candidates == 1 else dict(candidates=self.crop_candidates)),
+                                             **({} if degrade is None else dict(degrade=degrade, degrade_seed=degrade_seed)))
         else:
             self.train = self._loader(train_set, train_batch_size, train_sampler, drop_last=True)
         self.test = self._loader(self.test_dataset(eval_tf), test_batch_size, None, drop_last=False)

@@ -37,13 +37,15 @@ class SyntheticSRDataProvider(object):
     """attributes mirror DataProvider (base_provider.py): data_shape, image_size, train/valid/test."""
 
     def __init__(self, train_batch_size=16, test_batch_size=1, image_size=256, n_train_batches=4,
-                 n_test_batches=2, seed=0, rank=0, num_replicas=1, device="cpu", test_sizes=None, crop_candidates=1):
+                 n_test_batches=2, seed=0, rank=0, num_replicas=1, device="cpu", test_sizes=None, crop_candidates=1,
+                 degrade=None, degrade_seed=0, lr_on_device=False):
         self.image_size = image_size
         self.active_img_size = image_size
         self.n_classes = None
         g = torch.Generator().manual_seed(seed * 1000003 + rank)
         self.crop_candidates = int(crop_candidates)
-        if self.crop_candidates != 1:
+        self.degrade, self.degrade_seed = degrade, int(degrade_seed)
+        if self.crop_candidates != 1 or degrade is not None:
             self.train = self._resident_train(train_batch_size, image_size, n_train_batches, g)
         else:
             self.train = _ListLoader(make_batch(train_batch_size, image_size, g, device) for _ in range(n_train_batches))
@@ -51,10 +53,12 @@ class SyntheticSRDataProvider(object):
         sizes = test_sizes or [image_size] * n_test_batches
         # validation runs batch-1 full images whose sides are multiples of 4 (ModCrop(4), div2k_setxx.py:182-190)
         self.test = _ListLoader(make_batch(test_batch_size, s, gt, device) for s in sizes)
+        if lr_on_device:   # as Div2K_SetXXDataProvider(lr_on_device=True): the items carry the uint8 HR image alone
+            self.test = _ListLoader({"image_u8": b["image"].mul(255.0).round_().to(torch.uint8)} for b in self.test)
         self.valid = self.test
 
     def _resident_train(self, batch_size, size, n_batches, g):
-        """crop_candidates = K > 1: the best-of-K selection runs on a resident pool, so the training images -- one per
+        """crop_candidates = K > 1 or degrade=spec: both run on a resident pool, so the training images -- one per
         sample of an epoch, twice the crop's side, the left half one flat grey and the right half noise -- live in an
         augment.ResidentArraySet and `train` is the resident loader over it, in file order"""
         from .augment import ResidentArraySet, ResidentTrainLoader
@@ -65,7 +69,9 @@ class SyntheticSRDataProvider(object):
             images.append(a.numpy())
         self.resident_set = ResidentArraySet(images, torch.device("cuda", torch.cuda.current_device()))
         return ResidentTrainLoader(self.resident_set, batch_size, list(range(len(images))), size, drop_last=True,
-                                   want_f32=True, candidates=self.crop_candidates)
+                                   want_f32=True, candidates=self.crop_candidates,
+                                   **({} if self.degrade is None else dict(degrade=self.degrade,
+                                                                           degrade_seed=self.degrade_seed)))
 
     @staticmethod
     def name():
@@ -76,7 +82,8 @@ class SyntheticSRDataProvider(object):
         return 3, self.active_img_size, self.active_img_size
 
     def build_sub_train_loader(self, n_images, batch_size, num_worker=None, num_replicas=None, rank=None):
-        if self.crop_candidates != 1:      # BN re-calibration sees plain crops: no selection, cached like the providers'
+        if self.crop_candidates != 1 or self.degrade is not None:   # BN re-calibration sees plain crops: no selection, no
+            # degradation, cached like the providers'
             if self.__dict__.get("_sub_train") is None:
                 from .augment import ResidentTrainLoader
                 t = self.train

@@ -129,6 +129,73 @@ def take_crop_candidates(a, resident):
     return {"crop_candidates": K}
 
 
+def add_degrade_args(ap):
+    """the training scripts' --degrade-* options (degrade.py: blurred, noisy LR inputs); take_degrade checks them"""
+    ap.add_argument("--degrade-blur", default=None, metavar="LO:HI",
+                    help="train on LR inputs blurred before the down-sampling: a Gaussian whose sigma (HR pixels, at most "
+                         "10/3) is drawn per sample from LO .. HI; needs --resident or --video")
+    ap.add_argument("--degrade-aniso", action="store_true", help="draw sigma_x and sigma_y of the blur separately")
+    ap.add_argument("--degrade-noise", default=None, metavar="LO:HI",
+                    help="add noise to the LR inputs after the down-sampling: its sigma (8-bit levels, at most 50) is drawn "
+                         "per sample from LO .. HI; needs --resident or --video")
+    ap.add_argument("--degrade-gray-prob", type=float, default=0.0, metavar="P",
+                    help="the share of samples whose noise is the same in the three channels (default 0)")
+    ap.add_argument("--degrade-prob", type=float, default=1.0, metavar="P",
+                    help="the share of samples that are degraded at all (default 1)")
+    ap.add_argument("--degrade-seed", type=int, default=0, metavar="N", help="the seed of the noise generator (default 0)")
+
+
+def take_degrade(a, resident, video_kw=None, input_key=None, what=None):
+    """Remove the --degrade-* options from the parsed namespace `a` and return them as the run configs' keyword
+    arguments: {} when neither --degrade-blur nor --degrade-noise is given (everything is then what it was before the
+    options existed), {'degrade': spec, 'degrade_seed': N} otherwise.  Every refusal names its option.  `resident`: the
+    run keeps its training set on the GPU; `video_kw`: take_video_args' result; `input_key` / `what`: as
+    refuse_pair_for_hr_input's."""
+    from ... import degrade as dg
+    d = a.__dict__
+    blur, noise = d.pop("degrade_blur"), d.pop("degrade_noise")
+    aniso, gray, prob, seed = d.pop("degrade_aniso"), d.pop("degrade_gray_prob"), d.pop("degrade_prob"), d.pop("degrade_seed")
+    first = "--degrade-blur" if blur is not None else "--degrade-noise"
+    if blur is None and noise is None:
+        for opt, given in (("--degrade-aniso", aniso), ("--degrade-gray-prob", gray != 0.0), ("--degrade-prob", prob != 1.0),
+                           ("--degrade-seed", seed != 0)):
+            if given:
+                raise SystemExit("%s needs --degrade-blur LO:HI or --degrade-noise LO:HI" % opt)
+        return {}
+    if aniso and blur is None:
+        raise SystemExit("--degrade-aniso needs --degrade-blur LO:HI")
+
+    def parse(opt, text):
+        if text is None:
+            return (0.0, 0.0)
+        parts = text.split(":")
+        try:
+            vals = [float(p) for p in parts]
+        except ValueError:
+            vals = []
+        if len(vals) not in (1, 2) or len(vals) != len(parts):
+            raise SystemExit("%s takes LO:HI (or one number for both), got %r" % (opt, text))
+        return (vals[0], vals[-1])
+    try:
+        spec = dg.check_spec({"blur": parse("--degrade-blur", blur), "aniso": aniso,
+                              "noise": parse("--degrade-noise", noise), "gray_prob": gray, "prob": prob},
+                             names={"blur": "--degrade-blur", "noise": "--degrade-noise",
+                                    "gray_prob": "--degrade-gray-prob", "prob": "--degrade-prob"})
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if not 0 <= seed < 1 << 64:
+        raise SystemExit("--degrade-seed must be 0 .. 2^64 - 1, got %d" % seed)
+    if video_kw and video_kw.get("videos_lr"):
+        raise SystemExit("%s with --video-lr: the LR inputs of paired video are the decoded LR stream's, there is no "
+                         "bicubic to degrade" % first)
+    if input_key == "image":
+        raise SystemExit("%s: %s takes the HR image as its input ('image'), it has no LR input to degrade" % (first, what))
+    if not resident:
+        raise SystemExit("%s needs --resident or --video: the blur and the noise run on the GPU around the resident "
+                         "loader's bicubic; there is no PIL-side implementation" % first)
+    return {"degrade": spec, "degrade_seed": seed}
+
+
 def refuse_pair_for_hr_input(video_kw, input_key, what):
     """the entry scripts' refusal of --video-lr for a network whose input is the HR image itself (the X4 family)"""
     if video_kw and video_kw.get("videos_lr") and input_key == "image":
@@ -189,12 +256,15 @@ class VideoFramesDataProvider(object):
     files) the set is an augment.ResidentVideoPairSet and every batch and evaluation item carries the decoded LR
     stream's crop / frame; `rotate=False` trains without the rotation.  `crop_candidates=K` > 1: every training crop is
     the most detailed of K drawn candidates (augment.ResidentTrainLoader(candidates=K); a paired set scores on its HR
-    pool); the sub-train and evaluation loaders are untouched."""
+    pool); the sub-train and evaluation loaders are untouched.  `degrade=spec` (`degrade_seed`; not with `videos_lr`):
+    the training batches carry the table of the blind-SR degradation (degrade.py;
+    augment.ResidentTrainLoader(degrade=spec)); the sub-train and evaluation loaders are untouched."""
     SUB_SEED = 937162211     # DataProvider.SUB_SEED of div2k_setxx.py
 
     def __init__(self, videos, video_size=None, frames=None, valid_every=10, matrix="bt601", full_range=False,
                  train_batch_size=16, test_batch_size=1, image_size=32, num_replicas=None, rank=None,
-                 resident_max_bytes=32 << 30, videos_lr=None, video_lr_size=None, rotate=True, crop_candidates=1):
+                 resident_max_bytes=32 << 30, videos_lr=None, video_lr_size=None, rotate=True, crop_candidates=1,
+                 degrade=None, degrade_seed=0):
         import torch
         from ... import video
         from .augment import ResidentTrainLoader, ResidentVideoPairSet, ResidentVideoSet, count_frames
@@ -205,6 +275,10 @@ class VideoFramesDataProvider(object):
         self.videos_lr = None if videos_lr is None else ([videos_lr] if isinstance(videos_lr, str) else list(videos_lr))
         if self.videos_lr is None and not rotate:
             raise ValueError("VideoFramesDataProvider: rotate=False is for paired video (videos_lr)")
+        self.degrade, self.degrade_seed = degrade, int(degrade_seed)
+        if degrade is not None and self.videos_lr is not None:
+            raise ValueError("VideoFramesDataProvider: degrade= with paired video (videos_lr): the LR inputs are the decoded "
+                             "LR stream's, there is no bicubic to degrade")
         if self.videos_lr is not None and len(self.videos_lr) != len(self.videos):
             raise ValueError("VideoFramesDataProvider: %d LR videos (%s) for %d videos (%s): they are matched by position"
                              % (len(self.videos_lr), ", ".join(self.videos_lr), len(self.videos), ", ".join(self.videos)))
@@ -240,7 +314,8 @@ class VideoFramesDataProvider(object):
         self.crop_candidates = int(crop_candidates)
         self.train = ResidentTrainLoader(self.resident_set, train_batch_size, sampler, self.active_img_size,
                                          drop_last=True, want_f32=True,
-                                         **({} if self.crop_candidates == 1 else dict(candidates=self.crop_candidates)))
+                                         **({} if self.crop_candidates == 1 else dict(candidates=self.crop_candidates)),
+                                         **({} if degrade is None else dict(degrade=degrade, degrade_seed=degrade_seed)))
         self.test = _EvalFrames(self.resident_set, self.eval_indices)
         self.valid = self.test
 

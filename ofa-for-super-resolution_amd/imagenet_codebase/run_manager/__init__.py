@@ -7,6 +7,7 @@ import os
 
 from .sr_run_manager import RunConfig, SRRunManager  # noqa: F401
 from ..data_providers.synthetic_sr import SyntheticSRDataProvider
+from ... import degrade as _degrade
 
 
 class SyntheticSRRunConfig(RunConfig):
@@ -46,7 +47,7 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                  opt_param=None, weight_decay=4e-5, label_smoothing=0.1, no_decay_keys=None, mixup_alpha=None,
                  model_init="he_fout", validation_frequency=1, print_frequency=10, n_worker=32,
                  resize_scale=0.08, distort_color=None, image_size=32, allow_synthetic=None, resident=False,
-                 crop_candidates=1, **kwargs):
+                 crop_candidates=1, degrade=None, degrade_seed=0, lr_on_device=False, **kwargs):
         super().__init__(n_epochs, init_lr, lr_schedule_type, lr_schedule_param, dataset, train_batch_size,
                          test_batch_size, valid_size, opt_type, opt_param, weight_decay, label_smoothing,
                          no_decay_keys, mixup_alpha, model_init, validation_frequency, print_frequency,
@@ -62,6 +63,15 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                                  % int(crop_candidates))
             self.crop_candidates = int(crop_candidates)
             self._synthetic["crop_candidates"] = self.crop_candidates     # the stand-in selects on a resident pool too
+        if degrade is not None:           # blurred, noisy LR inputs (degrade.py); the keys exist only then
+            if not self.resident:
+                raise ValueError("degrade= needs resident=True: the blur and the noise run on the GPU around the resident "
+                                 "loader's bicubic; there is no PIL-side implementation")
+            self.degrade, self.degrade_seed = _degrade.check_spec(degrade), int(degrade_seed)
+            self._synthetic.update(degrade=self.degrade, degrade_seed=self.degrade_seed)
+        if lr_on_device:                  # evaluation items as {'image_u8'}: the LR images are made on the GPU
+            self.lr_on_device = True
+            self._synthetic["lr_on_device"] = True
         self.dataset_root = os.environ.get("OFASR_DIV2K_ROOT", "/SSD/div2k_setxx")
         self.allow_synthetic = (os.environ.get("OFASR_ALLOW_SYNTHETIC_DATA", "0") == "1") if allow_synthetic is None \
             else bool(allow_synthetic)
@@ -80,7 +90,10 @@ class Div2K_SetXXRunConfig(SyntheticSRRunConfig):
                     distort_color=self.distort_color, image_size=self.image_size,
                     num_replicas=ws if ws > 1 else None, rank=dd.rank() if ws > 1 else None,
                     resident=self.resident,
-                    **({} if self.__dict__.get("crop_candidates", 1) == 1 else dict(crop_candidates=self.crop_candidates)))
+                    **({} if self.__dict__.get("crop_candidates", 1) == 1 else dict(crop_candidates=self.crop_candidates)),
+                    **({} if self.__dict__.get("degrade") is None else dict(degrade=self.degrade,
+                                                                            degrade_seed=self.degrade_seed)),
+                    **({} if not self.__dict__.get("lr_on_device") else dict(lr_on_device=True)))
             elif self.allow_synthetic:
                 from ... import distributed as dd
                 if dd.rank() == 0:
@@ -109,7 +122,8 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
                  train_batch_size=256, test_batch_size=1, valid_size=None, opt_type="sgd", opt_param=None,
                  weight_decay=4e-5, label_smoothing=0.1, no_decay_keys=None, mixup_alpha=None, model_init="he_fout",
                  validation_frequency=1, print_frequency=10, n_worker=0, image_size=32, resident_max_bytes=32 << 30,
-                 videos_lr=None, video_lr_size=None, video_rotate=True, crop_candidates=1, **kwargs):
+                 videos_lr=None, video_lr_size=None, video_rotate=True, crop_candidates=1, degrade=None, degrade_seed=0,
+                 **kwargs):
         videos = [videos] if isinstance(videos, str) else list(videos)
         name = "video_frames: " + ", ".join(videos)
         if videos_lr is not None:
@@ -137,6 +151,11 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
             self.video_rotate = bool(video_rotate)
         if int(crop_candidates) != 1:     # best of K candidate crops; the key exists only then
             self.crop_candidates = int(crop_candidates)
+        if degrade is not None:           # blurred, noisy LR inputs (degrade.py); the keys exist only then
+            if videos_lr is not None:
+                raise ValueError("VideoFramesRunConfig: degrade= with videos_lr: the LR inputs of paired video are the "
+                                 "decoded LR stream's, there is no bicubic to degrade")
+            self.degrade, self.degrade_seed = _degrade.check_spec(degrade), int(degrade_seed)
 
     @property
     def data_provider(self):
@@ -152,5 +171,7 @@ class VideoFramesRunConfig(SyntheticSRRunConfig):
                 resident_max_bytes=self.resident_max_bytes,
                 **({} if self.__dict__.get("videos_lr") is None else dict(
                     videos_lr=self.videos_lr, video_lr_size=self.video_lr_size, rotate=self.video_rotate)),
-                **({} if self.__dict__.get("crop_candidates", 1) == 1 else dict(crop_candidates=self.crop_candidates)))
+                **({} if self.__dict__.get("crop_candidates", 1) == 1 else dict(crop_candidates=self.crop_candidates)),
+                **({} if self.__dict__.get("degrade") is None else dict(degrade=self.degrade,
+                                                                        degrade_seed=self.degrade_seed)))
         return self.__dict__["_data_provider"]

@@ -22,6 +22,7 @@ import torch.nn as nn
 from ... import distributed as dd
 from ... import ops
 from ...graphed import GraphedEval
+from ... import degrade as sr_degrade
 from ... import losses as sr_losses
 from ...utils import (AverageMeter, bucket_by_size, device_batch, psnr_from_sse, psnr_y, psnr_y_device,
                       psnr_y_per_image)
@@ -167,6 +168,13 @@ class SRRunManager(object):
 
         self.train_criterion = nn.MSELoss()
         self.test_criterion = nn.MSELoss()
+        spec = getattr(run_config, "degrade", None)
+        if spec is not None:
+            if type(self.network).__name__ == "OFAMobileNetX4":      # its input key is 'image' (search.lr_key)
+                raise ValueError("degrade=: %s takes the HR image as its input ('image'), it has no LR input to degrade"
+                                 % type(self.network).__name__)
+            self.write_log("Degraded LR inputs: %s seed %d (degrade.py: Gaussian blur before, noise after the bicubic)" % (
+                sr_degrade.describe(spec), run_config.degrade_seed), prefix="train")
         if self.loss != "reference":
             self.write_log("Training loss: %s%s (fused HIP loss, ops.sr_loss)" % (
                 self.loss, " eps %g" % self.loss_eps if self.loss == "charbonnier" else ""), prefix="train")
@@ -265,6 +273,10 @@ class SRRunManager(object):
         checkpoint["dataset"] = self.run_config.dataset
         if getattr(self.run_config, "crop_candidates", 1) != 1:      # best-of-K training crops (data_providers/augment.py)
             checkpoint["crop_candidates"] = int(self.run_config.crop_candidates)
+        if getattr(self.run_config, "degrade", None) is not None:    # blurred, noisy LR inputs (degrade.py)
+            checkpoint["degrade"] = dict(self.run_config.degrade, blur=list(self.run_config.degrade["blur"]),
+                                         noise=list(self.run_config.degrade["noise"]))
+            checkpoint["degrade_seed"] = int(self.run_config.degrade_seed)
         if self.loss != "reference":
             checkpoint["loss"] = self.loss
             if self.loss == "charbonnier":
@@ -303,10 +315,24 @@ class SRRunManager(object):
         print("Run configs dump to %s" % run_save_path)
 
     # --------------------------------------------------------------------- validate / train
+    def _eval_batch(self, mini_batch, degrade, at):
+        """device_batch of an evaluation item.  `degrade` = (blur sigma, noise sigma, seed): its LR images carry that fixed
+        degradation (degrade.fixed_rows: sigma_x = sigma_y, stream = the image's running index, `at` for the item's
+        first), which needs items that carry the uint8 HR image (a provider built with lr_on_device=True, or video)."""
+        if degrade is None:
+            return device_batch(mini_batch, self.device)
+        if "image_u8" not in mini_batch or "lr_u8" in mini_batch:
+            raise ValueError("degrade= evaluates items that carry 'image_u8' alone (a provider built with lr_on_device=True, "
+                             "or unpaired video): got keys %s" % sorted(mini_batch))
+        blur, noise, seed = degrade
+        rows = sr_degrade.fixed_rows(mini_batch["image_u8"].shape[0], blur, noise, first=at)
+        table = torch.from_numpy(sr_degrade.degrade_table(rows)).to(self.device)
+        return device_batch(dict(mini_batch, degrade=table, degrade_seed=int(seed)), self.device)
+
     def validate(self, epoch=0, is_test=True, run_str="", net=None, data_loader=None, no_logs=False,
-                 tensorboard_logging=False, input_key="2x_down_image"):
+                 tensorboard_logging=False, input_key="2x_down_image", degrade=None):
         """eval-mode pass over the test (or valid) loader: (mean MSE loss, mean Y-PSNR).  The reference
-        always feeds '2x_down_image' (:352-361, quirk Q4); `input_key` lifts that for 4x nets."""
+        always feeds '2x_down_image' (:352-361, quirk Q4); `input_key` lifts that for 4x nets.  `degrade`: _eval_batch."""
         if net is None:
             net = self.net
         if data_loader is None:
@@ -314,8 +340,10 @@ class SRRunManager(object):
         net.eval()
         losses, psnrs = AverageMeter(), AverageMeter()
         with torch.no_grad():
+            at = 0
             for mini_batch in data_loader:
-                mini_batch = device_batch(mini_batch, self.device)
+                mini_batch = self._eval_batch(mini_batch, degrade, at)
+                at += mini_batch["image"].shape[0]
                 images, lr = mini_batch["image"], mini_batch[input_key]
                 with self.autocast():
                     output = net(lr)
@@ -335,13 +363,13 @@ class SRRunManager(object):
         return g
 
     def validate_batched(self, net=None, data_loader=None, is_test=True, input_key="2x_down_image", max_batch=None,
-                         graphs=None):
+                         graphs=None, degrade=None):
         """`validate` with the loader's batch-1 items of EQUAL size run as one batch (BASELINE config 5: Set14 at
         full resolution, reference eval_ofa_net_sr.py:187-220,247-251 / sr_run_manager.py:323-393).  Loss and PSNR are
         taken per image, so the result equals `validate` on the batch-1 loader (tests/test_hip_configs.py).
         `graphs` (default: on for 16-bit GPU inference unless OFASR_EVAL_GRAPHS=0): the forwards of all size buckets are
         captured once as ONE hipGraph and replayed -- the per-launch host cost otherwise bounds this loop (graphed.py).
-        Returns (mean loss, mean PSNR, number of forward calls)."""
+        `degrade`: _eval_batch.  Returns (mean loss, mean PSNR, number of forward calls)."""
         if net is None:
             net = self.net
         if graphs is None:
@@ -354,7 +382,7 @@ class SRRunManager(object):
         net.eval()
         items = []
         for mini_batch in data_loader:
-            mini_batch = device_batch(mini_batch, self.device)
+            mini_batch = self._eval_batch(mini_batch, degrade, len(items))
             for i in range(mini_batch["image"].shape[0]):
                 items.append({k: v[i:i + 1] for k, v in mini_batch.items() if torch.is_tensor(v)})
         losses, psnrs, calls = AverageMeter(), AverageMeter(), 0
@@ -379,7 +407,7 @@ class SRRunManager(object):
         return losses.avg, psnrs.avg, calls
 
     def validate_quality(self, net=None, data_loader=None, is_test=True, input_key="2x_down_image", max_batch=None,
-                         graphs=None, shave=0, self_ensemble=1):
+                         graphs=None, shave=0, self_ensemble=1, degrade=None):
         """`validate_batched` (same size buckets, same forwards) scored on the GPU: Y-PSNR and Y-SSIM by the HIP metric
         kernel (ops.quality_y: exact integer luma, `shave` border pixels dropped) and the per-image MSE loss by
         ops.quality_mse, straight from the network's output.  No image goes to the host and no ATen kernel runs between
@@ -387,7 +415,7 @@ class SRRunManager(object):
         image holds one of the 194 colours whose exact luma is a rounding tie (utils.y_exact).
         `self_ensemble` = k in {2, 4, 8}: every bucket is scored on the fp32 mean of the network's outputs under the first
         k flips / transposes (ops.self_ensemble); with graphs, the transformed inputs of all buckets run as one replay.
-        "calls" then counts k forwards per bucket.
+        "calls" then counts k forwards per bucket.  `degrade`: _eval_batch.
         Returns {"loss", "psnr", "ssim", "calls"} (means over the images; "psnr_per_image" / "ssim_per_image" beside)."""
         if net is None:
             net = self.net
@@ -403,7 +431,7 @@ class SRRunManager(object):
         net.eval()
         items = []
         for mini_batch in data_loader:
-            mini_batch = device_batch(mini_batch, self.device)
+            mini_batch = self._eval_batch(mini_batch, degrade, len(items))
             for i in range(mini_batch["image"].shape[0]):
                 items.append({k_: v[i:i + 1] for k_, v in mini_batch.items() if torch.is_tensor(v)})
         calls = 0

@@ -189,18 +189,86 @@ def bicubic_resize_u8(img, out_h, out_w):
     return out
 
 
-def lr_images_from_u8(hr_u8, image=None, given=None):
+def _degrade_operands(name, img, table):
+    """the checks degrade_blur_u8 and degrade_noise_u8 share: a contiguous uint8 [N, 3, H, W] batch and the int32
+    [>= N, 48] table (degrade.degrade_table) on its device"""
+    _gpu(img, table)
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.size(1) != 3 or not img.is_contiguous():
+        raise _C.OfasrError("%s: a contiguous uint8 [N, 3, H, W] batch, got %s %s" % (name, img.dtype, tuple(img.shape)))
+    if table.dtype != torch.int32 or table.dim() != 2 or table.size(1) != 48 or table.size(0) < img.size(0) or \
+            not table.is_contiguous() or table.device != img.device:
+        raise _C.OfasrError("%s: table is a contiguous int32 [>= %d, 48] tensor on %s, got %s %s on %s"
+                            % (name, img.size(0), img.device, table.dtype, tuple(table.shape), table.device))
+
+
+def degrade_blur_u8(hr_u8, table, max_radius=10):
+    """The uint8 batch [N, 3, H, W] under the per-sample separable Gaussian of the int32 [N, 48] device table: a new
+    tensor, bit-equal to degrade.blur_np (ofasr_degrade_blur_u8, csrc/degrade.hip).  `max_radius`: the largest radius
+    the table's rows hold, where the caller knows a smaller one than 10."""
+    name = "degrade_blur_u8"
+    _degrade_operands(name, hr_u8, table)
+    N, _, H, W = hr_u8.shape
+    out = torch.empty_like(hr_u8)
+    with _timed(name, 2 * hr_u8.numel()):
+        _C.check(_C.lib().ofasr_degrade_blur_u8(_p(hr_u8), _p(table), N, H, W, int(max_radius), _p(out), _stream()), name)
+    return out
+
+
+def degrade_noise_u8(lr_u8, table, seed, scale, want_f32=False, out=None):
+    """The uint8 batch [N, 3, H, W] with the per-sample noise of the int32 [N, 48] device table laid on it, bit-equal to
+    degrade.noise_np(lr_u8, table, seed, scale) (ofasr_degrade_noise_u8, csrc/degrade.hip); with `want_f32` the pair
+    (uint8, float32 = u8 / 255, ToTensor's bits).  `seed`: the run's 64-bit seed; `scale`: 2 or 4, the down-scale of
+    `lr_u8`; `out`: the uint8 result's tensor, `lr_u8` itself for in place."""
+    name = "degrade_noise_u8"
+    _degrade_operands(name, lr_u8, table)
+    if out is None:
+        out = torch.empty_like(lr_u8)
+    elif out.dtype != torch.uint8 or out.shape != lr_u8.shape or not out.is_contiguous() or out.device != lr_u8.device:
+        raise _C.OfasrError("%s: out= is a contiguous uint8 %s tensor on %s, got %s %s on %s"
+                            % (name, tuple(lr_u8.shape), lr_u8.device, out.dtype, tuple(out.shape), out.device))
+    N, _, H, W = lr_u8.shape
+    f32 = torch.empty(lr_u8.shape, dtype=torch.float32, device=lr_u8.device) if want_f32 else None
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    with _timed(name, lr_u8.numel() * (6 if want_f32 else 2)):
+        _C.check(_C.lib().ofasr_degrade_noise_u8(_p(lr_u8), _p(table), seed & 0xFFFFFFFF, seed >> 32, int(scale), N, H, W,
+                                                 _p(out), _p(f32) if want_f32 else None, _stream()), name)
+    return (out, f32) if want_f32 else out
+
+
+def _degraded_lr_images(hr_u8, image, table, seed):
+    """lr_images_from_u8 with `degrade`: the HR batch is blurred once, both bicubics read the blurred batch, and each LR
+    image gets its scale's noise in place; 'image', the target, stays the clean batch"""
+    _, _, H, W = hr_u8.shape
+    out = {"image": hr_u8.float().div_(255.0) if image is None else image}
+    blurred = degrade_blur_u8(hr_u8.contiguous(), table)
+    for f in (2, 4):
+        lr = bicubic_resize_u8(blurred, int(H * (1.0 / f)), int(W * (1.0 / f)))
+        if image is None:                  # as below: ATen's division where the caller brought no exact `image`
+            out["%dx_down_image" % f] = degrade_noise_u8(lr, table, seed, f, out=lr).float().div_(255.0)
+        else:
+            out["%dx_down_image" % f] = degrade_noise_u8(lr, table, seed, f, want_f32=True, out=lr)[1]
+    return out
+
+
+def lr_images_from_u8(hr_u8, image=None, given=None, degrade=None, degrade_seed=0):
     """{'image', '2x_down_image', '4x_down_image'} (float32 in [0, 1], the loader contract of the reference's
     Div2K_SetXXDataset.__getitem__, div2k_setxx.py:288-298) from a uint8 HR batch [N, 3, H, W] already on the GPU:
     Scale(1/2) and Scale(1/4) as PIL computes them (output size int(h/f) x int(w/f)), then ToTensor's /255.
     `image`: the fp32 HR batch where the caller already has it (aug_gather_u8's second output: u8 / 255 with a correctly
     rounded division, ToTensor's bits), reused as it is; the LR images are then divided exactly as well.
     `given`: {f: float32 [N, 3, H/f, W/f]} LR batches that exist already (the decoded LR stream of a paired video
-    batch); they take the place of the bicubic at their scale."""
+    batch); they take the place of the bicubic at their scale.
+    `degrade`: the int32 [N, 48] device table of degrade.degrade_table (with `degrade_seed`, the run's seed): the LR
+    images are then those of the blind-SR degradation model, degrade.degrade_np bit for bit; not together with `given`."""
     _, _, H, W = hr_u8.shape
     if image is not None and (image.dtype != torch.float32 or image.shape != hr_u8.shape or image.device != hr_u8.device):
         raise _C.OfasrError("lr_images_from_u8: image= must be the float32 batch of hr_u8 (%s on %s), got %s %s on %s"
                             % (tuple(hr_u8.shape), hr_u8.device, image.dtype, tuple(image.shape), image.device))
+    if degrade is not None:
+        if given:
+            raise _C.OfasrError("lr_images_from_u8: degrade= makes the LR images itself; given= brings scale(s) %s"
+                                % sorted(given))
+        return _degraded_lr_images(hr_u8, image, degrade, degrade_seed)
     out = {"image": hr_u8.float().div_(255.0) if image is None else image}
     for f in (2, 4):
         if given and f in given:       # a paired batch brings this scale's LR images: no bicubic is computed for it

@@ -225,7 +225,9 @@ def device_batch(mini_batch, device):
     (data_providers/augment.py) may hand over the fp32 HR batch beside it ('image'), which is then reused.  A batch of
     a paired video set carries 'lr_u8' and 'lr_scale' = f as well (and 'lr', the fp32 batch, from the training loader):
     the decoded LR stream's crop becomes '<f>x_down_image' (the kernel's fp32 output, else lr_u8 / 255 correctly
-    rounded); the other scale's key stays Pillow's bicubic of the HR crop."""
+    rounded); the other scale's key stays Pillow's bicubic of the HR crop.  A batch of a degrading loader carries
+    'degrade' (the int32 [N, 48] table of degrade.py) and 'degrade_seed': the LR images are then the blurred, noisy ones
+    of ops.lr_images_from_u8(degrade=), and 'image' stays the clean batch."""
     if "image_u8" in mini_batch:
         image = mini_batch.get("image")
         given = None
@@ -235,8 +237,13 @@ def device_batch(mini_batch, device):
                 lr_u8 = mini_batch["lr_u8"].to(device, non_blocking=True)
                 lr = ops._unit_lut(lr_u8.device)[lr_u8.long()]
             given = {int(mini_batch["lr_scale"]): lr.to(device, non_blocking=True)}
+        extra = {}
+        if mini_batch.get("degrade") is not None:      # a degrading loader's table (degrade.py): blurred, noisy LR images
+            extra = dict(degrade=mini_batch["degrade"].to(device, non_blocking=True),
+                         degrade_seed=mini_batch.get("degrade_seed", 0))
         return ops.lr_images_from_u8(mini_batch["image_u8"].to(device, non_blocking=True),
-                                     image=None if image is None else image.to(device, non_blocking=True), given=given)
+                                     image=None if image is None else image.to(device, non_blocking=True), given=given,
+                                     **extra)
     return {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in mini_batch.items()}
 
 

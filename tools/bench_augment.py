@@ -17,11 +17,15 @@
  * the best-of-K leg (--crop-candidates 1,4,8; --only-candidates runs nothing else): the resident loader's img/s per K
    (--repeats measurements each) on the PNG pool and on --yuv-frames 1920x1080 4:2:0 frames, and per K > 1 the GPU time
    of ofasr_aug_select's two launches per batch; K = 1 is the loader without candidates.
+ * the degrade leg (--degrade; runs nothing else): the resident loader's img/s on the PNG pool without the option and
+   with ResidentTrainLoader(degrade=...) (blur 0.2:3.3 anisotropic, noise 1:25, every sample degraded; --repeats
+   measurements each, interleaved; the batch counts when its HR + LR images are on the device), and the GPU time per
+   batch of the blur launch and of the two noise launches.
 Prints one JSON line.
 usage: python tools/bench_augment.py [--files 32] [--entries 256] [--height 1356] [--width 2040] [--batches 200]
                                      [--warmup 10] [--host-batches 200] [--workers 16] [--skip-host]
                                      [--yuv-frames 64] [--only-yuv] [--only-pair]
-                                     [--crop-candidates 1,4,8] [--repeats 3] [--only-candidates]"""
+                                     [--crop-candidates 1,4,8] [--repeats 3] [--only-candidates] [--degrade]"""
 import argparse
 import importlib
 import json
@@ -229,6 +233,32 @@ def candidates_leg(C, L, aug, utils, dev, N, S, Ks, sets, batches, warmup, repea
     return res
 
 
+DEGRADE_SPEC = {"blur": (0.2, 3.3), "aniso": True, "noise": (1.0, 25.0), "gray_prob": 0.4, "prob": 1.0}
+
+
+def degrade_leg(C, L, aug, utils, dev, N, S, ds, batches, warmup, repeats, reps):
+    """blurred, noisy LR inputs (--degrade): the resident loader's img/s with the option off and on, measured in turns, and
+    the GPU time of the option's three launches per batch"""
+    import torch
+    sync = torch.cuda.synchronize
+
+    def step(b):
+        return utils.device_batch(b, dev)["image"].size(0)
+
+    sampler = torch.utils.data.RandomSampler(range(len(ds)))
+    off = aug.ResidentTrainLoader(ds, N, sampler, S, want_f32=True)
+    on = aug.ResidentTrainLoader(ds, N, sampler, S, want_f32=True, degrade=DEGRADE_SPEC, degrade_seed=1)
+    res = {"images": len(ds), "spec": DEGRADE_SPEC, "off_img_per_s": [], "on_img_per_s": []}
+    for _ in range(repeats):
+        res["off_img_per_s"].append(loader_rate(off, batches, warmup, step, sync))
+        res["on_img_per_s"].append(loader_rate(on, batches, warmup, step, sync))
+    idx = [torch.randint(0, len(ds), (N,)).tolist() for _ in range(reps)]
+    run = lambda ix: step(on.batch(ix))
+    res["blur_kernel_us"] = kernel_us(C, L, run, idx, "degrade_blur_kernel")
+    res["noise_kernels_us"] = kernel_us(C, L, run, idx, "degrade_noise_kernel")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=32)
@@ -249,6 +279,8 @@ def main():
                          "1920x1080 4:2:0 frames (1 = the loader without candidates)")
     ap.add_argument("--repeats", type=int, default=3, help="measurements per K of the best-of-K leg")
     ap.add_argument("--only-candidates", action="store_true", help="run the best-of-K leg alone")
+    ap.add_argument("--degrade", action="store_true", help="run the degrade leg alone: the resident loader with and "
+                                                           "without blurred, noisy LR inputs")
     a = ap.parse_args()
     import torch
     C = importlib.import_module(PKG + "._C")
@@ -268,7 +300,7 @@ def main():
         return
     if a.only_candidates and not a.crop_candidates:
         raise SystemExit("--only-candidates needs --crop-candidates K1,K2,...")
-    if a.yuv_frames > 0 and not a.only_candidates:
+    if a.yuv_frames > 0 and not a.only_candidates and not a.degrade:
         out["yuv420"] = yuv_leg(C, L, ops, aug, dev, N, S, a.yuv_frames, a.reps)
     if a.only_yuv:
         print(json.dumps(out), flush=True)
@@ -285,6 +317,11 @@ def main():
         out["resident_decode_upload_s"] = time.perf_counter() - t0
         out["resident_bytes"] = prov.resident_set.nbytes
         loader = prov.train
+        if a.degrade:
+            out["degrade"] = degrade_leg(C, L, aug, utils, dev, N, S, prov.resident_set, a.batches, a.warmup, a.repeats,
+                                         a.reps)
+            print(json.dumps(out), flush=True)
+            return
         if a.crop_candidates:
             frames = max(a.yuv_frames, 1)
             ypool, fb = synthetic_yuv_pool(dev, frames, 1080, 1920, 1)

@@ -10,7 +10,8 @@ Differences from the reference script: hyper-parameters that it edits in source 
 (--net s4|x4, --teacher-path, --path, --mix-prec); with --synthetic the synthetic provider stands in for a missing
 DIV2K directory (otherwise a missing dataset is an error); --video PATH trains on the frames of raw 8-bit YUV 4:2:0
 video instead (data_providers/video_frames.py), and --video-lr PATH pairs each video with its decoded low-resolution
-stream, which then is the network input at its scale; multi-GPU is RCCL data parallelism (one flat all-reduce per step)."""
+stream, which then is the network input at its scale; --degrade-blur / --degrade-noise train on blurred, noisy LR
+inputs made on the GPU (degrade.py); multi-GPU is RCCL data parallelism (one flat all-reduce per step)."""
 import argparse
 import importlib
 import os
@@ -46,12 +47,15 @@ def main():
     ap.add_argument("--loss-eps", type=float, default=None, metavar="E", help="the Charbonnier eps (default 1e-3)")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
+    vf.add_degrade_args(ap)
     args = ap.parse_args()
     loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, args.loss, args.__dict__.pop("loss_eps"))
     loss = args.__dict__.pop("loss")        # `args` goes into the run config: it stays what it always was
     video_kw = vf.take_video_args(args)     # None without --video: `args` is then what it always was
     args.__dict__.update(vf.take_crop_candidates(args, args.resident or bool(video_kw)))    # nothing with K = 1
     vf.refuse_pair_for_hr_input(video_kw, "image" if args.net == "x4" else None, "--net x4")
+    args.__dict__.update(vf.take_degrade(args, args.resident or bool(video_kw), video_kw,     # nothing without the options
+                                         "image" if args.net == "x4" else None, "--net x4"))
 
     import numpy as np
     import torch

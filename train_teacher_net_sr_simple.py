@@ -36,10 +36,12 @@ def main():
     ap.add_argument("--loss-eps", type=float, default=None, metavar="E", help="the Charbonnier eps (default 1e-3)")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
+    vf.add_degrade_args(ap)
     a = ap.parse_args()
     loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, a.loss, a.loss_eps)
     video_kw = vf.take_video_args(a)
     crop_kw = vf.take_crop_candidates(a, a.resident or bool(video_kw))
+    crop_kw.update(vf.take_degrade(a, a.resident or bool(video_kw), video_kw))      # blurred, noisy LR inputs (degrade.py)
 
     import numpy as np
     import torch
