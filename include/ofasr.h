@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 315 /* + ofasr_degrade_blur_u8, ofasr_degrade_noise_u8 */
+#define OFASR_VERSION 316 /* + ofasr_sr_loss_ssim_workspace, ofasr_sr_loss_ssim_fwd, ofasr_sr_loss_ssim_bwd */
 
 typedef enum {
     OFASR_OK = 0,
@@ -900,6 +900,31 @@ int ofasr_sr_loss_fwd(const void* o, int fmt_o, const void* t, int fmt_t, const 
 int ofasr_sr_loss_bwd(const void* o, int fmt_o, const void* t, int fmt_t, const void* s, int fmt_s, const float* g,
                       int64_t N, int64_t H, int64_t W, int kind, double eps, double w_main, double w_kd, void* grad,
                       void* stream);
+/* The same loss with an SSIM term (csrc/loss.hip; host statement: losses.ssim_np, losses.sr_loss_ssim_np,
+ * losses.sr_loss_ssim_grad_np): L = (1 - alpha) * L_pix + alpha * (1 - S), alpha in (0, 1], L_pix the line [2] above.
+ *   S = (sum of SSIM) / K over the three colour planes of every image, on the fp32 readings of o and t promoted to fp64
+ *   (no clamp, no quantisation; s has no part in it): ofasr_quality_y's window (11 taps, sigma 1.5, separable) at the
+ *   (H - 10) x (W - 10) positions where it lies inside the plane, K = 3 N (H - 10) (W - 10), C1 = 0.01^2, C2 = 0.03^2,
+ *   m1 = G*o, m2 = G*t, s1 = G*(o o) - m1^2, s2 = G*(t t) - m2^2, s12 = G*(o t) - m1 m2,
+ *   SSIM = (2 m1 m2 + C1)(2 s12 + C2) / ((m1^2 + m2^2 + C1)(s1 + s2 + C2)).  H >= 11 and W >= 11.
+ * ofasr_sr_loss_ssim_fwd writes result[0 .. 7] (64 bytes): [0] [1] [3] [4] as above, [2] L, [5] (float)L, [6] the sum
+ *   of SSIM, [7] S.  Three launches: the streaming kernel above, one workgroup per (plane, 16 x 16 tile of positions)
+ *   that leaves one fp64 partial, one folding workgroup.  workspace: ofasr_sr_loss_ssim_workspace(N, H, W) bytes
+ *   (host-only query; 0 for a shape the call refuses), 16-byte aligned; it holds per-workgroup partials only.
+ * ofasr_sr_loss_ssim_bwd writes grad [N, 3, H, W] in o's format, one launch, no workspace: per element
+ *   fl(pix + fl((double)g * -alpha * dS/do)), with pix the element ofasr_sr_loss_bwd writes for ca = (float)((1 - alpha)
+ *   * w_main / M), cb = (float)((1 - alpha) * w_kd / M), and dS/do in fp64 from moments the kernel recomputes on each
+ *   16 x 16 tile plus 10 pixels to every side; nothing is kept between the two calls.
+ * Every load is bounded by the plane it belongs to; any element-aligned address is accepted.  Two runs give equal bits.
+ * Refusals as above, and OFASR_ERR_INVALID_ARG for alpha outside (0, 1] or not finite and for H < 11 or W < 11;
+ * OFASR_ERR_UNSUPPORTED beyond 2^31 - 1 tiles. */
+size_t ofasr_sr_loss_ssim_workspace(int64_t N, int64_t H, int64_t W);
+int ofasr_sr_loss_ssim_fwd(const void* o, int fmt_o, const void* t, int fmt_t, const void* s, int fmt_s, int64_t N, int64_t H,
+                           int64_t W, int kind, double eps, double w_main, double w_kd, double psnr_count, double alpha,
+                           double* result, void* workspace, size_t workspace_bytes, void* stream);
+int ofasr_sr_loss_ssim_bwd(const void* o, int fmt_o, const void* t, int fmt_t, const void* s, int fmt_s, const float* g,
+                           int64_t N, int64_t H, int64_t W, int kind, double eps, double w_main, double w_kd, double alpha,
+                           void* grad, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Diagnostics (tests and bench.py; nothing on the product path calls these).

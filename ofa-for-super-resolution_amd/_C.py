@@ -182,6 +182,12 @@ SIGNATURES = {
                                    _c_vp]),
     "ofasr_sr_loss_bwd": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_i64, _c_int,
                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp]),
+    "ofasr_sr_loss_ssim_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    "ofasr_sr_loss_ssim_fwd": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_int,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                        _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ofasr_sr_loss_ssim_bwd": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_i64, _c_int,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp]),
     "ofasr_debug_mbfused_tile": (_c_int, [_c_int]),
     "ofasr_debug_mbfused_split": (_c_int, [_c_int]),
     "ofasr_debug_mbconv_bn_bwd_stat": (_c_int, [_c_int]),

@@ -146,6 +146,7 @@ def train_one_epoch(run_manager, args, epoch, warmup_epochs=0, warmup_lr=0):
     psnr_meter.update(float(psnr_sum) / max(n_seen, 1), n_seen)
     run_manager._last_train_log = log
     run_manager.log_crop_selection(epoch)      # a line only with best-of-K training crops
+    run_manager.log_train_ssim(epoch)          # a line only with an SSIM term in the loss
     return losses.avg, psnr_meter.avg
 
 
@@ -163,6 +164,8 @@ def train(run_manager, args, validate_func=None):
                 epoch + 1 - args.warmup_epochs, run_manager.run_config.n_epochs, val_loss, val_acc,
                 run_manager.best_acc)
             val_log += ", Train top-1 {top1:.3f}, Train loss {loss:.3f}\t".format(top1=train_psnr, loss=train_loss)
+            if run_manager.last_train_ssim is not None:
+                val_log += "Train SSIM {0:.4f}\t".format(run_manager.last_train_ssim)
             val_log += _val_log
             run_manager.write_log(val_log, "valid", should_print=False)
             run_manager.save_model({"epoch": epoch, "best_acc": run_manager.best_acc,

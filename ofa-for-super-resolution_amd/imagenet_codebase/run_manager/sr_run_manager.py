@@ -130,13 +130,19 @@ class SRRunManager(object):
     train_criterion, test_criterion; plus `reducer` (None on one GPU)."""
 
     def __init__(self, path, net, run_config, init=True, measure_latency=None, no_gpu=False, mix_prec=None,
-                 num_gpus=None, args=None, loss="reference", loss_eps=sr_losses.DEFAULT_EPS):
+                 num_gpus=None, args=None, loss="reference", loss_eps=sr_losses.DEFAULT_EPS, loss_ssim=0.0):
         if loss != "reference" and loss not in sr_losses.KINDS:
             raise ValueError("loss must be 'reference' or one of %s, got %r" % (", ".join(sr_losses.KINDS), loss))
         if not (loss_eps > 0 and math.isfinite(loss_eps)):
             raise ValueError("loss_eps must be positive, got %r" % (loss_eps,))
         self.loss = loss           # 'reference': nn.MSELoss through ATen, as ever; else the fused HIP loss (train_loss)
         self.loss_eps = float(loss_eps)
+        if not (0.0 <= loss_ssim <= 1.0):
+            raise ValueError("loss_ssim must lie in [0, 1], got %r" % (loss_ssim,))
+        if loss_ssim > 0 and loss == "reference":
+            raise ValueError("loss_ssim belongs to the fused losses (%s), got loss='reference'" % ", ".join(sr_losses.KINDS))
+        self.loss_ssim = float(loss_ssim)   # alpha of (1 - alpha) * loss + alpha * (1 - SSIM); 0: no SSIM term
+        self._ssim_sum, self._ssim_steps, self.last_train_ssim = None, 0, None
         self.path = path
         self.net = net
         self.run_config = run_config
@@ -176,8 +182,10 @@ class SRRunManager(object):
             self.write_log("Degraded LR inputs: %s seed %d (degrade.py: Gaussian blur before, noise after the bicubic)" % (
                 sr_degrade.describe(spec), run_config.degrade_seed), prefix="train")
         if self.loss != "reference":
-            self.write_log("Training loss: %s%s (fused HIP loss, ops.sr_loss)" % (
-                self.loss, " eps %g" % self.loss_eps if self.loss == "charbonnier" else ""), prefix="train")
+            self.write_log("Training loss: %s%s%s (fused HIP loss, ops.sr_loss)" % (
+                self.loss, " eps %g" % self.loss_eps if self.loss == "charbonnier" else "",
+                " + %g (1 - SSIM), the pixel term weighted %g" % (self.loss_ssim, 1.0 - self.loss_ssim)
+                if self.loss_ssim > 0 else ""), prefix="train")
 
         if self.run_config.no_decay_keys:
             keys = self.run_config.no_decay_keys.split("#")
@@ -281,6 +289,8 @@ class SRRunManager(object):
             checkpoint["loss"] = self.loss
             if self.loss == "charbonnier":
                 checkpoint["loss_eps"] = self.loss_eps
+            if self.loss_ssim > 0:
+                checkpoint["loss_ssim"] = self.loss_ssim
         model_path = os.path.join(self.save_path, model_name)
         with open(os.path.join(self.save_path, "latest.txt"), "w") as fout:
             fout.write(model_path + "\n")
@@ -310,8 +320,11 @@ class SRRunManager(object):
         if not self.is_root:
             return
         run_save_path = os.path.join(self.path, "run.config")
+        config = self.run_config.config
+        if self.loss_ssim > 0:      # the one setting of the run that lives on the manager and has no other record here
+            config = dict(config, loss_ssim=self.loss_ssim)
         with open(run_save_path, "w") as f:
-            json.dump(self.run_config.config, f, indent=4)
+            json.dump(config, f, indent=4)
         print("Run configs dump to %s" % run_save_path)
 
     # --------------------------------------------------------------------- validate / train
@@ -487,7 +500,8 @@ class SRRunManager(object):
         loss='reference': the lines the two loops always ran -- output.float(), nn.MSELoss, F.mse_loss against the
         teacher, utils.psnr_y_device (psnr is None in the teacher loop, which scores `output` on the host after its
         step).  Otherwise ops.sr_loss on the output as it is: loss, gradient and PSNR from the HIP kernels, psnr a 0-dim
-        fp64 view of the result buffer."""
+        fp64 view of the result buffer.  With loss_ssim > 0 the loss carries the SSIM term and the step's mean SSIM is
+        added, on the GPU, to the epoch's sum (log_train_ssim)."""
         if self.loss == "reference":
             output = output.float()
             loss = self.train_criterion(output, images)
@@ -499,7 +513,12 @@ class SRRunManager(object):
         w_main, w_kd = sr_losses.kd_weights(kd_ratio, shrinking) if soft is not None else (1.0, 0.0)
         n, _, h, w = output.shape
         loss, res = ops.sr_loss(output, images, soft, kind=self.loss, eps=self.loss_eps, w_main=w_main, w_kd=w_kd,
-                                psnr_count=sr_losses.mosaic_count(n, h, w))
+                                psnr_count=sr_losses.mosaic_count(n, h, w), ssim=self.loss_ssim)
+        if self.loss_ssim > 0:
+            if self._ssim_sum is None:
+                self._ssim_sum = torch.zeros((), device=res.device, dtype=torch.float64)
+            self._ssim_sum += res[ops.SR_LOSS_SSIM]
+            self._ssim_steps += 1
         return loss, res[ops.SR_LOSS_PSNR], output
 
     def train_one_epoch(self, args, epoch, warmup_epochs=0, warmup_lr=0, input_key="2x_down_image"):
@@ -543,7 +562,22 @@ class SRRunManager(object):
             end = time.time()
         self._last_lr = new_lr
         self.log_crop_selection(epoch)
+        self.log_train_ssim(epoch)
         return losses.avg, psnrs.avg
+
+    def log_train_ssim(self, epoch):
+        """with loss_ssim > 0: one line per epoch, the mean over the epoch's loss calls of S, the mean SSIM of the output
+        against the HR batch (slot SR_LOSS_SSIM of each call's result buffer, summed on the GPU).  Both loops call it
+        after their own host reads, so the one read here waits for nothing; last_train_ssim keeps the value for the
+        epoch's Valid line."""
+        self.last_train_ssim = None
+        if self.loss_ssim <= 0 or self._ssim_steps == 0:
+            return
+        self.last_train_ssim = float(self._ssim_sum) / self._ssim_steps
+        self.write_log("Train SSIM [%d]\tmean S %.6f\tloss calls %d" % (epoch + 1, self.last_train_ssim, self._ssim_steps),
+                       prefix="train")
+        self._ssim_sum.zero_()
+        self._ssim_steps = 0
 
     def log_crop_selection(self, epoch):
         """with best-of-K training crops (ResidentTrainLoader(candidates=K > 1)): one line per epoch, the mean luma
@@ -568,9 +602,11 @@ class SRRunManager(object):
                 val_loss, val_psnr = self.validate(epoch=epoch, is_test=False)
                 is_best = np.mean(val_psnr) > self.best_acc
                 self.best_acc = max(self.best_acc, np.mean(val_psnr))
-                self.write_log("Valid [%d/%d]\tloss %.3f\ttop-1 acc %.3f (%.3f)\tTrain top-1 %.3f\tloss %.3f\t" % (
+                self.write_log("Valid [%d/%d]\tloss %.3f\ttop-1 acc %.3f (%.3f)\tTrain top-1 %.3f\tloss %.3f\t%s" % (
                     epoch + 1 - warmup_epoch, self.run_config.n_epochs, np.mean(val_loss), np.mean(val_psnr),
-                    self.best_acc, train_psnr, train_loss), prefix="valid", should_print=False)
+                    self.best_acc, train_psnr, train_loss,
+                    "" if self.last_train_ssim is None else "SSIM %.4f\t" % self.last_train_ssim),
+                    prefix="valid", should_print=False)
             self.save_model({"epoch": epoch, "best_acc": self.best_acc, "optimizer": self.optimizer.state_dict(),
                              "state_dict": self.network.state_dict()}, is_best=is_best)
 

@@ -23,6 +23,10 @@ and the value autograd sees is fp32(L).  Gradient with respect to o alone: ca = 
 rounded to nearest even into o's dtype.  The logged metric is the exact integer squared error of the two luma images
 (utils.y_exact on the images quantised as utils.tensor2img_np does) and utils.psnr_from_sse of it over a pixel count
 the caller passes; the training loops pass mosaic_count, the count utils.psnr_y_device divides by.
+
+With an SSIM weight alpha (ops.sr_loss(ssim=alpha), --loss-ssim) the loss is (1 - alpha) * L + alpha * (1 - S); S, its
+gradient and how the two addends of an element meet are stated further down (ssim_np, sr_loss_ssim_np,
+sr_loss_ssim_grad_np).
 """
 import math
 
@@ -128,6 +132,109 @@ def sr_loss_grad_np(o, t, s=None, kind="l1", eps=DEFAULT_EPS, w_main=1.0, w_kd=0
     return round_to(out, dtype)
 
 
+# ------------------------------------------------------------------------------------------------ the SSIM term
+# L = (1 - alpha) * L_pix + alpha * (1 - S), alpha in (0, 1] (ops.sr_loss(ssim=alpha); ofasr_sr_loss_ssim_*; DESIGN.md
+# section 3.1s).  S is the mean SSIM of o against t over the three colour planes of every image: the fp32 values
+# promoted to fp64, no clamp and no quantisation, the metric's window (utils.SSIM_WINDOW taps, utils.SSIM_SIGMA,
+# utils._gauss_valid: along W, then along H) at the (H - 10) x (W - 10) positions where it lies inside the plane,
+# C1 = 0.01^2 and C2 = 0.03^2 (data range 1).  The teacher term stays pixel-wise.
+SSIM_C1, SSIM_C2 = 0.01 ** 2, 0.03 ** 2
+
+
+def ssim_window():
+    g = np.exp(-((np.arange(utils.SSIM_WINDOW) - utils.SSIM_WINDOW // 2) ** 2) / (2.0 * utils.SSIM_SIGMA ** 2))
+    return g / g.sum()
+
+
+def check_ssim(alpha, h, w):
+    if not (0.0 < alpha <= 1.0):
+        raise ValueError("the SSIM weight must lie in (0, 1], got %r" % (alpha,))
+    if h < utils.SSIM_WINDOW or w < utils.SSIM_WINDOW:
+        raise ValueError("a %dx%d plane has a side below the %d-pixel SSIM window" % (h, w, utils.SSIM_WINDOW))
+
+
+def _ssim_terms(o, t):
+    """(m1, m2, A1, A2, B1, B2) of fp32 NCHW batches, each [N * C, H - 10, W - 10] fp64"""
+    o, t = _f32(o), _f32(t)
+    check_ssim(1.0, o.shape[2], o.shape[3])
+    a = o.astype(np.float64).reshape((-1,) + o.shape[2:])
+    b = t.astype(np.float64).reshape((-1,) + t.shape[2:])
+    g = ssim_window()
+    m1, m2 = utils._gauss_valid(a, g), utils._gauss_valid(b, g)
+    s1 = utils._gauss_valid(a * a, g) - m1 * m1
+    s2 = utils._gauss_valid(b * b, g) - m2 * m2
+    s12 = utils._gauss_valid(a * b, g) - m1 * m2
+    return m1, m2, 2.0 * m1 * m2 + SSIM_C1, 2.0 * s12 + SSIM_C2, m1 * m1 + m2 * m2 + SSIM_C1, s1 + s2 + SSIM_C2
+
+
+def ssim_np(o, t):
+    """(S, K): the mean SSIM of fp32 arrays o and t over all planes and valid positions, and their number"""
+    _, _, A1, A2, B1, B2 = _ssim_terms(o, t)
+    ssim = (A1 * A2) / (B1 * B2)
+    return float(ssim.sum()) / float(ssim.size), int(ssim.size)
+
+
+def _gauss_full_t(d, g):
+    """the transpose of utils._gauss_valid: [P, h, w] maps at the valid positions -> [P, h + 10, w + 10], the full
+    correlation with the same taps (the map is zero outside the valid positions), along H and then along W"""
+    k = len(g)
+    P, h, w = d.shape
+    u = np.zeros((P, h + k - 1, w), np.float64)
+    for i in range(k):
+        u[:, i:i + h, :] += g[i] * d
+    v = np.zeros((P, h + k - 1, w + k - 1), np.float64)
+    for i in range(k):
+        v[:, :, i:i + w] += g[i] * u
+    return v
+
+
+def ssim_grad_np(o, t):
+    """dS/do of fp32 arrays o and t, fp64, shaped like o"""
+    m1, m2, A1, A2, B1, B2 = _ssim_terms(o, t)
+    K = float(m1.size)
+    dr = 2.0 * A1 / (B1 * B2)
+    dp = -A1 * A2 / (B1 * B2 * B2)
+    dm = 2.0 * m2 * (A2 - A1) / (B1 * B2) - 2.0 * m1 * A1 * A2 * (B2 - B1) / ((B1 * B2) * (B1 * B2))
+    g = ssim_window()
+    od = _f32(o).astype(np.float64).reshape((-1,) + o.shape[2:])
+    td = _f32(t).astype(np.float64).reshape((-1,) + t.shape[2:])
+    return ((_gauss_full_t(dm, g) + 2.0 * od * _gauss_full_t(dp, g) + td * _gauss_full_t(dr, g)) / K).reshape(o.shape)
+
+
+def sr_loss_ssim_np(o, t, s=None, kind="l1", eps=DEFAULT_EPS, w_main=1.0, w_kd=0.0, psnr_count=None, alpha=0.2):
+    """sr_loss_np's dict with "loss" = (1 - alpha) * L_pix + alpha * (1 - S) in fp64, its "loss_f32", "loss_pix" (what
+    sr_loss_np calls "loss"), "ssim" (S) and "ssim_sum" (S * K as summed)"""
+    check_ssim(alpha, o.shape[2], o.shape[3])
+    r = sr_loss_np(o, t, s, kind, eps, w_main, w_kd, psnr_count)
+    _, _, A1, A2, B1, B2 = _ssim_terms(o, t)
+    ssim = (A1 * A2) / (B1 * B2)
+    r["ssim_sum"] = float(ssim.sum())
+    r["ssim"] = r["ssim_sum"] / float(ssim.size)
+    r["loss_pix"] = r["loss"]
+    r["loss"] = (1.0 - float(alpha)) * r["loss_pix"] + float(alpha) * (1.0 - r["ssim"])
+    r["loss_f32"] = _F32(r["loss"])
+    return r
+
+
+def sr_loss_ssim_parts_np(o, t, s=None, kind="l1", eps=DEFAULT_EPS, w_main=1.0, w_kd=0.0, g=1.0, alpha=0.2):
+    """(pix, add): the two fp32 addends of the gradient -- sr_loss_grad_np's fp32 element for the weights scaled by
+    (1 - alpha) (the products formed in fp64) and fp32(fp64(g) * -alpha * dS/do)"""
+    check_ssim(alpha, o.shape[2], o.shape[3])
+    a = float(alpha)
+    pix = sr_loss_grad_np(o, t, s, kind, eps, (1.0 - a) * float(w_main), (1.0 - a) * float(w_kd), g=g, dtype="f32")
+    add = (float(_F32(g)) * -a * ssim_grad_np(o, t)).astype(np.float32)
+    return pix, add
+
+
+def sr_loss_ssim_grad_np(o, t, s=None, kind="l1", eps=DEFAULT_EPS, w_main=1.0, w_kd=0.0, g=1.0, dtype="f32", alpha=0.2):
+    """dL/do with the SSIM term for the incoming gradient g: fl32(pix + fl32(fp64(g) * -alpha * dS/do)) per element, as
+    the fp32 values of its round-to-nearest-even into o's dtype ("f32", "f16", "bf16")"""
+    pix, add = sr_loss_ssim_parts_np(o, t, s, kind, eps, w_main, w_kd, g, alpha)
+    out = pix + add
+    assert out.dtype == np.float32
+    return round_to(out, dtype)
+
+
 def kd_weights(kd_ratio, shrinking):
     """(w_main, w_kd) of the two training loops: the teacher loop adds kd_ratio times the teacher term, the
     progressive-shrinking loop scales that sum by 2 / (kd_ratio + 1)"""
@@ -135,9 +242,13 @@ def kd_weights(kd_ratio, shrinking):
     return (2.0 / (kd + 1.0), 2.0 * kd / (kd + 1.0)) if shrinking else (1.0, kd)
 
 
-def check_cli(ap, loss, loss_eps):
-    """the --loss / --loss-eps rules of the training scripts; `ap` is the argparse parser that reports the refusal.
-    Returns the eps to use."""
+def check_cli(ap, loss, loss_eps, loss_ssim=0.0):
+    """the --loss / --loss-eps / --loss-ssim rules of the training scripts; `ap` is the argparse parser that reports the
+    refusal.  Returns the eps to use."""
+    if not (0.0 <= loss_ssim <= 1.0):
+        ap.error("--loss-ssim must lie in [0, 1], got %r" % (loss_ssim,))
+    if loss_ssim > 0 and loss == "reference":
+        ap.error("--loss-ssim belongs to the fused losses (--loss mse|l1|charbonnier), got --loss reference")
     if loss_eps is not None:
         if loss != "charbonnier":
             ap.error("--loss-eps belongs to --loss charbonnier (got --loss %s)" % loss)

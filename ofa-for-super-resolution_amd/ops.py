@@ -457,42 +457,57 @@ def quality_mse(output, target, out=None):
 
 # ------------------------------------------------------------------------------ the training loss
 # slots of sr_loss's result buffer (fp64 [6]; include/ofasr.h): the two fp64 sums, L in fp64, the bits of the int64 Y-SSE,
-# the Y-PSNR, and fp32(L) in the low half of the last word
+# the Y-PSNR, and fp32(L) in the low half of the last word; with an SSIM term (fp64 [8]) the sum of SSIM and its mean S
 SR_LOSS_SUM_MAIN, SR_LOSS_SUM_KD, SR_LOSS_VALUE, SR_LOSS_Y_SSE, SR_LOSS_PSNR, SR_LOSS_VALUE_F32 = range(6)
+SR_LOSS_SSIM_SUM, SR_LOSS_SSIM = 6, 7
 
 
 class _SrLossFn(Function):
     """forward: ofasr_sr_loss_fwd (stream kernel + fold); backward: ofasr_sr_loss_bwd, which reads the incoming gradient
     where it is and writes dL/d(output) in output's dtype.  `cfg`: (target, soft, result buffer, kind code, eps, w_main,
-    w_kd, psnr_count) -- the tensors in it are not differentiated."""
+    w_kd, psnr_count, alpha) -- the tensors in it are not differentiated.  alpha > 0: ofasr_sr_loss_ssim_fwd (stream
+    kernel + SSIM tile kernel + fold) and ofasr_sr_loss_ssim_bwd (one tile kernel)."""
 
     @staticmethod
     def forward(ctx, output, cfg):
-        t, s, res, kind, eps, w_main, w_kd, count = cfg
+        t, s, res, kind, eps, w_main, w_kd, count, alpha = cfg
         o = output.contiguous()
         N, _, H, W = o.shape
         L = _C.lib()
-        wst, wsp, wsn = _ws(L.ofasr_sr_loss_workspace(o.numel()), o.device)
         nbytes = sum(x.numel() * x.element_size() for x in (o, t, s) if x is not None)
-        with _timed("sr_loss_fwd", nbytes):
-            _C.check(L.ofasr_sr_loss_fwd(_p(o), _dt(o), _p(t), _dt(t), None if s is None else _p(s),
-                                         0 if s is None else _dt(s), N, H, W, kind, eps, w_main, w_kd, count, _p(res),
-                                         wsp, wsn, _stream()), "sr_loss_fwd")
+        if alpha > 0:
+            wst, wsp, wsn = _ws(L.ofasr_sr_loss_ssim_workspace(N, H, W), o.device)
+            with _timed("sr_loss_ssim_fwd", nbytes):
+                _C.check(L.ofasr_sr_loss_ssim_fwd(_p(o), _dt(o), _p(t), _dt(t), None if s is None else _p(s),
+                                                  0 if s is None else _dt(s), N, H, W, kind, eps, w_main, w_kd, count, alpha,
+                                                  _p(res), wsp, wsn, _stream()), "sr_loss_ssim_fwd")
+        else:
+            wst, wsp, wsn = _ws(L.ofasr_sr_loss_workspace(o.numel()), o.device)
+            with _timed("sr_loss_fwd", nbytes):
+                _C.check(L.ofasr_sr_loss_fwd(_p(o), _dt(o), _p(t), _dt(t), None if s is None else _p(s),
+                                             0 if s is None else _dt(s), N, H, W, kind, eps, w_main, w_kd, count, _p(res),
+                                             wsp, wsn, _stream()), "sr_loss_fwd")
         ctx.save_for_backward(o)
-        ctx.cfg = (t, s, kind, eps, w_main, w_kd)
-        return res[SR_LOSS_VALUE_F32:].view(torch.float32)[0]
+        ctx.cfg = (t, s, kind, eps, w_main, w_kd, alpha)
+        return res[SR_LOSS_VALUE_F32:SR_LOSS_VALUE_F32 + 1].view(torch.float32)[0]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         o, = ctx.saved_tensors
-        t, s, kind, eps, w_main, w_kd = ctx.cfg
+        t, s, kind, eps, w_main, w_kd, alpha = ctx.cfg
         if not g.is_cuda or g.dtype != torch.float32:
             raise _C.OfasrError("sr_loss: the incoming gradient is a float32 GPU scalar, got %s on %s" % (g.dtype, g.device))
         g = g.contiguous()
         N, _, H, W = o.shape
         grad = torch.empty_like(o)
         nbytes = sum(x.numel() * x.element_size() for x in (o, o, t, s) if x is not None)
+        if alpha > 0:
+            with _timed("sr_loss_ssim_bwd", nbytes):
+                _C.check(_C.lib().ofasr_sr_loss_ssim_bwd(_p(o), _dt(o), _p(t), _dt(t), None if s is None else _p(s),
+                                                         0 if s is None else _dt(s), _p(g), N, H, W, kind, eps, w_main,
+                                                         w_kd, alpha, _p(grad), _stream()), "sr_loss_ssim_bwd")
+            return grad, None
         with _timed("sr_loss_bwd", nbytes):
             _C.check(_C.lib().ofasr_sr_loss_bwd(_p(o), _dt(o), _p(t), _dt(t), None if s is None else _p(s),
                                                 0 if s is None else _dt(s), _p(g), N, H, W, kind, eps, w_main, w_kd,
@@ -500,15 +515,23 @@ class _SrLossFn(Function):
         return grad, None
 
 
-def sr_loss(output, target, soft=None, kind="l1", eps=1e-3, w_main=1.0, w_kd=0.0, psnr_count=None, out=None):
+def sr_loss(output, target, soft=None, kind="l1", eps=1e-3, w_main=1.0, w_kd=0.0, psnr_count=None, out=None, ssim=0.0):
     """(loss, result): the training loss w_main * mean rho(output - target) + w_kd * mean rho(output - soft) as a
     differentiable 0-dim float32 tensor, and the fp64 [6] result buffer it is a view of (slots SR_LOSS_*: the two fp64
     sums, the loss in fp64, the bits of the exact int64 Y-SSE of output against target, its Y-PSNR over `psnr_count`
     pixels -- default N * H * W --, fp32(loss)).  `kind`: "mse", "l1" or "charbonnier" (`eps`); the definition is
     losses.py.  output, target and soft are [N, 3, H, W] GPU batches of f32 / f16 / bf16, each on its own; the gradient
     reaches `output` alone, in its dtype.  Two launches forward, one backward, no ATen kernel and no host sync
-    (ofasr_sr_loss_fwd / ofasr_sr_loss_bwd, csrc/loss.hip).  `out`: a contiguous fp64 [6] GPU tensor to write into."""
+    (ofasr_sr_loss_fwd / ofasr_sr_loss_bwd, csrc/loss.hip).  `out`: a contiguous fp64 [6] GPU tensor to write into.
+    `ssim` = alpha in (0, 1]: the loss is (1 - alpha) * that + alpha * (1 - S), S the mean SSIM of output against target
+    per colour plane (losses.ssim_np; H, W >= 11); the result buffer is fp64 [8] with the sum of SSIM and S in slots
+    SR_LOSS_SSIM_SUM and SR_LOSS_SSIM; three launches forward, one backward (ofasr_sr_loss_ssim_fwd / _bwd).  0: none of
+    that, the path above as it is."""
     from . import losses
+    ssim = float(ssim)
+    if not (0.0 <= ssim <= 1.0):
+        raise _C.OfasrError("sr_loss: ssim is a weight in [0, 1], got %r" % (ssim,))
+    slots = 8 if ssim > 0 else 6
     if kind not in losses.KINDS:
         raise _C.OfasrError("sr_loss: unknown kind %r (one of %s)" % (kind, ", ".join(losses.KINDS)))
     if output.dim() != 4 or output.size(1) != 3:
@@ -517,18 +540,25 @@ def sr_loss(output, target, soft=None, kind="l1", eps=1e-3, w_main=1.0, w_kd=0.0
         if x is not None and (x.shape != output.shape or x.device != output.device):
             raise _C.OfasrError("sr_loss: %s is %s on %s, output is %s on %s"
                                 % (what, tuple(x.shape), x.device, tuple(output.shape), output.device))
+    if ssim > 0:
+        if output.size(2) < 11 or output.size(3) < 11:
+            raise _C.OfasrError("sr_loss: a %dx%d plane has a side below the 11-pixel SSIM window"
+                                % (output.size(2), output.size(3)))
+        if out is not None and tuple(out.shape) != (slots,):
+            raise _C.OfasrError("sr_loss: with an SSIM term out must be a contiguous fp64 [8] tensor, got %s"
+                                % (tuple(out.shape),))
     _gpu(output, target, soft, out)
     for x in (output, target, soft):
         if x is not None:
             _dt(x)
     if out is None:
-        out = torch.empty(6, dtype=torch.float64, device=output.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (6,) or not out.is_contiguous() or out.device != output.device:
-        raise _C.OfasrError("sr_loss: out must be a contiguous fp64 [6] tensor on %s" % output.device)
+        out = torch.empty(slots, dtype=torch.float64, device=output.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (slots,) or not out.is_contiguous() or out.device != output.device:
+        raise _C.OfasrError("sr_loss: out must be a contiguous fp64 [%d] tensor on %s" % (slots, output.device))
     N, _, H, W = output.shape
     count = float(N * H * W if psnr_count is None else psnr_count)
     cfg = (target.detach().contiguous(), None if soft is None else soft.detach().contiguous(), out,
-           losses.KINDS.index(kind), float(eps), float(w_main), float(w_kd), count)
+           losses.KINDS.index(kind), float(eps), float(w_main), float(w_kd), count, ssim)
     return _SrLossFn.apply(output, cfg), out
 
 

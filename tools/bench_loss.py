@@ -9,7 +9,11 @@ the fused path with kind mse, l1 and charbonnier):
     and the wall time per section of `--reps` back-to-back runs ended by one synchronise (what a host-bound step pays);
   * the three new kernels alone, from the library's per-launch events, against the bytes they move at the 8.0 TB/s HBM
     peak and the 6.3 TB/s measured copy rate.
-Prints one JSON line.  usage: python tools/bench_loss.py [--reps 200] [--warmup 20]"""
+The SSIM section (key "ssim"): on the same tensors, ops.sr_loss(ssim=A) for each kind, without /
+with the teacher term, against an ATen statement of the same loss -- fp32, the five moments as one grouped F.conv2d with
+the 11 x 11 window each, autograd -- with launches, device time and wall time of forward plus backward for both, the two
+alternating in one process, and the SSIM kernels alone from the library's per-launch events.
+Prints one JSON line.  usage: python tools/bench_loss.py [--reps 200] [--warmup 20] [--ssim 0.2]"""
 import argparse
 import importlib
 import json
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shape", default="16x256x256")
     ap.add_argument("--no-launch-count", action="store_true", help="leave torch.profiler out")
+    ap.add_argument("--ssim", type=float, default=0.2, metavar="A", help="the SSIM weight of the SSIM section (0: skip it)")
     a = ap.parse_args()
     import torch
     import torch.nn.functional as F
@@ -64,6 +69,41 @@ def main():
                                 psnr_count=count)
         loss.backward()
         return loss, res[ops.SR_LOSS_PSNR]
+
+    def fused_ssim(kind, teacher):
+        out16.grad = None
+        w_main, w_kd = losses.kd_weights(kd, True) if teacher else (1.0, 0.0)
+        loss, res = ops.sr_loss(out16, images, soft if teacher else None, kind=kind, w_main=w_main, w_kd=w_kd,
+                                psnr_count=count, ssim=a.ssim)
+        loss.backward()
+        return loss, res[ops.SR_LOSS_SSIM]
+
+    gw = torch.from_numpy(losses.ssim_window()).float().cuda()
+    win = (gw[:, None] * gw[None, :])[None, None].repeat(3, 1, 1, 1).contiguous()
+    eps2 = float(losses.eps2_f32(losses.DEFAULT_EPS))
+
+    def rho(x, kind):
+        if kind == "mse":
+            return (x * x).mean()
+        if kind == "l1":
+            return x.abs().mean()
+        return torch.sqrt(x * x + eps2).mean()
+
+    def aten_ssim(kind, teacher):
+        """the same loss through ATen in fp32 (no PSNR: the loss alone)"""
+        out16.grad = None
+        w_main, w_kd = losses.kd_weights(kd, True) if teacher else (1.0, 0.0)
+        o = out16.float()
+        pix = w_main * rho(o - images, kind)
+        if teacher:
+            pix = pix + w_kd * rho(o - soft, kind)
+        conv = lambda x: F.conv2d(x, win, groups=3)
+        m1, m2 = conv(o), conv(images)
+        s1, s2, s12 = conv(o * o) - m1 * m1, conv(images * images) - m2 * m2, conv(o * images) - m1 * m2
+        S = (((2 * m1 * m2 + 1e-4) * (2 * s12 + 9e-4)) / ((m1 * m1 + m2 * m2 + 1e-4) * (s1 + s2 + 9e-4))).mean()
+        loss = (1.0 - a.ssim) * pix + a.ssim * (1.0 - S)
+        loss.backward()
+        return loss, S
 
     def launches(fn):
         if a.no_launch_count:
@@ -142,6 +182,30 @@ def main():
                                        "TBps": by / us * 1e-6 if us else None,
                                        "fraction_of_hbm_peak": by / us * 1e-6 / HBM_TBPS if us else None,
                                        "fraction_of_copy_rate": by / us * 1e-6 / COPY_TBPS if us else None})
+    if a.ssim > 0:
+        out["ssim"] = {"alpha": a.ssim, "sections": [], "kernels": []}
+        for teacher in (False, True):
+            variants = [("fused", k, (lambda k=k: fused_ssim(k, teacher))) for k in losses.KINDS]
+            variants += [("aten", k, (lambda k=k: aten_ssim(k, teacher))) for k in losses.KINDS]
+            dev = device_us([fn for _, _, fn in variants])
+            for (path, kind, fn), d in zip(variants, dev):
+                loss, S = fn()
+                out["ssim"]["sections"].append({"path": path, "loss": kind, "teacher": teacher, "gpu_launches": launches(fn),
+                                                "device_us": d, "wall_us": wall_us(fn), "value": float(loss.detach()),
+                                                "S": float(S.detach())})
+            for kind in losses.KINDS:
+                fused_ssim(kind, teacher)
+                sync()
+                L.ofasr_profile_enable(1)
+                C.profile_read()
+                for _ in range(a.reps):
+                    fused_ssim(kind, teacher)
+                prof = C.profile_read()
+                L.ofasr_profile_enable(0)
+                for sym, v in sorted(prof.items()):
+                    if "sr_loss" in sym or "sr_ssim" in sym:
+                        out["ssim"]["kernels"].append({"kernel": sym, "kind": kind, "teacher": teacher,
+                                                       "us": v["total_us"] / v["launches"]})
     print(json.dumps(out))
 
 

@@ -45,11 +45,15 @@ def main():
                     help="training loss: reference = nn.MSELoss through ATen, as ever; the others run the fused HIP "
                          "loss kernels (ops.sr_loss)")
     ap.add_argument("--loss-eps", type=float, default=None, metavar="E", help="the Charbonnier eps (default 1e-3)")
+    ap.add_argument("--loss-ssim", type=float, default=0.0, metavar="A",
+                    help="weight of an SSIM term: (1 - A) * loss + A * (1 - SSIM), A in [0, 1] (0: off); needs a fused "
+                         "--loss")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     vf.add_degrade_args(ap)
     args = ap.parse_args()
-    loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, args.loss, args.__dict__.pop("loss_eps"))
+    loss_ssim = args.__dict__.pop("loss_ssim")
+    loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, args.loss, args.__dict__.pop("loss_eps"), loss_ssim)
     loss = args.__dict__.pop("loss")        # `args` goes into the run config: it stays what it always was
     video_kw = vf.take_video_args(args)     # None without --video: `args` is then what it always was
     args.__dict__.update(vf.take_crop_candidates(args, args.resident or bool(video_kw)))    # nothing with K = 1
@@ -140,7 +144,7 @@ def main():
               pixelshuffle_depth_list=args.pixelshuffle_depth_list)
     run_manager = rm.SRRunManager(args.path, net, run_config, mix_prec=args.mix_prec,
                                   num_gpus=int(os.environ.get("WORLD_SIZE", "1")), args=args, loss=loss,
-                                  loss_eps=loss_eps)
+                                  loss_eps=loss_eps, loss_ssim=loss_ssim)
     run_manager.save_config()
 
     validate_func_dict = {"image_size_list": None, "width_mult_list": None,
