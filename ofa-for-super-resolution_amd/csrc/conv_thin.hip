@@ -30,6 +30,7 @@
 // (conv_thin_*_supported); unsupported shapes keep the implicit-GEMM kernels.
 #include <stdlib.h>
 #include "ofasr_common.h"
+#include "conv_thin_addr.h"   // the work split, the block mappings and every global offset of a possibly masked lane
 
 namespace ofasr {
 
@@ -41,19 +42,11 @@ typedef __attribute__((ext_vector_type(8))) short ct_s16x8;
 typedef __attribute__((ext_vector_type(4))) unsigned int ct_u32x4;
 typedef __attribute__((address_space(3))) ct_s16x4 ct_lds_s16x4;
 
-constexpr int CT_ROWB = 288;             // bytes per channel row of a staged image row: 18 chunks of 16 B (72 dwords = 8 mod 64:
-                                         // the 8 channel rows a half-wave's transposing read touches fall on disjoint banks)
-constexpr int CT_CHUNKS = 18;
-constexpr int CT_D = 4;                  // image rows requested ahead of the one being computed
-constexpr int CT_PSTRIDE = 148;          // floats per row of the P image (4 * 148 = 16 mod 32: the two 16-lane groups of a
-                                         // half-wave store to disjoint banks)
-
 template <typename T> struct CtElem;
-template <> struct CtElem<bf16_t> { static constexpr bool is16 = true; static constexpr int CW = 128, EPC = 8; };
-template <> struct CtElem<f16_t> { static constexpr bool is16 = true; static constexpr int CW = 128, EPC = 8; };
-template <> struct CtElem<float> { static constexpr bool is16 = false; static constexpr int CW = 64, EPC = 4; };
-// CW: output columns per strip; EPC: elements per 16-byte chunk.  A staged row holds CT_CHUNKS * EPC columns starting at
-// column x0 - EPC (one chunk of left halo, one of right halo).
+template <> struct CtElem<bf16_t> { static constexpr bool is16 = true; static constexpr int CW = ct_cw(2), EPC = ct_epc(2); };
+template <> struct CtElem<f16_t> { static constexpr bool is16 = true; static constexpr int CW = ct_cw(2), EPC = ct_epc(2); };
+template <> struct CtElem<float> { static constexpr bool is16 = false; static constexpr int CW = ct_cw(4), EPC = ct_epc(4); };
+// CW: output columns per strip; EPC: elements per 16-byte chunk (conv_thin_addr.h)
 
 template <typename T> __device__ __forceinline__ ct_f32x4 ct_mma16(ct_s16x8 a, ct_s16x8 b, ct_f32x4 c);
 template <> __device__ __forceinline__ ct_f32x4 ct_mma16<bf16_t>(ct_s16x8 a, ct_s16x8 b, ct_f32x4 c) {
@@ -94,12 +87,6 @@ __device__ __forceinline__ void ct_stage_weights(float* dst, const float* w, int
     for (int i = tid; i < count; i += nthreads) dst[i] = w[i];
 }
 
-struct CtGeom {
-    int N, H, W;        // images, rows, columns
-    int Ct, Cw;         // thin / wide channel counts
-    int strips, segs, RS;   // column strips per row, row segments per image, rows per segment
-};
-
 // ------------------------------------------------------------------------------------------------------------------
 // thin OUTPUT: X [N][Cw][H][W] -> out [N][Ct][H][W], Ct * K <= 16, Cw = 32 * NC
 //
@@ -114,12 +101,9 @@ template <typename T> struct CtOut {
     static constexpr bool is16 = CtElem<T>::is16;
     static constexpr int THREADS = is16 ? 576 : 512;
     static constexpr int NT = is16 ? 9 : 5;                // 16-column tiles
-    static constexpr int PSTR = is16 ? CT_PSTRIDE : 84;    // floats per P row (4 * PSTR = 16 mod 32)
-    static constexpr int ring_rows(int K) { return is16 ? K + 1 : K; }
-    static constexpr int planes(int K, int NC) { return is16 ? 2 : K * NC; }
-    static constexpr size_t lds_bytes(int K, int NC) {
-        return (size_t)ring_rows(K) * 32 * NC * CT_ROWB + (size_t)planes(K, NC) * 16 * PSTR * sizeof(float);
-    }
+    static constexpr int PSTR = is16 ? CT_PSTRIDE : CT_PSTRIDE_F32;    // floats per P row (4 * PSTR = 16 mod 32)
+    static constexpr int ring_rows(int K) { return ct_out_ring_rows(is16, K); }
+    static constexpr size_t lds_bytes(int K, int NC) { return ct_out_lds_bytes(is16, K, NC); }
 };
 
 template <typename T, int K, int NC>
@@ -138,21 +122,8 @@ __global__ __launch_bounds__(CtOut<T>::THREADS) void ct_out_kernel(const T* __re
     float* Pb = reinterpret_cast<float*>(smem + RR * ROW_BYTES);   // [planes][16][PSTR]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // The strips of one (image, segment) request each other's edge lines (a 16-byte halo chunk lies in the neighbour's
-    // 128-byte line), so they must share an L2: workgroups go to the 8 XCDs round robin by blockIdx, hence the strips of
-    // a unit are 8 apart in blockIdx and run side by side on one XCD (measured without: 1.95x the algorithmic reads).
-    int strip, unit;
-    {
-        const int b = blockIdx.x, units = g.N * g.segs;
-        if (units % 8 == 0) {
-            const int grp = b / (8 * g.strips), rem = b % (8 * g.strips);
-            strip = rem / 8;
-            unit = grp * 8 + rem % 8;
-        } else {
-            strip = b % g.strips;
-            unit = b / g.strips;
-        }
-    }
+    int strip, unit;   // the strips of a unit on one XCD where the unit count allows it (conv_thin_addr.h)
+    ct_block_map((int)blockIdx.x, g.N * g.segs, g.strips, strip, unit);
     const int seg = unit % g.segs;
     const int n = unit / g.segs;
     const int x0 = strip * CW;
@@ -206,22 +177,18 @@ __global__ __launch_bounds__(CtOut<T>::THREADS) void ct_out_kernel(const T* __re
         // slots beyond the row's chunk count wrap around: such a lane requests and writes a chunk some other lane handles
         // as well (same bytes to the same place).  A slot that is skipped under a branch instead leaves its request
         // "pending" on that path in the compiler's wait-count analysis, which then drains ALL requests at every re-use.
-        const int id = (q * THREADS + tid) % NCH;
-        const int c = id / CT_CHUNKS, jc = id % CT_CHUNKS;
-        const int col = x0 - EPC + jc * EPC;
-        col_ok[q] = col >= 0 && col < g.W;
-        ch_off[q] = c * CT_ROWB + jc * 16;
-        g_off[q] = (long long)c * plane + (col_ok[q] ? col : 0);
+        const CtOutChunk k = ct_out_chunk((q * THREADS + tid) % NCH, x0, EPC, g.W, plane);
+        col_ok[q] = k.col_ok;
+        ch_off[q] = k.c * CT_ROWB + k.jc * 16;
+        g_off[q] = k.g_off;
     }
     ct_u32x4 stage[CT_D][SLOTS];
     auto request = [&](int d, int row) {
-        // rows above / below the image are zero (handled at the LDS write); the request itself goes to a clamped row,
-        // and rows beyond what this segment needs re-request the last needed row (a cache hit, no HBM traffic)
-        int r = min(row, min(ye - 1 + P, g.H - 1));
-        r = max(r, 0);
+        // rows above / below the image are zero (handled at the LDS write); the request itself goes to a clamped row
+        const int r = ct_out_request_row(row, ye, P, g.H);
 #pragma unroll
         for (int q = 0; q < SLOTS; ++q)
-            stage[d][q] = *reinterpret_cast<const ct_u32x4*>(Xn + g_off[q] + (long long)r * g.W);
+            stage[d][q] = *reinterpret_cast<const ct_u32x4*>(Xn + g_off[q] + ct_row_off(r, g.W));
     };
     auto deposit = [&](int d, int row) {
         const bool row_ok = row >= 0 && row < g.H;
@@ -240,10 +207,10 @@ __global__ __launch_bounds__(CtOut<T>::THREADS) void ct_out_kernel(const T* __re
         ct_u32x4 pro[K][SLOTS];
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            const int r = max(min(ys - P + i, g.H - 1), 0);
+            const int r = ct_out_prologue_row(ys, P, i, g.H);
 #pragma unroll
             for (int q = 0; q < SLOTS; ++q)
-                pro[i][q] = *reinterpret_cast<const ct_u32x4*>(Xn + g_off[q] + (long long)r * g.W);
+                pro[i][q] = *reinterpret_cast<const ct_u32x4*>(Xn + g_off[q] + ct_row_off(r, g.W));
         }
 #pragma unroll
         for (int d = 1; d < CT_D; ++d) request((2 * P + d) % CT_D, ys + P + d);   // input row i lives in set (i - (ys - P)) % CT_D
@@ -396,17 +363,11 @@ __global__ __launch_bounds__(CtOut<T>::THREADS) void ct_out_kernel(const T* __re
 // The thin rows of the whole segment (+ halo) are loaded once into LDS (a few tens of KB), so the row loop has no global
 // request in it; the wide result goes through a double-buffered [channel][column] LDS tile to 16-byte row stores.
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int CT_IN_THREADS = 512;
-constexpr int CT_OSTR = 272;   // bytes per channel row of the output tile: 68 dwords = 4 mod 32 (2-way at worst, the minimum)
-constexpr int CT_IN_MAXRS = 64;
-
 template <typename T> struct CtIn {
     static constexpr bool is16 = CtElem<T>::is16;
     static constexpr int CTILES = CtElem<T>::CW / 16;        // column tiles per strip: 8 (16-bit), 4 (fp32)
     static constexpr int WPT = 8 / CTILES;                   // waves per column tile: 1 / 2
-    static constexpr size_t lds_bytes(int K, int Ct, int Cw, int RS) {
-        return (size_t)(RS + K - 1) * Ct * CT_ROWB + 2 * (size_t)Cw * CT_OSTR + 64;
-    }
+    static constexpr size_t lds_bytes(int K, int Ct, int Cw, int RS) { return ct_in_lds_bytes(K, Ct, Cw, RS); }
 };
 
 template <typename T, int K, int NM>
@@ -421,18 +382,8 @@ __global__ __launch_bounds__(CT_IN_THREADS) void ct_in_kernel(const T* __restric
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    int strip, unit;
-    {
-        const int b = blockIdx.x, units = g.N * g.segs;
-        if (units % 8 == 0) {   // (as ct_out_kernel: the strips of a unit on one XCD -- they share the thin rows in L2)
-            const int grp = b / (8 * g.strips), rem = b % (8 * g.strips);
-            strip = rem / 8;
-            unit = grp * 8 + rem % 8;
-        } else {
-            strip = b % g.strips;
-            unit = b / g.strips;
-        }
-    }
+    int strip, unit;   // (as ct_out_kernel: the strips of a unit on one XCD -- they share the thin rows in L2)
+    ct_block_map((int)blockIdx.x, g.N * g.segs, g.strips, strip, unit);
     const int seg = unit % g.segs, n = unit / g.segs;
     const int x0 = strip * CW;
     const int ys = seg * g.RS, ye = min(ys + g.RS, g.H);
@@ -452,14 +403,13 @@ __global__ __launch_bounds__(CT_IN_THREADS) void ct_in_kernel(const T* __restric
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int id = min(id0 + u * CT_IN_THREADS + tid, total - 1);   // (the tail repeats the last chunk)
-                const int jc = id % CT_CHUNKS, rc = id / CT_CHUNKS;
-                const int t = rc % g.Ct, row = ys - P + rc / g.Ct;
-                const int col = x0 - EPC + jc * EPC;
-                const bool ok = row >= 0 && row < g.H && col >= 0 && col < g.W;
-                const long long src = (long long)t * plane + (long long)(ok ? row : 0) * g.W + (ok ? col : 0);
+                const CtThinItem k = ct_thin_item(id, CT_CHUNKS, g.Ct, ys, P);
+                const int col = CT_CHUNK_COL(x0, k.jc, EPC);              // (the macros: see conv_thin_addr.h)
+                const bool ok = CT_THIN_OK(k.row, col, g.H, g.W);
+                const long long src = ct_thin_src(k.t, k.row, col, g.W, plane, ok);
                 v[u] = *reinterpret_cast<const ct_u32x4*>(In_n + src);
                 if (!ok) v[u] = ct_u32x4{0u, 0u, 0u, 0u};
-                off[u] = rc * CT_ROWB + jc * 16;
+                off[u] = k.rc * CT_ROWB + k.jc * 16;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) *reinterpret_cast<ct_u32x4*>(thin + off[u]) = v[u];
@@ -587,14 +537,14 @@ __global__ __launch_bounds__(CT_IN_THREADS) void ct_in_kernel(const T* __restric
         }
         ct_lds_barrier();
         // read the tile out row-wise: CWD channels x 16 chunks of 16 bytes
-        T* orow = out + (long long)n * g.Cw * plane + (long long)r * g.W + x0;
+        T* orow = out + CT_IN_STORE_ROW(n, g.Cw, plane, r, g.W, x0);
 #pragma unroll
         for (int u = 0; u < (CWD * 16 + CT_IN_THREADS - 1) / CT_IN_THREADS; ++u) {
             const int id = u * CT_IN_THREADS + tid;
             const int c = id >> 4, ch = id & 15;
-            if (id < CWD * 16 && x0 + ch * EPC < g.W) {
+            if (CT_IN_STORE_LIVE(id, ch, CWD, x0, EPC, g.W)) {
                 const ct_u32x4 v = *reinterpret_cast<const ct_u32x4*>(ob + c * CT_OSTR + ch * 16);
-                *reinterpret_cast<ct_u32x4*>(orow + (long long)c * plane + ch * EPC) = v;
+                *reinterpret_cast<ct_u32x4*>(orow + ct_in_store_chan_off(id, plane) + ct_in_store_col_off(id, EPC)) = v;
             }
         }
         // (no second barrier: the next row writes the other tile; the row after that is behind the next barrier)
@@ -639,15 +589,7 @@ __global__ __launch_bounds__(CT_IN_THREADS) void ct_in_kernel(const T* __restric
 // in registers; at the end the waves add their tiles into one LDS slab in wave order and the block writes the slab;
 // ct_wg_reduce_kernel sums the slabs in block order into the parameter's gradient (deterministic, no atomics).
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int CT_WG_THREADS = 512;
 constexpr int CT_WPD = 3;          // items whose wide fragments are in flight ahead of the one being multiplied
-
-struct CtWgGeom {
-    int N, H, W, Ct, Cw;
-    int segs, RS;          // row segments per image, rows per segment
-    int nchunks;           // 32-pixel chunks per row
-    int trow;              // bytes per (row, channel) of the thin LDS image: (W + 16 + pad) elements
-};
 
 template <typename T, int K, int NT>
 __global__ __launch_bounds__(CT_WG_THREADS) void ct_wg_kernel(const T* __restrict__ Thin, const T* __restrict__ Wide,
@@ -655,7 +597,7 @@ __global__ __launch_bounds__(CT_WG_THREADS) void ct_wg_kernel(const T* __restric
     constexpr bool is16 = CtElem<T>::is16;
     constexpr int EPC = CtElem<T>::EPC, P = K / 2, ES = (int)sizeof(T);
     constexpr int BV = is16 ? 1 : 2;                  // 16-byte requests per lane and channel tile
-    constexpr int HALO = 8;                           // thin image: column index = column + HALO
+    constexpr int HALO = CT_WG_HALO;                  // thin image: column index = column + HALO
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int seg = blockIdx.x % g.segs, n = blockIdx.x / g.segs;
@@ -675,14 +617,13 @@ __global__ __launch_bounds__(CT_WG_THREADS) void ct_wg_kernel(const T* __restric
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int id = min(id0 + u * CT_WG_THREADS + tid, total - 1);
-                const int jc = id % cpr, rc = id / cpr;
-                const int t = rc % g.Ct, row = ys - P + rc / g.Ct;
-                const int col = jc * EPC - HALO;
-                const bool ok = row >= 0 && row < g.H && col >= 0 && col < g.W;
-                const long long src = (long long)t * plane + (long long)(ok ? row : 0) * g.W + (ok ? col : 0);
+                const CtThinItem k = ct_thin_item(id, cpr, g.Ct, ys, P);
+                const int col = ct_wg_chunk_col(k.jc, EPC);
+                const bool ok = ct_thin_ok(k.row, col, g.H, g.W);
+                const long long src = ct_thin_src(k.t, k.row, col, g.W, plane, ok);
                 v[u] = *reinterpret_cast<const ct_u32x4*>(Tn + src);
                 if (!ok) v[u] = ct_u32x4{0u, 0u, 0u, 0u};
-                off[u] = rc * g.trow + jc * 16;
+                off[u] = k.rc * g.trow + k.jc * 16;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) *reinterpret_cast<ct_u32x4*>(thin + off[u]) = v[u];
@@ -698,7 +639,7 @@ __global__ __launch_bounds__(CT_WG_THREADS) void ct_wg_kernel(const T* __restric
     const int a_lane = mt * g.trow + (is16 ? (ja & ~1) * 2 : ja * 4);
     const int sh = (ja & 1) * 16;
     const T* Wn = Wide + (long long)n * g.Cw * plane;
-    const long long b_lane = (long long)l16 * plane + 8 * kg;     // + tile * 16 * plane + row * W + xb
+    const long long b_lane = ct_wg_wide_lane(l16, plane);         // + tile * 16 * plane + row * W + the clamped column
 
     ct_f32x4 acc[K][NT];
 #pragma unroll
@@ -712,14 +653,15 @@ __global__ __launch_bounds__(CT_WG_THREADS) void ct_wg_kernel(const T* __restric
     ct_u32x4 bst[CT_WPD][NT][BV];
     auto request = [&](int d, int it) {
         const int i = min(wave + 8 * it, nitems - 1);            // items beyond the block's last repeat it (and contribute zero)
-        const int row = ys + i / g.nchunks, xb = 32 * (i % g.nchunks);
-        const bool ok = xb + 8 * kg < g.W;                        // (W % 8 == 0: the 8 pixels are all in or all out)
-        const T* src = Wn + b_lane + (long long)row * g.W + (ok ? xb : 0);
+        int row, xb;
+        ct_wg_item(i, g.nchunks, ys, row, xb);
+        // the whole column xb + 8 kg is clamped, not xb alone: a lane group past the row's end must not request past it
+        const T* src = Wn + b_lane + ct_wg_wide_rowcol(row, xb, kg, g.W);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int q = 0; q < BV; ++q)
-                bst[d][nt][q] = *reinterpret_cast<const ct_u32x4*>(src + (long long)nt * 16 * plane + q * 4);
+                bst[d][nt][q] = *reinterpret_cast<const ct_u32x4*>(src + ct_wg_wide_tile_off(nt, plane) + ct_wg_wide_half_off(q));
     };
 #pragma unroll
     for (int d = 0; d < CT_WPD - 1; ++d) request(d, d);
@@ -850,18 +792,9 @@ static int ct_num_cus() {
     return n;
 }
 
+// the work splits of conv_thin_addr.h on this device
 template <typename T> static CtGeom ct_geom(int64_t N, int64_t Ct, int64_t Cw, int64_t H, int64_t W) {
-    CtGeom g{};
-    g.N = (int)N; g.H = (int)H; g.W = (int)W; g.Ct = (int)Ct; g.Cw = (int)Cw;
-    g.strips = (int)cdiv(W, CtElem<T>::CW);
-    // one workgroup per CU: as few row segments as that allows (every segment re-reads 2 * (k / 2) halo rows)
-    const int64_t units = N * g.strips;
-    int64_t segs = cdiv(ct_num_cus(), units);
-    int64_t RS = cdiv(H, segs < 1 ? 1 : segs);
-    if (RS < 8) RS = H < 8 ? H : 8;
-    g.RS = (int)RS;
-    g.segs = (int)cdiv(H, RS);
-    return g;
+    return ct_geom(N, Ct, Cw, H, W, (int)sizeof(T), ct_num_cus());
 }
 
 bool conv_thin_enabled() {
@@ -870,12 +803,7 @@ bool conv_thin_enabled() {
 }
 
 template <typename T> static CtGeom ct_geom_in(int64_t N, int64_t Ct, int64_t Cw, int64_t H, int64_t W) {
-    CtGeom g = ct_geom<T>(N, Ct, Cw, H, W);
-    if (g.RS > CT_IN_MAXRS) {       // the thin rows of a whole segment live in LDS
-        g.RS = CT_IN_MAXRS;
-        g.segs = (int)cdiv(H, g.RS);
-    }
-    return g;
+    return ct_geom_in(N, Ct, Cw, H, W, (int)sizeof(T), ct_num_cus());
 }
 
 bool conv_thin_in_supported(int64_t Ct, int64_t Cw, int K, int64_t W, int dtype, const void* x, const void* y) {
@@ -894,7 +822,7 @@ static void ct_in_launch(const void* x, CtW Wt, void* y, const CtGeom& g, StatOu
     const size_t lds = CtIn<T>::lds_bytes(K, g.Ct, g.Cw, g.RS);
     static bool attr = [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ct_in_kernel<T, K, NM>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)CT_LDS_LIMIT);
         return true;
     }();
     (void)attr;
@@ -921,20 +849,7 @@ int conv_thin_in(const void* x, const float* w, void* y, int64_t N, int64_t Ct, 
 }
 
 static CtWgGeom ct_wg_geom(int64_t N, int64_t Ct, int64_t Cw, int64_t H, int64_t W, int es) {
-    CtWgGeom g{};
-    g.N = (int)N; g.H = (int)H; g.W = (int)W; g.Ct = (int)Ct; g.Cw = (int)Cw;
-    g.nchunks = (int)cdiv(W, 32);
-    // bytes per (row, channel): columns -8 .. 32 * nchunks + 8 + 2 (the funnel shift reads one dword further)
-    g.trow = (int)((32 * g.nchunks + 24) * es + 15) / 16 * 16;
-    int64_t segs = cdiv(ct_num_cus(), N);
-    int64_t RS = cdiv(H, segs < 1 ? 1 : segs);
-    // a block's fixed costs (thin image, the waves' fold, its 20 KB slab) want >= 8 items per wave
-    const int64_t min_rows = cdiv(64, g.nchunks);
-    if (RS < min_rows) RS = H < min_rows ? H : min_rows;
-    while (RS > 4 && (RS + 4) * Ct * g.trow > 96 * 1024) RS = (RS + 1) / 2;
-    g.RS = (int)RS;
-    g.segs = (int)cdiv(H, RS);
-    return g;
+    return ct_wg_geom(N, Ct, Cw, H, W, es, ct_num_cus());
 }
 
 bool conv_thin_wgrad_supported(int64_t Ct, int64_t Cw, int K, int64_t H, int64_t W, int dtype, const void* a, const void* b) {
@@ -951,12 +866,10 @@ size_t conv_thin_wgrad_workspace(int64_t N, int64_t Ct, int64_t Cw, int64_t H, i
 
 template <typename T, int K, int NT>
 static void ct_wg_launch(const void* thin, const void* wide, float* slabs, const CtWgGeom& g, hipStream_t st) {
-    size_t lds = (size_t)(g.RS + K - 1) * g.Ct * g.trow;
-    const size_t slab = (size_t)K * NT * 256 * sizeof(float);
-    if (lds < slab) lds = slab;
+    const size_t lds = ct_wg_lds_bytes(K, NT, g.RS, g.Ct, g.trow);
     static bool attr = [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ct_wg_kernel<T, K, NT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)CT_LDS_LIMIT);
         return true;
     }();
     (void)attr;
@@ -1011,7 +924,7 @@ static void ct_out_launch(const void* x, CtW Wt, void* y, const CtGeom& g, StatO
     const size_t lds = CtOut<T>::lds_bytes(K, NC);
     static bool attr = [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ct_out_kernel<T, K, NC>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)CT_LDS_LIMIT);
         return true;
     }();
     (void)attr;
