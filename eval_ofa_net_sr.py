@@ -23,14 +23,25 @@ def input_key(upscale):
     return "%dx_down_image" % upscale
 
 
-def export_static(supernet, out_dir):
-    """the supernet's active sub-network as a static network: out_dir/net_config.json + its state dict"""
+def load_checkpoint_weights(fname, ema=False):
+    """the state dict a checkpoint reader loads: checkpoint["state_dict"], or with `ema` (--ema) the averaged parameters
+    of a run with --ema-decay laid over it (ema.averaged_state_dict: a checkpoint without them is refused)"""
+    import torch
+    checkpoint = torch.load(fname, map_location="cpu", weights_only=True)
+    if not ema:
+        return checkpoint["state_dict"]
+    return importlib.import_module(PKG + ".ema").averaged_state_dict(checkpoint, fname)
+
+
+def export_static(supernet, out_dir, ema=False):
+    """the supernet's active sub-network as a static network: out_dir/net_config.json + its state dict.  `ema`: the
+    supernet holds averaged weights (--ema); net_config.json then records "ema": true"""
     import json
     import torch
     os.makedirs(out_dir, exist_ok=True)
     sub = supernet.get_active_subnet(preserve_weight=True)
     with open(os.path.join(out_dir, "net_config.json"), "w") as f:
-        json.dump(sub.config, f, indent=1)
+        json.dump(dict(sub.config, ema=True) if ema else sub.config, f, indent=1)
     torch.save({"state_dict": sub.state_dict()}, os.path.join(out_dir, STATIC_WEIGHTS))
     return sub
 
@@ -49,6 +60,8 @@ def load_static(in_dir):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--ema", action="store_true", help="with --checkpoint: load the averaged weights of a run with "
+                                                       "--ema-decay (the checkpoint's \"ema\" entry) instead of the raw ones")
     ap.add_argument("--path", default="exp/sr/eval")
     ap.add_argument("--ks", type=int, default=7)
     ap.add_argument("--expand", type=int, default=6)
@@ -79,7 +92,17 @@ def main(argv=None):
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     a = ap.parse_args(argv)
+    if a.ema and not a.checkpoint:
+        ap.error("--ema needs --checkpoint FILE (the averaged weights live in a training checkpoint's \"ema\" entry)")
+    if a.ema and a.static:
+        ap.error("--ema with --static: an exported network holds one set of weights (its net_config.json says which)")
     video_kw = vf.take_video_args(a)        # --video: evaluate on the evaluation frames of raw YUV 4:2:0 video
+    weights = None
+    if a.ema:                               # refused here, before anything is set up, when the file has no average
+        try:
+            weights = load_checkpoint_weights(a.checkpoint, ema=True)
+        except ValueError as e:
+            ap.error("--ema: %s" % e)
     degrade = None
     if a.degrade_blur is not None or a.degrade_noise is not None:
         dg = importlib.import_module(PKG + ".degrade")
@@ -128,11 +151,11 @@ def main(argv=None):
         key = input_key(net.upscale)
     else:
         if a.checkpoint:
-            net.load_weights_from_net(torch.load(a.checkpoint, map_location="cpu", weights_only=True)["state_dict"])
+            net.load_weights_from_net(load_checkpoint_weights(a.checkpoint) if weights is None else weights)
         net.set_active_subnet(ks=a.ks, e=a.expand, d=a.depth, pixel_d=a.pixelshuffle_depth)
         key = "4x_down_image" if a.pixelshuffle_depth == 2 or net.COMPAT_REFERENCE_INDEXING else "2x_down_image"
         if a.export:
-            export_static(net, a.export)
+            export_static(net, a.export, ema=a.ema)
     import time
     if degrade is not None:
         print("degraded LR inputs: blur sigma %g, noise sigma %g, seed %d" % degrade)

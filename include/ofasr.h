@@ -50,7 +50,7 @@ extern "C" {
 #endif
 
 /* major*100 + minor: the minor number moves whenever the exported set below changes (tests/test_abi.py reads it here) */
-#define OFASR_VERSION 316 /* + ofasr_sr_loss_ssim_workspace, ofasr_sr_loss_ssim_fwd, ofasr_sr_loss_ssim_bwd */
+#define OFASR_VERSION 317 /* + ofasr_ema_chunk, ofasr_ema_update, ofasr_ema_swap */
 
 typedef enum {
     OFASR_OK = 0,
@@ -703,6 +703,23 @@ int ofasr_d4_accumulate(const void* src, float* acc, int64_t N, int64_t C, int64
  * -- the long skip connection of the static networks in an eval-mode forward (ops.skip_add).  y may be a or b; any
  * element-aligned pointers (vector access only when all three are aligned for it); n <= 2^40. */
 int ofasr_add(const void* a, const void* b, void* y, int64_t n, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Weight EMA of training (ema.py): every parameter tensor of the network in ONE launch.
+ *   table  DEVICE memory, [rows, 3] int64: {parameter address, shadow address, count}, both fp32 ranges of `count`
+ *          elements, 1 <= count <= ofasr_ema_chunk(); a row never spans two tensors (ema.plan_chunks).  A count outside
+ *          that range is clamped into it by the kernel.  Element-aligned addresses: a row takes 16-byte accesses when
+ *          both of its addresses are 16-byte aligned and element accesses otherwise.
+ *   update: e = e + float32(w * float32(p - e)) per element -- three fp32 operations, each rounded once, never
+ *          contracted (ema.update_np gives the same bits); reads p and e, writes e only.  0 <= w <= 1.
+ *   swap:   exchanges the two ranges of every row element for element.
+ * The ranges of different rows must not overlap.  rows == 0 is success without a launch.  OFASR_ERR_INVALID_ARG:
+ * rows < 0, a null table with rows > 0, w not finite or outside [0, 1]; OFASR_ERR_UNSUPPORTED: rows > 2^30.
+ * ofasr_ema_chunk is host only: elements per table row, a multiple of 4.
+ * ------------------------------------------------------------------------------------------- */
+int64_t ofasr_ema_chunk(void);
+int ofasr_ema_update(const int64_t* table, int64_t rows, float w, void* stream);
+int ofasr_ema_swap(const int64_t* table, int64_t rows, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training augmentation on GPU-resident images: RandomCrop(S) -> RandomHorizontalFlip -> RandomRotation (nearest, same

@@ -162,6 +162,9 @@ SIGNATURES = {
     "ofasr_d4_accumulate": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, ctypes.c_float,
                                      _c_vp]),
     "ofasr_add": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp]),
+    "ofasr_ema_chunk": (_c_i64, []),
+    "ofasr_ema_update": (_c_int, [_c_vp, _c_i64, ctypes.c_float, _c_vp]),
+    "ofasr_ema_swap": (_c_int, [_c_vp, _c_i64, _c_vp]),
     "ofasr_aug_gather_u8": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
     "ofasr_aug_gather_yuv420": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ofasr_aug_gather_yuv420_pair": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp,

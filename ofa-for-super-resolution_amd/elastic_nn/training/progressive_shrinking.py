@@ -157,8 +157,10 @@ def train(run_manager, args, validate_func=None):
     for epoch in range(run_manager.start_epoch, run_manager.run_config.n_epochs + args.warmup_epochs):
         train_loss, train_psnr = train_one_epoch(run_manager, args, epoch, args.warmup_epochs, args.warmup_lr)
         if (epoch + 1) % args.validation_frequency == 0:
-            val_loss, val_acc, _val_log = validate_func(run_manager, epoch=epoch, is_test=True)
-            is_best = val_acc > run_manager.best_acc
+            with run_manager.ema_weights():    # with ema_decay: the averaged weights are what is validated and kept
+                val_loss, val_acc, _val_log = validate_func(run_manager, epoch=epoch, is_test=True)
+                is_best = val_acc > run_manager.best_acc
+                best_sd = run_manager.best_state_dict() if is_best else None
             run_manager.best_acc = max(run_manager.best_acc, val_acc)
             val_log = "Valid [{0}/{1}] loss={2:.3f}, top-1={3:.3f} ({4:.3f})".format(
                 epoch + 1 - args.warmup_epochs, run_manager.run_config.n_epochs, val_loss, val_acc,
@@ -170,7 +172,8 @@ def train(run_manager, args, validate_func=None):
             run_manager.write_log(val_log, "valid", should_print=False)
             run_manager.save_model({"epoch": epoch, "best_acc": run_manager.best_acc,
                                     "optimizer": run_manager.optimizer.state_dict(),
-                                    "state_dict": run_manager.net.state_dict()}, is_best=is_best)
+                                    "state_dict": run_manager.net.state_dict()}, is_best=is_best,
+                                   best_state_dict=best_sd)
 
 
 def load_models(run_manager, dynamic_net, model_path=None):
@@ -201,8 +204,10 @@ def _run_stages(kind, attr, constraint, key, train_func, run_manager, args, vali
     model_path = getattr(args, "teacher_path", None)
     if model_path:
         load_models(run_manager, net, model_path=model_path)
+        run_manager.reset_ema("warm start")
     if reorganize:
         net.re_organize_middle_weights()
+        run_manager.reset_ema("channels re-organised")
     run_manager.write_log("%.3f\t%.3f\t%s" % validate(run_manager, **validate_func_dict), "valid")
 
     stage_list = sorted(full_list, reverse=True)
@@ -227,6 +232,7 @@ def _run_stages(kind, attr, constraint, key, train_func, run_manager, args, vali
             net.re_organize_middle_weights(expand_ratio_stage=stage_info["stage"])
             from ... import distributed as dd
             dd.broadcast_module(net)   # what DistributedRunManager.broadcast() did (reference :389-390, Q5)
+            run_manager.reset_ema("channels re-organised")   # the average of the old channel order means nothing now
         run_manager.save_model(model_name="%s_stage%d.pth.tar" % (kind, stage_info["stage"]))
         if run_manager.is_root:
             with open(stage_info_path, "w") as f:

@@ -10,6 +10,7 @@ Differences that are deliberate (MI355X-first) and do not change results on one 
   * apex / tensorboardX hooks are not carried over (both absent; dead code in the reference).
 Checkpoint files, dict keys, log files and the optimizer grouping are the reference's.
 """
+import contextlib
 import json
 import math
 import os
@@ -23,6 +24,7 @@ from ... import distributed as dd
 from ... import ops
 from ...graphed import GraphedEval
 from ... import degrade as sr_degrade
+from ... import ema as sr_ema
 from ... import losses as sr_losses
 from ...utils import (AverageMeter, bucket_by_size, device_batch, psnr_from_sse, psnr_y, psnr_y_device,
                       psnr_y_per_image)
@@ -127,10 +129,11 @@ class RunConfig(object):
 
 class SRRunManager(object):
     """reference :136-549.  attrs: net, network, optimizer, run_config, device, best_acc, start_epoch, path,
-    train_criterion, test_criterion; plus `reducer` (None on one GPU)."""
+    train_criterion, test_criterion; plus `reducer` (None on one GPU) and `ema` (None without ema_decay)."""
 
     def __init__(self, path, net, run_config, init=True, measure_latency=None, no_gpu=False, mix_prec=None,
-                 num_gpus=None, args=None, loss="reference", loss_eps=sr_losses.DEFAULT_EPS, loss_ssim=0.0):
+                 num_gpus=None, args=None, loss="reference", loss_eps=sr_losses.DEFAULT_EPS, loss_ssim=0.0,
+                 ema_decay=0.0):
         if loss != "reference" and loss not in sr_losses.KINDS:
             raise ValueError("loss must be 'reference' or one of %s, got %r" % (", ".join(sr_losses.KINDS), loss))
         if not (loss_eps > 0 and math.isfinite(loss_eps)):
@@ -143,6 +146,8 @@ class SRRunManager(object):
             raise ValueError("loss_ssim belongs to the fused losses (%s), got loss='reference'" % ", ".join(sr_losses.KINDS))
         self.loss_ssim = float(loss_ssim)   # alpha of (1 - alpha) * loss + alpha * (1 - SSIM); 0: no SSIM term
         self._ssim_sum, self._ssim_steps, self.last_train_ssim = None, 0, None
+        self.ema_decay = sr_ema.check_decay(ema_decay)   # 0: no weight average; else ema.ParamEMA after every step()
+        self.ema = None
         self.path = path
         self.net = net
         self.run_config = run_config
@@ -201,6 +206,10 @@ class SRRunManager(object):
             early = self.network.early_gradient_parameters()
         self.reducer = dd.FlatGradReducer(self.network.parameters(), gather=True, early_params=early) \
             if dd.is_distributed() else None
+        if self.ema_decay > 0:
+            self.ema = sr_ema.ParamEMA(self.network.named_parameters(), self.ema_decay)
+            self.write_log("Weight EMA: decay %g (warm-up (1+t)/(10+t)); validation, best_acc and model_best use the "
+                           "averaged weights" % self.ema_decay, prefix="train")
 
     # ------------------------------------------------------------------ distributed helpers
     @property
@@ -220,10 +229,37 @@ class SRRunManager(object):
             self.reducer.arm()
 
     def step(self):
-        """gradient exchange (one flat all-reduce) + optimizer step."""
+        """gradient exchange (one flat all-reduce) + optimizer step + (with ema_decay) the weight average's update, one
+        launch.  Under data parallelism every rank updates its own shadow from parameters that are identical on all
+        ranks after the all-reduce and the same optimizer step, so the shadows stay equal and nothing is exchanged."""
         if self.reducer is not None:
             self.reducer.reduce()
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside: the network holds the averaged parameters (and its own current buffers); on exit, also by an
+        exception, the trained ones again -- one swap launch each way, at the same addresses (ema.ParamEMA.swap, which
+        clears the inference operand cache both times).  A no-op without ema_decay."""
+        if self.ema is None:
+            yield
+            return
+        self.ema.swap()
+        try:
+            yield
+        finally:
+            self.ema.swap()
+
+    def reset_ema(self, why=None):
+        """re-initialise the shadow from the parameters as they are now (updates = 0): after anything that rewrites
+        the parameters other than an optimizer step -- a warm start, a re-organisation of the channels"""
+        if self.ema is None:
+            return
+        self.ema.reset()
+        if why:
+            self.write_log("Weight EMA: re-initialised from the current parameters, updates = 0 (%s)" % why, prefix="train")
 
     def autocast(self):
         if self.mix_prec in (None, "f32"):
@@ -270,8 +306,10 @@ class SRRunManager(object):
             print(log_str)
 
     # ------------------------------------------------------------------------- checkpoints
-    def save_model(self, checkpoint=None, is_best=False, model_name=None):
-        """checkpoint/{<model_name>,model_best}.pth.tar + latest.txt (reference :253-273)"""
+    def save_model(self, checkpoint=None, is_best=False, model_name=None, best_state_dict=None):
+        """checkpoint/{<model_name>,model_best}.pth.tar + latest.txt (reference :253-273).  `best_state_dict`: what
+        model_best holds when it is not the checkpoint's own state dict (the averaged weights, taken inside
+        ema_weights()).  With ema_decay every checkpoint written here gains "ema" and "ema_decay"."""
         if not self.is_root:
             return
         if checkpoint is None:
@@ -291,12 +329,25 @@ class SRRunManager(object):
                 checkpoint["loss_eps"] = self.loss_eps
             if self.loss_ssim > 0:
                 checkpoint["loss_ssim"] = self.loss_ssim
+        if self.ema is not None:
+            checkpoint["ema_decay"] = self.ema_decay
+            if "ema" not in checkpoint:
+                checkpoint["ema"] = self.ema.state_dict()
         model_path = os.path.join(self.save_path, model_name)
         with open(os.path.join(self.save_path, "latest.txt"), "w") as fout:
             fout.write(model_path + "\n")
         torch.save(checkpoint, model_path)
         if is_best:
-            torch.save({"state_dict": checkpoint["state_dict"]}, os.path.join(self.save_path, "model_best.pth.tar"))
+            torch.save({"state_dict": checkpoint["state_dict"] if best_state_dict is None else best_state_dict},
+                       os.path.join(self.save_path, "model_best.pth.tar"))
+
+    def best_state_dict(self):
+        """a copy of the network's state dict as it is now, for save_model(best_state_dict=): called inside
+        ema_weights(), where it holds the averaged parameters.  None without ema_decay (model_best is then written from
+        the checkpoint itself, as ever)."""
+        if self.ema is None:
+            return None
+        return {k: v.detach().clone() for k, v in self.network.state_dict().items()}
 
     def load_model(self, model_fname=None):
         """reference :275-308 -- but failures are raised, not swallowed."""
@@ -314,6 +365,11 @@ class SRRunManager(object):
             self.best_acc = checkpoint["best_acc"]
         if "optimizer" in checkpoint:
             self.optimizer.load_state_dict(checkpoint["optimizer"])
+        if self.ema is not None:
+            if "ema" in checkpoint:
+                self.ema.load_state_dict(checkpoint["ema"])
+            else:
+                self.reset_ema("%s has no \"ema\" entry" % model_fname)
         return model_fname
 
     def save_config(self):
@@ -323,6 +379,8 @@ class SRRunManager(object):
         config = self.run_config.config
         if self.loss_ssim > 0:      # the one setting of the run that lives on the manager and has no other record here
             config = dict(config, loss_ssim=self.loss_ssim)
+        if self.ema_decay > 0:
+            config = dict(config, ema_decay=self.ema_decay)
         with open(run_save_path, "w") as f:
             json.dump(config, f, indent=4)
         print("Run configs dump to %s" % run_save_path)
@@ -597,10 +655,13 @@ class SRRunManager(object):
         """reference :516-541"""
         for epoch in range(self.start_epoch, self.run_config.n_epochs + warmup_epoch):
             train_loss, train_psnr = self.train_one_epoch(args, epoch, warmup_epoch, warmup_lr)
-            is_best = False
+            is_best, best_sd = False, None
             if (epoch + 1) % self.run_config.validation_frequency == 0:
-                val_loss, val_psnr = self.validate(epoch=epoch, is_test=False)
-                is_best = np.mean(val_psnr) > self.best_acc
+                with self.ema_weights():       # with ema_decay: the averaged weights are what is validated and kept
+                    val_loss, val_psnr = self.validate(epoch=epoch, is_test=False)
+                    is_best = np.mean(val_psnr) > self.best_acc
+                    if is_best:
+                        best_sd = self.best_state_dict()
                 self.best_acc = max(self.best_acc, np.mean(val_psnr))
                 self.write_log("Valid [%d/%d]\tloss %.3f\ttop-1 acc %.3f (%.3f)\tTrain top-1 %.3f\tloss %.3f\t%s" % (
                     epoch + 1 - warmup_epoch, self.run_config.n_epochs, np.mean(val_loss), np.mean(val_psnr),
@@ -608,7 +669,7 @@ class SRRunManager(object):
                     "" if self.last_train_ssim is None else "SSIM %.4f\t" % self.last_train_ssim),
                     prefix="valid", should_print=False)
             self.save_model({"epoch": epoch, "best_acc": self.best_acc, "optimizer": self.optimizer.state_dict(),
-                             "state_dict": self.network.state_dict()}, is_best=is_best)
+                             "state_dict": self.network.state_dict()}, is_best=is_best, best_state_dict=best_sd)
 
     def reset_running_statistics(self, net=None):
         from ...elastic_nn.utils import set_running_statistics

@@ -844,6 +844,38 @@ def skip_add(x, skip):
     return y
 
 
+# --------------------------------------------------------------------------------- weight EMA
+def ema_chunk():
+    """elements per row of the table of ema_update / ema_swap (host only, a multiple of 4)"""
+    return int(_C.lib().ofasr_ema_chunk())
+
+
+def _ema_table(table, rows, what):
+    _gpu(table)
+    rows = int(rows)
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.numel() < 3 * max(rows, 0):
+        raise _C.OfasrError("%s: the table is a contiguous int64 GPU tensor of at least rows x 3 words" % what)
+    return rows
+
+
+def ema_update(table, rows, w, elements=0):
+    """e = e + float32(w * float32(p - e)) over every row {parameter address, shadow address, count} of `table` (int64
+    [rows, 3] on the GPU, ema.plan_chunks): ONE launch on the current stream whatever the number of tensors
+    (ofasr_ema_update; the bits of ema.update_np).  Reads p and e, writes e.  `elements`: the rows' total count, for the
+    timer's byte accounting only (the host does not read the table)."""
+    rows = _ema_table(table, rows, "ema_update")
+    with _timed("ema_update", 3 * 4 * elements):
+        _C.check(_C.lib().ofasr_ema_update(_p(table), rows, float(w), _stream()), "ofasr_ema_update")
+
+
+def ema_swap(table, rows, elements=0):
+    """exchange the two ranges of every row of `table` (ofasr_ema_swap), one launch.  The parameters are rewritten behind
+    their version counters: the caller clears the inference operand cache (clear_infer_cache; ema.ParamEMA.swap does)."""
+    rows = _ema_table(table, rows, "ema_swap")
+    with _timed("ema_swap", 4 * 4 * elements):
+        _C.check(_C.lib().ofasr_ema_swap(_p(table), rows, _stream()), "ofasr_ema_swap")
+
+
 # --------------------------------------------------------------------------- kernel transform
 def _kt_args(chain, mats):
     ks = (ctypes.c_int * len(chain))(*chain)

@@ -23,6 +23,8 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--net", default="s4", choices=["s4", "x4"])
     ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--ema", action="store_true", help="with --checkpoint: search and export the averaged weights of a run "
+                                                       "with --ema-decay (the checkpoint's \"ema\" entry)")
     ap.add_argument("--path", default="exp/sr/search")
     ap.add_argument("--upscale", type=int, default=4, help="LR -> HR factor of every candidate (s4)")
     budget = ap.add_mutually_exclusive_group(required=True)
@@ -51,7 +53,16 @@ def parse_args(argv=None):
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     a = ap.parse_args(argv)
+    if a.ema and not a.checkpoint:
+        ap.error("--ema needs --checkpoint FILE (the averaged weights live in a training checkpoint's \"ema\" entry)")
     a.video_kw = vf.take_video_args(a)      # --video: calibrate and validate on the frames of raw YUV 4:2:0 video
+    a.weights = None
+    if a.ema:                               # refused here, before anything is set up, when the file has no average
+        import eval_ofa_net_sr as ev
+        try:
+            a.weights = ev.load_checkpoint_weights(a.checkpoint, ema=True)
+        except ValueError as e:
+            ap.error("--ema: %s" % e)
     vf.refuse_pair_for_hr_input(a.video_kw, "image" if a.net == "x4" else None, "--net x4")
     if a.test_sizes:
         a.test_sizes = [tuple(int(v) for v in s.split("x")) for s in a.test_sizes.split(",")]
@@ -80,7 +91,7 @@ def main(argv=None):
                                       allow_synthetic=True if a.synthetic else None, **kw)
     mgr = rm.SRRunManager(a.path, net, cfg, init=a.checkpoint is None, mix_prec="f32", num_gpus=1)
     if a.checkpoint:
-        net.load_weights_from_net(torch.load(a.checkpoint, map_location="cpu", weights_only=True)["state_dict"])
+        net.load_weights_from_net(ev.load_checkpoint_weights(a.checkpoint) if a.weights is None else a.weights)
     net = mgr.net
     bn_before = search.bn_buffers(net)
     calib = cfg.data_provider.build_sub_train_loader(a.calib_images, a.calib_batch)
@@ -120,7 +131,7 @@ def main(argv=None):
         snap = search.bn_buffers(net)
         space.apply(net, best)
         eutils.recalibrate_bn(net, calib, input_key=search.lr_key(net), max_batches=n_batches)
-        static = ev.export_static(net, a.export)
+        static = ev.export_static(net, a.export, ema=a.ema)
         quality = None
         if a.fitness != "psnr":      # the winner's numbers by the GPU metric, on the re-calibrated supernet path
             quality = mgr.validate_quality(net=net, data_loader=cfg.test_loader, input_key=search.lr_key(net), graphs=False,
@@ -134,6 +145,8 @@ def main(argv=None):
                   "budget_kind": "ms" if a.budget_ms is not None else "gmacs"}
         if quality is not None:
             result.update({"ssim": quality["ssim"], "fitness": a.fitness, "shave": a.shave})
+        if a.ema:
+            result["ema"] = True
         with open(os.path.join(a.export, "search.json"), "w") as f:
             json.dump(result, f, indent=1)
         print("exported to %s" % a.export)

@@ -48,11 +48,17 @@ def main():
     ap.add_argument("--loss-ssim", type=float, default=0.0, metavar="A",
                     help="weight of an SSIM term: (1 - A) * loss + A * (1 - SSIM), A in [0, 1] (0: off); needs a fused "
                          "--loss")
+    ap.add_argument("--ema-decay", type=float, default=0.0, metavar="D",
+                    help="keep an exponential moving average of the weights with decay D in [0, 1) (0: off; 0.999 is the "
+                         "usual value): validation, best_acc and model_best use it, checkpoints carry it (ema.py)")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     vf.add_degrade_args(ap)
     args = ap.parse_args()
     loss_ssim = args.__dict__.pop("loss_ssim")
+    ema_decay = args.__dict__.pop("ema_decay")
+    if not (0.0 <= ema_decay < 1.0):        # nan fails both comparisons
+        ap.error("--ema-decay must lie in [0, 1), got %r" % (ema_decay,))
     loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, args.loss, args.__dict__.pop("loss_eps"), loss_ssim)
     loss = args.__dict__.pop("loss")        # `args` goes into the run config: it stays what it always was
     video_kw = vf.take_video_args(args)     # None without --video: `args` is then what it always was
@@ -144,7 +150,7 @@ def main():
               pixelshuffle_depth_list=args.pixelshuffle_depth_list)
     run_manager = rm.SRRunManager(args.path, net, run_config, mix_prec=args.mix_prec,
                                   num_gpus=int(os.environ.get("WORLD_SIZE", "1")), args=args, loss=loss,
-                                  loss_eps=loss_eps, loss_ssim=loss_ssim)
+                                  loss_eps=loss_eps, loss_ssim=loss_ssim, ema_decay=ema_decay)
     run_manager.save_config()
 
     validate_func_dict = {"image_size_list": None, "width_mult_list": None,
@@ -156,6 +162,7 @@ def main():
         validate_func_dict["ks_list"] = sorted(args.ks_list)
         if args.teacher_path:
             ps.load_models(run_manager, net, args.teacher_path)
+            run_manager.reset_ema("warm start")      # nothing without --ema-decay
         run_manager.write_log("%.3f\t%.3f\t%s" % ps.validate(run_manager, **validate_func_dict), "valid")
         ps.train(run_manager, args, lambda _rm, epoch, is_test: ps.validate(_rm, epoch, is_test, **validate_func_dict))
     elif args.task == "depth":

@@ -37,11 +37,16 @@ def main():
     ap.add_argument("--loss-ssim", type=float, default=0.0, metavar="A",
                     help="weight of an SSIM term: (1 - A) * loss + A * (1 - SSIM), A in [0, 1] (0: off); needs a fused "
                          "--loss")
+    ap.add_argument("--ema-decay", type=float, default=0.0, metavar="D",
+                    help="keep an exponential moving average of the weights with decay D in [0, 1) (0: off; 0.999 is the "
+                         "usual value): validation, best_acc and model_best use it, checkpoints carry it (ema.py)")
     vf = importlib.import_module(PKG + ".imagenet_codebase.data_providers.video_frames")
     vf.add_video_args(ap)
     vf.add_degrade_args(ap)
     a = ap.parse_args()
     loss_eps = importlib.import_module(PKG + ".losses").check_cli(ap, a.loss, a.loss_eps, a.loss_ssim)
+    if not (0.0 <= a.ema_decay < 1.0):      # nan fails both comparisons
+        ap.error("--ema-decay must lie in [0, 1), got %r" % (a.ema_decay,))
     video_kw = vf.take_video_args(a)
     crop_kw = vf.take_crop_candidates(a, a.resident or bool(video_kw))
     crop_kw.update(vf.take_degrade(a, a.resident or bool(video_kw), video_kw))      # blurred, noisy LR inputs (degrade.py)
@@ -69,7 +74,8 @@ def main():
     net = nets.OFAMobileNetS4(ks_list=[a.ks], expand_ratio_list=[a.expand], depth_list=[a.depth],
                               pixelshuffle_depth_list=[a.pixelshuffle_depth])
     mgr = rm.SRRunManager(a.path, net, cfg, mix_prec=a.mix_prec, num_gpus=int(os.environ.get("WORLD_SIZE", "1")),
-                          args=args, loss=a.loss, loss_eps=loss_eps, loss_ssim=a.loss_ssim)
+                          args=args, loss=a.loss, loss_eps=loss_eps, loss_ssim=a.loss_ssim,
+                          ema_decay=a.ema_decay)
     mgr.save_config()
     mgr.train(args)
     if dist.is_initialized():
